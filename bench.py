@@ -3,11 +3,12 @@
 
 A "step" is one pass of the hot path (sketch -> seed lookup -> chain -> extension -> hits) over one block of synthetic ONT reads.
 Default workload = BASELINE.json configs[2]: synthetic GRCh38-scale genome (3.09 Gbp, index built on the device), map-ont, 1 M reads
-N50 ~10 kb: the read set is cut into steps + warmup DISTINCT blocks of 73 728 reads (14 + 1 by default: 1 032 192 reads in the timed
-region, no read mapped twice in it; the warm-up block is a block of its own).  `value` is the PCIe-inclusive rate of the drop-in call
-over ALL timed blocks (H2D of the reads and D2H of the hit records inside the timed region): every sub-batch is handed to
-mm355_map_batch as host buffers, in input order (contiguous chunks, the way mappy_rs.map_batch cuts them).  The rate with the reads
-already resident in HBM (mm355_map_resident) is timed afterwards on a few of the same blocks: `resident_mbases_per_s`.
+N50 ~10 kb: the read set is cut into blocks of 73 728 reads, steps + warmup DISTINCT ones under --full (14 + 1 by default: 1 032 192
+reads in the timed region, no read mapped twice in it; the warm-up block is a block of its own), at most PLAIN_MAX_BLOCKS in a plain run.
+`value` is the PCIe-inclusive rate of the drop-in call over ALL timed blocks (H2D of the reads and D2H of the hit records
+inside the timed region): every sub-batch is handed to mm355_map_batch as host buffers, in input order (contiguous chunks, the way
+mappy_rs.map_batch cuts them).  Under --full the rate with the reads already resident in HBM (mm355_map_resident) is timed afterwards
+on a few of the same blocks: `resident_mbases_per_s`.
 
 Multi-GPU (--gpus N): ONE read set of N x --reads reads is cut into N contiguous shards balanced by cumulative bases (SURVEY 8e);
 rank r maps shard r against its own replica of the index; no data-path collective.  The driver launches the ranks with
@@ -20,8 +21,18 @@ Workloads (--workload):
   human-hifi   configs[4]               same genome, map-hifi k19 w19, HiFi-like reads N(18 kb, 2.5 kb), 0.2 % error, read set seed 6
   ecoli        configs[1]               synthetic 4.64 Mbp genome (seed 1), map-ont, reads N50 ~8 kb, read set seed 2
   ecoli-hifi   configs[4] shape on the small genome
-The JSON line also carries `roofline` (dominant kernel; algorithmic bytes of SURVEY 8d / live HIP-event time on the launch stream)
-and `cpu_baseline` (the CPU oracle timed on the host cores on a bounded sample of the same reads, index built with host threads).
+The JSON line also carries `roofline` (dominant kernel; algorithmic bytes of SURVEY 8d / live HIP-event time on the launch stream,
+taken from the timed steps themselves).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what `value` and `ms_per_step` need: synthesis, index, warm-up, the N
+timed steps, the result line.  It synthesises at most PLAIN_MAX_BLOCKS distinct blocks and cycles over them when N + W is larger (the
+first warm-up block is one of its own).  `--full` adds what needs runs of its own, as before: a distinct block for every step,
+the second timed region with the reads resident in HBM (`resident_mbases_per_s`), the seed-lookup kernel alone, `cpu_baseline` (the CPU
+oracle timed on the host cores on a bounded sample of the same reads, with a record-by-record parity check of those reads) and
+`reference_on_box`.
+
+--dump-outputs DIR writes what the timed path returned for the last timed step (rank 0: every sub-batch of that block, reads in input
+order) as DIR/<name>.npy, float64 / float32, at most 64 MB: see dump_outputs().  The inputs depend only on the arguments.
 """
 import argparse
 import os as _os
@@ -51,6 +62,9 @@ def _parse_args():
     ap.add_argument("--synth-procs", type=int, default=0, help="worker processes that synthesise the reads (0 = automatic; 1 under a profiler)")
     ap.add_argument("--oversubscribe", action="store_true", help="test hook: more ranks than GPUs on the node -- rank r uses GPU r mod (GPUs visible); the JSON line is flagged `oversubscribed`")
     ap.add_argument("--bin", action="store_true", help="experiment: sort the reads of a step by length before cutting the sub-batches (untimed preprocessing the drop-in path does not do)")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: a distinct block for every step, the HBM-resident region, "
+                                                         "the seed-lookup kernel alone, the CPU baseline with its parity check, the reference if installed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the hit records of the last timed step as DIR/<name>.npy (at most 64 MB)")
     return ap.parse_args()
 
 
@@ -318,6 +332,82 @@ VALU_LANE_OPS = 256 * 4 * 32 * 2.4e9
 DP_LANE_OPS_PER_CELL = 17.0
 CHAIN_LANE_OPS_PER_PAIR = 30.0
 
+# distinct blocks a plain run synthesises (~0.5 s of host time each for the default workload); --full synthesises one per step
+PLAIN_MAX_BLOCKS = 4
+
+# --dump-outputs: per-hit fields of mm355_hit_t written as hit_<field>.npy, the budget of all files together, the size of the CIGAR / cs sample
+DUMP_HIT_FIELDS = ("rid", "target_len", "target_start", "target_end", "query_start", "query_end", "strand", "mapq", "is_primary", "NM",
+                   "match_len", "block_len", "n_cigar", "cs_len")
+DUMP_BYTES = 64 << 20
+DUMP_SAMPLE_HITS = 512
+
+
+def dump_outputs(dirn, parts, seed=0):
+    """writes what the drop-in call returned for the sub-batches `parts` [(n_reads, mm355_hits_t *)], concatenated in order:
+      hits_per_read            float64 [reads]          hits of every read
+      hit_<field>              float64 [hits]           DUMP_HIT_FIELDS of every hit record (exact: every value is below 2^53)
+      hit_cigar_op_bases       float64 [hits, 9]        bases per CIGAR operation M I D N S H P = X of every hit
+      sample_hit               float64 [s]              a seeded sample of hit indices, sorted; its full CIGARs and cs strings:
+      sample_cigar(_off)       float64                  the packed words len<<4|op, and s+1 offsets
+      sample_cs(_off)          float32 / float64        the cs bytes (ASCII codes; none when cs_len < 0), and s+1 offsets
+    When the per-hit arrays alone would exceed 5/8 of DUMP_BYTES, hit_row (float64) names the seeded sample of hits they cover."""
+    from mappy_rs import _ffi
+    hit_dt = np.dtype([(k, np.dtype(t)) for k, t in _ffi.Hit._fields_], align=True)
+    assert hit_dt.itemsize == C.sizeof(_ffi.Hit)
+    per_read, recs, opb, bufs = [], [], [], []
+    for nr, hp in parts:
+        h = hp.contents
+        per_read.append(np.diff(np.ctypeslib.as_array(h.hit_off, shape=(nr + 1,))) if nr else np.zeros(0, np.int64))
+        nh = int(h.n_hits)
+        rec = np.frombuffer(C.string_at(h.hits, nh * hit_dt.itemsize), dtype=hit_dt) if nh else np.zeros(0, hit_dt)
+        cig = np.ctypeslib.as_array(h.cigar, shape=(int(h.n_cigar),)).copy() if h.n_cigar > 0 else np.zeros(0, np.uint32)
+        sbuf = C.string_at(h.str, int(h.n_str)) if h.n_str > 0 else b""
+        nc = rec["n_cigar"].astype(np.int64)
+        tot = int(nc.sum())
+        ob = np.zeros((nh, 16))
+        if tot:
+            first = np.cumsum(nc) - nc
+            w = cig[np.repeat(rec["cigar_off"] - first, nc) + np.arange(tot)]
+            ob = np.bincount(np.repeat(np.arange(nh), nc) * 16 + (w & 15), weights=(w >> 4).astype(np.float64), minlength=nh * 16).reshape(nh, 16)
+        recs.append(rec)
+        opb.append(ob[:, :9])
+        bufs.append((cig, sbuf))
+    part_of = np.repeat(np.arange(len(recs)), [len(r) for r in recs])      # sub-batch of every hit: its CIGAR words and cs string live there
+    rec = np.concatenate(recs) if recs else np.zeros(0, hit_dt)
+    opb = np.concatenate(opb) if opb else np.zeros((0, 9))
+    nh = len(rec)
+    rng = np.random.default_rng(seed)
+    files = {"hits_per_read": np.concatenate(per_read).astype(np.float64) if per_read else np.zeros(0)}
+    row_bytes = 8 * (len(DUMP_HIT_FIELDS) + 9)
+    rows = np.arange(nh)
+    if nh * row_bytes > DUMP_BYTES * 5 // 8:
+        rows = np.sort(rng.choice(nh, DUMP_BYTES * 5 // 8 // row_bytes, replace=False))
+        files["hit_row"] = rows.astype(np.float64)
+    for k in DUMP_HIT_FIELDS:
+        files["hit_" + k] = rec[k][rows].astype(np.float64)
+    files["hit_cigar_op_bases"] = opb[rows]
+    left = DUMP_BYTES - sum(a.nbytes for a in files.values()) - 16 * (DUMP_SAMPLE_HITS + 1) - 8 * DUMP_SAMPLE_HITS
+    picked, cig, cs = [], [], []
+    for i in np.sort(rng.choice(nh, min(nh, DUMP_SAMPLE_HITS), replace=False)) if nh else []:
+        r, (cw, sb) = rec[i], bufs[part_of[i]]
+        c_ = cw[int(r["cigar_off"]):int(r["cigar_off"]) + int(r["n_cigar"])]
+        s_ = sb[int(r["cs_off"]):int(r["cs_off"]) + int(r["cs_len"])] if r["cs_len"] >= 0 else b""
+        need = 8 * len(c_) + 4 * len(s_)
+        if need > left:
+            continue
+        left -= need
+        picked.append(int(i)); cig.append(c_); cs.append(s_)
+    files["sample_hit"] = np.array(picked, np.float64)
+    files["sample_cigar"] = np.concatenate(cig).astype(np.float64) if cig else np.zeros(0)
+    files["sample_cigar_off"] = np.concatenate([[0], np.cumsum([len(c) for c in cig])]).astype(np.float64)
+    files["sample_cs"] = np.frombuffer(b"".join(cs), np.uint8).astype(np.float32)
+    files["sample_cs_off"] = np.concatenate([[0], np.cumsum([len(c) for c in cs])]).astype(np.float64)
+    assert sum(a.nbytes for a in files.values()) <= DUMP_BYTES
+    os.makedirs(dirn, exist_ok=True)
+    for k, a in files.items():
+        np.save(os.path.join(dirn, k + ".npy"), a)
+    return {k: a.shape for k, a in files.items()}
+
 
 def main():
     args = _ARGS
@@ -335,6 +425,8 @@ def main():
     K, W = max(1, args.steps), max(0, args.warmup)
     # every step maps a block of its own; the library keeps at most 64 resident batches per context (depth of them per block)
     max_blocks = 63 // depth if args.resident_value else 1 << 30   # (resident batches: 64 slots per context, slot 0 is the drop-in call's)
+    if not args.full:                                               # a plain run cycles over a few distinct blocks
+        max_blocks = min(max_blocks, PLAIN_MAX_BLOCKS)
     n_blocks = min(K + W, max_blocks)
     n_timed_blocks = min(K, n_blocks - min(W, 1)) if n_blocks > 1 else 1
 
@@ -402,7 +494,8 @@ def main():
     t0 = time.time()
     packed, rlens_np, block_bases = {}, {}, []
     resident_value = bool(args.resident_value)
-    n_res_blocks = n_timed_blocks if resident_value else (0 if args.no_resident else min(args.resident_steps, n_timed_blocks))
+    n_res_blocks = n_timed_blocks if resident_value else (0 if args.no_resident or not args.full else min(args.resident_steps, n_timed_blocks))
+    cpu_leg = args.full and not args.no_cpu and world == 1
     from mappy_rs import shard_by_bases, order_by_length
     for b in range(n_blocks):
         blk = reads[b * per_block:(b + 1) * per_block]
@@ -421,14 +514,14 @@ def main():
             if b < n_res_blocks or (resident_value and b >= n_timed_blocks):   # blocks of the HBM-resident region: uploaded before it (slot 0 is the drop-in call's)
                 _ffi.check(L.mm355_batch_select(ctxs[si % n_thr], 1 + (b % (63 // depth)) * depth + si // n_thr))
                 _ffi.check(L.mm355_batch_upload(ctxs[si % n_thr], len(pk[2]), pk[0], pk[1]))
-    cpu_sample = reads[:min(len(reads), per_block)]   # the CPU leg samples the first block
+    cpu_sample = reads[:min(len(reads), per_block)] if cpu_leg else []   # the CPU leg samples the first block
     n_reads_rank = len(reads)
     del reads
     log("[bench] %d blocks of %d reads packed (%d sub-batches of ~%d reads; %d blocks also resident in HBM for the second region) in %.1fs" %
         (n_blocks, per_block, n_blocks * n_str, per_block // n_str, n_res_blocks, time.time() - t0))
     reads_per_sub_nominal = per_block // n_str
 
-    def step_one(b, si, resident):
+    def step_one(b, si, resident, records=None):
         ctx = ctxs[si % n_thr]
         hp = C.POINTER(_ffi.Hits)()
         if resident:   # inputs already in HBM
@@ -444,7 +537,10 @@ def main():
         mapped = np.diff(off) > 0
         aligned = int(rlens_np[(b, si)][mapped].sum())
         n_hits = int(h.n_hits)
-        L.mm355_free_hits(hp)
+        if records is not None:    # --dump-outputs, last timed step: the records stay with the library until dump_outputs has read them
+            records[si] = (nr, hp)
+        else:
+            L.mm355_free_hits(hp)
         st = _ffi.Stats()
         L.mm355_get_stats(ctx, C.byref(st))
         return aligned, n_hits, st, nr, time.perf_counter()
@@ -452,11 +548,11 @@ def main():
     from concurrent.futures import ThreadPoolExecutor
     pool = ThreadPoolExecutor(n_thr)
 
-    def run_blocks(resident, blocks):
+    def run_blocks(resident, blocks, records=None):
         """one pass over every listed block: every host thread maps its own sub-batches of block after block without waiting for the other
-        threads between blocks (the barriers bracket the whole region, not a step)"""
+        threads between blocks (the barriers bracket the whole region, not a step).  records: dict that receives the records of the last block"""
         def thread(ti):
-            return [(k,) + step_one(b, si, resident) for k, b in enumerate(blocks) for si in range(ti, n_str, n_thr)]
+            return [(k,) + step_one(b, si, resident, records if k == len(blocks) - 1 else None) for k, b in enumerate(blocks) for si in range(ti, n_str, n_thr)]
         res = [r for part in pool.map(thread, range(n_thr)) for r in part]
         done = [0.0] * len(blocks)                 # when the last sub-batch of every step finished
         for r in res:
@@ -481,10 +577,10 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    def timed(resident, blocks):
+    def timed(resident, blocks, records=None):
         barrier()
         t0 = time.perf_counter()
-        aligned_tot, n_hits, agg, n_mapped = run_blocks(resident, blocks)
+        aligned_tot, n_hits, agg, n_mapped = run_blocks(resident, blocks, records)
         barrier()
         dt = time.perf_counter() - t0
         timed.step_ms = [round((b - a) * 1e3, 1) for a, b in zip([t0] + run_blocks.step_done[:-1], run_blocks.step_done)]
@@ -497,8 +593,17 @@ def main():
     warm_blocks = [(n_timed_blocks + k) % n_blocks for k in range(W)]
     if warm_blocks:
         run_blocks(resident_value, warm_blocks)
-    dt, aligned_all, bases_all, agg, n_mapped = timed(resident_value, timed_blocks)   # `value`: the drop-in call, H2D / D2H inside
+    last_step = {} if args.dump_outputs else None
+    dt, aligned_all, bases_all, agg, n_mapped = timed(resident_value, timed_blocks, last_step)   # `value`: the drop-in call, H2D / D2H inside
     step_ms = timed.step_ms
+    if last_step is not None:
+        if rank == 0:
+            t0 = time.time()
+            shapes = dump_outputs(args.dump_outputs, [last_step[si] for si in range(n_str)])
+            log("[bench] outputs of the last timed step (block %d) written to %s in %.1fs: %s" % (timed_blocks[-1], args.dump_outputs, time.time() - t0,
+                ", ".join("%s %s" % (k, "x".join(map(str, v))) for k, v in shapes.items())))
+        for _nr, hp in last_step.values():
+            L.mm355_free_hits(hp)
     if n_res_blocks and not resident_value:
         dt_r, aligned_r, _b, _agg, _n = timed(True, list(range(n_res_blocks)))      # the same reads again, resident in HBM
     else:
@@ -667,7 +772,7 @@ def main():
     barrier()
     gpu_sigs = None
     gpu_recs = None
-    if rank == 0 and not args.no_cpu and world == 1:   # (outside the timed region) the records of the reads the CPU sample will cover
+    if rank == 0 and cpu_leg:   # (outside the timed region) the records of the reads the CPU sample will cover
         import mappy_rs
         gpu_sigs = []
         import shutil as _sh
@@ -703,7 +808,7 @@ def main():
         L.mm355_ctx_destroy(ctx)
     L.mm355_index_free(idx)
     if rank == 0:
-        if not args.no_cpu and world == 1:   # after the GPU side has released its memory; rank 0 at N=1 only
+        if cpu_leg:   # after the GPU side has released its memory; rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(g, names, wl["preset"], cpu_sample, args.cpu_seconds, min(16, os.cpu_count() or 1), gpu_sigs)
             # the real minimap2 / mappy, if the box has one (it never did): timed on the same sample, records diffed -- null otherwise
             n_ref = len(gpu_recs) if gpu_recs else min(len(cpu_sample), 6144)

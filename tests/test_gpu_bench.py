@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -16,7 +17,7 @@ KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "
         "roofline", "roofline_seed_lookup", "host")
 
 
-def _check(line, steps, warmup, cpu, n_gpus=1):
+def _check(line, steps, warmup, cpu, n_gpus=1, distinct=None):
     d = json.loads(line)
     for k in KEYS:
         assert k in d, k
@@ -26,7 +27,7 @@ def _check(line, steps, warmup, cpu, n_gpus=1):
     assert d["n_gpus"] == n_gpus and d["steps"] == steps and d["warmup"] == warmup and d["scaling"] == "weak" and d["higher_is_better"] is True
     assert d["value"] > 0 and d["ms_per_step"] > 0 and d["vs_baseline"] is None and d["data"] == "synthetic"
     assert "workload" in d["config"] and "model" not in d["config"]
-    assert d["config"]["distinct_blocks_in_timed_region"] == steps          # no read mapped twice in the timed region
+    assert d["config"]["distinct_blocks_in_timed_region"] == (steps if distinct is None else distinct)   # no read mapped twice in the timed region
     for r in (d["roofline"], d["roofline_seed_lookup"], d["roofline_seed_lookup"]["four_term_B_seed"]):
         assert r["bound"] in ("hbm", "valu") and r["peak"] > 0
         assert r["achieved"] is None or abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3
@@ -55,8 +56,36 @@ def _run(cmd, timeout=900, extra_env=None, may_fail=False):
 
 
 def test_bench_json_contract_single_process():
-    line = _run([sys.executable, "bench.py", "--workload", "ecoli", "--reads", "4096", "--steps", "2", "--warmup", "1", "--cpu-seconds", "3"])
-    _check(line, 2, 1, True)
+    line = _run([sys.executable, "bench.py", "--full", "--workload", "ecoli", "--reads", "4096", "--steps", "2", "--warmup", "1", "--cpu-seconds", "3"])
+    d = _check(line, 2, 1, True)
+    assert d["resident_mbases_per_s"] > 0 and "alone" in d["roofline_seed_lookup"]
+
+
+def _load_dump(d):
+    out = {}
+    for fn in sorted(os.listdir(d)):
+        a = np.load(os.path.join(d, fn))
+        assert fn.endswith(".npy") and a.dtype in (np.float32, np.float64), fn
+        out[fn[:-4]] = a
+    assert sum(os.path.getsize(os.path.join(d, fn)) for fn in os.listdir(d)) <= 64 << 20
+    return out
+
+
+def test_bench_plain_run_and_its_outputs(tmp_path):
+    """a plain run: only the timed steps (no CPU leg, no HBM-resident region), more steps than distinct blocks (it cycles over
+    PLAIN_MAX_BLOCKS - 1 timed blocks), and --dump-outputs gives the same files for the same arguments"""
+    dumps = []
+    for tag in ("a", "b"):
+        line = _run([sys.executable, "bench.py", "--gpus", "1", "--workload", "ecoli", "--reads", "2048", "--steps", "9", "--warmup", "1",
+                     "--dump-outputs", str(tmp_path / tag)])
+        d = _check(line, 9, 1, False, distinct=3)
+        assert "cpu_baseline" not in d and "reference_on_box" not in d and d["resident_mbases_per_s"] is None
+        dumps.append(_load_dump(str(tmp_path / tag)))
+    a, b = dumps
+    assert sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a)
+    assert len(a["hits_per_read"]) == 2048 and a["hits_per_read"].sum() == len(a["hit_target_start"]) > 0
+    assert len(a["sample_hit"]) > 0 and len(a["sample_cigar"]) == a["sample_cigar_off"][-1] and len(a["sample_cs"]) == a["sample_cs_off"][-1] > 0
+    assert np.array_equal(a["hit_cigar_op_bases"][:, [0, 1, 7, 8]].sum(1), a["hit_query_end"] - a["hit_query_start"])   # M / I / = / X cover the query span
 
 
 def test_bench_under_the_distributed_launcher():
@@ -75,7 +104,7 @@ def test_two_ranks_share_the_one_gpu():
     for backend in ("nccl", "gloo"):
         s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-               "bench.py", "--gpus", "2", "--oversubscribe", "--workload", "ecoli", "--reads", "2048", "--steps", "2", "--warmup", "1", "--no-cpu", "--streams", "2", "--depth", "1"]
+               "bench.py", "--gpus", "2", "--full", "--oversubscribe", "--workload", "ecoli", "--reads", "2048", "--steps", "2", "--warmup", "1", "--no-cpu", "--streams", "2", "--depth", "1"]
         out = _run(cmd, extra_env={"MM355_BENCH_DIST_BACKEND": backend, "MM355_HOST_THREADS": "4"}, may_fail=backend == "nccl")
         if isinstance(out, str):
             break

@@ -5,7 +5,7 @@
 # deleted: gpurun merges at most 64 MiB back.
 out=$GRAFT_REPO_ROOT/$1; mkdir -p $out
 cd $GRAFT_REPO_ROOT
-timeout 900 python bench.py > $out/bench_default.json 2> $out/bench_default.err
+timeout 900 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 # (the driver command was run in the two earlier calls of this script: 1452.8 and 1430.8 Mbases/s)
 cd /tmp; export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kstats -o r04 -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 1 --no-cpu --no-resident > $out/bench_under_rocprof.json 2> $out/bench_under_rocprof.err
