@@ -125,7 +125,10 @@ int mm355_ctx_create(const mm355_index_t *idx, int device_id, mm355_ctx_t **out)
 void mm355_ctx_destroy(mm355_ctx_t *ctx);
 
 /* --- the hot path: replaces mm_map (+ mm_gen_cs / mm_gen_MD) for a whole batch of reads.
- * seqs[i] need not be NUL-terminated.  flags: bit0 = cs (short form), bit1 = MD. --- */
+ * seqs[i] need not be NUL-terminated.  flags: bit0 = cs (short form), bit1 = MD.
+ * Without MM_F_CIGAR in mo->flag the call maps chain-only (minimap2 without -c): seeds, chains, regions, MAPQ from the chains, no extension.
+ * Its hits have n_cigar = 0, cs_len = md_len = -1, NM = dp_max = dp_max2 = dp_score = 0; cs / MD flags are MM355_EINVAL; an index without
+ * sequence (MM_I_NO_SEQ) is mappable.  The region logic runs on the device (k_regs); MM355_REGS_HOST=1 runs it on the host for every read. --- */
 #define MM355_OUT_CS 1
 #define MM355_OUT_MD 2
 int mm355_map_batch(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs,
@@ -170,13 +173,18 @@ typedef struct {
 	 * sort (LDS), 7 literal radix_sort_128x emulation (reads with equal keys), 8 chain segments, 9 chain (long segments, a wave each),
 	 * 10 chain (short segments, a lane each), 11 chain backtrack, 12 / 13 / 14 mg_lchain_rmq sort / recurrence / backtrack, 15 extension
 	 * gather, 16 extension backtrack (CIGAR), 17 mm_update_extra + cs walk, 18 read codes, 19 chain / anchor pack; the literal emulation by kernel:
-	 * 7 k_sort_level_mw<1024> (all its levels), 20 k_sort_level_mw<256>, 21 k_sort_tasks, 22 its plain sort / copy / tcnt of the tie reads */
+	 * 7 k_sort_level_mw<1024> (all its levels), 20 k_sort_level_mw<256>, 21 k_sort_tasks, 22 its plain sort / copy / tcnt of the tie reads;
+	 * 23 the chain-only region stage (k_regs) */
 	double ms_kernel[24];
 	int64_t chain_pairs_big;                     /* k_chain_big's share of chain_pairs */
 	int64_t n_a_literal;                         /* anchors (all of them, culled ones included) of the reads that were sorted literally */
 	int64_t n_v_rmq;                             /* anchors mg_lchain_rmq chained on the device */
 	int64_t n_dp_band, n_dp_band_redo;           /* gap fills run on a diagonal band with a sufficiency proof / of those, run again on the full matrix */
 	int64_t n_rounds_split;                      /* extension rounds whose direction matrices did not fit the HBM budget and were cut into several launches */
+	/* chain-only calls (mo->flag without MM_F_CIGAR): reads whose region logic ran on the device (k_regs, kernel time in ms_kernel[23]) /
+	   reads that took the host path (the RMQ stage left them to the host, an argument of logf beyond the device table, a strand_retained
+	   comparison on a divergence that pow() rounding could move, or MM355_REGS_HOST=1) */
+	int64_t n_regs_dev, n_regs_host;
 } mm355_stats_t;
 
 /* sketch: minimizers of each read (mm_sketch). mz_off[n_reads+1] host array is filled; mz = (x,y) pairs */

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include "mm355_glue.h"
 #include "mm355_prof.h"
+#include "mm355_regs.h"
 #include <atomic>
 #include <chrono>
 #include <string.h>
@@ -809,7 +810,7 @@ void mm355_glue_chain_rmq(const mm355_index *mi, const mm355_mapopt_t *opt, Read
 }
 
 // ================================================================== stage 1: after the chain kernels
-void mm355_glue_pre_align(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, int rmq_state)
+void mm355_glue_regions(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, int rmq_state)
 {
 	const int qlen = rs.qlen;
 	uint32_t hash = 0;   // qname is NULL through the reference (the L2 crate passes null)
@@ -850,6 +851,12 @@ void mm355_glue_pre_align(const mm355_index *mi, const mm355_mapopt_t *opt, Read
 	}
 	n = filter_strand_retained(n, rs.regs.data());
 	rs.regs.resize(n);
+}
+
+void mm355_glue_pre_align(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, int rmq_state)
+{
+	mm355_glue_regions(mi, opt, rs, rmq_state);
+	const int qlen = rs.qlen, n = (int)rs.regs.size();
 	ProfScope pfc(PF_PRE_CODES);
 	// U:align.c::mm_align_skeleton prologue: query codes and anchor squeeze
 	static const struct Nt4Lut { uint8_t t[256]; Nt4Lut() { for (int c = 0; c < 256; ++c) t[c] = (uint8_t)mm_nt4((uint8_t)c); } } lut;
@@ -1790,6 +1797,25 @@ void mm355_glue_finish(const mm355_index *mi, const mm355_mapopt_t *opt, ReadSta
 			if (flags & MM355_OUT_CS) { h.cs_off = (int64_t)str.size(); h.cs_len = (int64_t)r->p->cs.size(); str += r->p->cs; str += '\0'; }
 			if (flags & MM355_OUT_MD) { h.md_off = (int64_t)str.size(); h.md_len = (int64_t)r->p->md.size(); str += r->p->md; str += '\0'; }
 		}
+		hits.push_back(h);
+	}
+}
+
+// ================================================================== chain-only (no MM_F_CIGAR): U:map.c::align_regs returns at once, then
+// U:hit.c::mm_set_mapq on its r->p == NULL branch -- no filter_regs, hit_sort or second set_parent.  The host path of the reads that the
+// device's region stage (mm355_regs.h) does not take.
+void mm355_glue_chain_finish(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, std::vector<mm355_hit_t> &hits)
+{
+	const int n = (int)rs.regs.size();
+	set_mapq(n, rs.regs.data(), opt->min_chain_score, opt->a, rs.rep_len);
+	for (int i = 0; i < n; ++i) {
+		const Reg *r = &rs.regs[i];
+		Mm355Reg t;
+		memset(&t, 0, sizeof(t));
+		t.qs = r->qs; t.qe = r->qe; t.rev = r->rev; t.rid = r->rid; t.rs = r->rs; t.re = r->re; t.mlen = r->mlen; t.blen = r->blen;
+		t.parent = r->parent; t.id = r->id; t.score0 = r->score0; t.cnt = r->cnt; t.n_sub = r->n_sub; t.subsc = r->subsc;
+		mm355_hit_t h;
+		mm355r_hit(&t, r->mapq, mi->seq_len.data(), &h);
 		hits.push_back(h);
 	}
 }

@@ -89,6 +89,10 @@ void mm355_glue_chain_rmq(const mm355_index *mi, const mm355_mapopt_t *opt, Read
 // here; MM355_RMQ_HOST: rs.a holds the chained anchors already sorted by x, mg_lchain_rmq runs here; -1: the stage did not run, the
 // rescue test, the sort and mg_lchain_rmq all run here (MM355_RMQ_ON_HOST=1)
 void mm355_glue_pre_align(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, int rmq_state);
+// its first half alone: re-chain (if triggered), gen_regs, set_parent + select_sub, est_err, filter_strand_retained -> rs.regs
+void mm355_glue_regions(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, int rmq_state);
+// chain-only (no MM_F_CIGAR), after mm355_glue_regions: MAPQ from the chains and the hit records, in the order of rs.regs
+void mm355_glue_chain_finish(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, std::vector<mm355_hit_t> &hits);
 // stage 2: advance the skeleton of one read as far as cached DP results allow; appends missing DP problems to `reqs`.
 // returns true when the read needs no more DP.
 bool mm355_glue_align_step(const mm355_index *mi, const mm355_mapopt_t *opt, int read_id, ReadState &rs, std::vector<DpReq> &reqs, int flags);

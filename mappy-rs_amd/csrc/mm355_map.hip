@@ -307,6 +307,7 @@ extern "C" int mm355_batch_upload(mm355_ctx_t *c, int64_t n_reads, const char *c
 extern "C" int mm355_map_batch(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens, int flags, mm355_hits_t **out)
 {
 	*out = 0;
+	if (mo && !(mo->flag & MMF_CIGAR) && (flags & (MM355_OUT_CS | MM355_OUT_MD))) return MM355_EINVAL;   // cs / MD need the base-level alignment
 	int rc = mm355_batch_upload(c, n_reads, seqs, lens);
 	if (rc) return rc;
 	return mm355_map_resident(c, mo, flags, out);
@@ -320,6 +321,8 @@ extern "C" int mm355_map_resident(mm355_ctx_t *c, const mm355_mapopt_t *mo, int 
 	if (c->mi == 0) return MM355_ENOIDX;
 	int rc = mm355_check_opts(mo, c->mi);
 	if (rc) return rc;
+	const bool chain_only = !(mo->flag & MMF_CIGAR);   // minimap2 without -c: regions and MAPQ from the chains, no extension
+	if (chain_only && (flags & (MM355_OUT_CS | MM355_OUT_MD))) return MM355_EINVAL;
 	HIPCHK(hipSetDevice(c->dev));
 	const double t_start = now_ms();
 	const int64_t cpu_start = thread_cpu_ns(); tl_helper_cpu_ns = 0;
@@ -355,8 +358,21 @@ extern "C" int mm355_map_resident(mm355_ctx_t *c, const mm355_mapopt_t *mo, int 
 			FRONT_STAGE("f:backtrack", mm355_run_backtrack(c, pr));
 		}
 		FRONT_STAGE("f:rmq", mm355_run_rmq(c, mo, pr));                  // row a9: long-join re-chain / primary RMQ chainer on the device
-		FRONT_STAGE("f:codes", mm355_run_read_codes(c));
+		if (!chain_only) FRONT_STAGE("f:codes", mm355_run_read_codes(c));
 #undef FRONT_STAGE
+	}
+	if (chain_only) {   // the chains are on the device: regions, MAPQ and records there (mm355_regs.hip); no pack, no extension rounds
+		tv_front = now_ms() - tv0; trace_add(c, "front", tv0, now_ms());
+		const double tr0 = now_ms();
+		if ((rc = mm355_map_chain_only(c, mo, dl, out))) return rc;
+		trace_add(c, "regs", tr0, now_ms());
+		mm355_timers_resolve(c);
+		if (verbose) fprintf(stderr, "[mm355] map_resident (chain-only): front %.1f ms | regions %.1f (%lld reads on the device, %lld on the host) | total %.1f\n",
+		                     tv_front, now_ms() - tr0, (long long)c->stats.n_regs_dev, (long long)c->stats.n_regs_host, now_ms() - t_start);
+		c->stats.ms_host = now_ms() - tr0;
+		c->stats.ms_total = now_ms() - t_start;
+		c->stats.host_cpu_ms = (double)(thread_cpu_ns() - cpu_start + tl_helper_cpu_ns) * 1e-6;
+		return 0;
 	}
 	HostBatch &hb = c->hb;
 	tv_front = now_ms() - tv0; trace_add(c, "front", tv0, now_ms()); tv0 = now_ms();

@@ -99,6 +99,8 @@ struct mm355_ctx {
 	DBuf rq;       // per-read query codes fwd|rev
 	DBuf rmq_list, rmq_flag; HBuf h_rmq;   // device mg_lchain_rmq: listed reads, per-read state
 	DBuf x_jobs, x_cig, x_cs, x_out, x_dense; HBuf h_xjobs, h_xcig, h_xout, h_xcs;   // k_extra (mm_update_extra's walk + cs on the device)
+	DBuf logt, regs_scr, regs_in, regs_sel; HBuf h_regs_in, h_regs_out, h_regs_sel;  // chain-only region stage (mm355_regs.hip): host-logf table, scratch + rows, read tables
+	bool logt_ok = false;
 	mm355_stats_t stats;
 	hipEvent_t ev0 = 0, ev1 = 0;
 	std::vector<hipEvent_t> tev; std::vector<double*> tacc; int n_tpend = 0;   // lazy stage timers (EvTimer, mm355_kt)
@@ -127,6 +129,9 @@ int mm355_run_chain(mm355_ctx *ctx, const DevParams &pr);
 int mm355_run_backtrack(mm355_ctx *ctx, const DevParams &pr);
 int mm355_run_chain_skip(mm355_ctx *c);
 int mm355_run_rmq(mm355_ctx *c, const mm355_mapopt_t *mo, const DevParams &pr);   // mg_lchain_rmq on the device: long-join re-chain, or the primary chainer of MM_F_RMQ presets
+// chain-only tail of a batch (mo->flag without MM_F_CIGAR), after mm355_run_rmq: regions, MAPQ and hit records on the device (k_regs), the
+// reads it does not take on the host; qlen[i] = 0 for reads that are not mapped (empty, longer than max_qlen)
+int mm355_map_chain_only(mm355_ctx *c, const mm355_mapopt_t *mo, const std::vector<int32_t> &qlen, mm355_hits_t **out);
 
 // time one launch group on the context's stream with HIP events (the stream the kernels are launched on)
 // Stage timers.  EvTimer records a pair of events around the launches of a stage and does NOT synchronise: the pairs are turned into

@@ -1,0 +1,355 @@
+// mm355_regs.h -- the chain-only tail of a read (mapping without MM_F_CIGAR): chains -> regions -> primary / secondary selection ->
+// divergence estimate -> MAPQ -> hit records.  U:map.c::mm_map_frag after the chainers, with U:map.c::align_regs returning at once
+// (no MM_F_CIGAR) and U:hit.c::mm_set_mapq on its r->p == NULL branch.  Same steps, same order and the same float / double expressions as
+// mm355_glue.cpp's region part (gen_regs, set_parent, select_sub, est_err, filter_strand_retained) and its set_mapq.
+//
+// One read, sequential, on caller-provided scratch: compiled __host__ __device__ under hipcc (k_regs of mm355_regs.hip runs it on the
+// device, a lane per read) and as plain C++ under g++ (tests/host_harness/regs_host.cpp holds it against the oracle).
+//
+// Two library calls do not agree between the device and glibc bit for bit, so the device never decides with them on its own:
+//   logf  (mm_set_mapq): the arguments are integers (chain score, n_sub + 1); the values come from a table filled with the host's logf.
+//         An argument beyond the table sends the read to the host.
+//   pow   (mm_est_err): the result only reaches the records through filter_strand_retained's comparisons.  A region whose float divergence
+//         could change under a few ulp of error in pow is marked; a read whose comparisons read a marked divergence goes to the host.
+#pragma once
+#include "../../include/mm355.h"
+#include "mm355_core.h"
+#include <math.h>
+
+#define MM355_PARENT_UNSET   (-1)
+#define MM355_PARENT_TMP_PRI (-2)
+
+struct Mm355Reg {           // the fields of U:minimap.h::mm_reg1_t the chain-only tail reads or writes
+	int32_t id, parent, cnt, rid, score, score0;
+	int32_t qs, qe, rs, re, as, mlen, blen, subsc, n_sub;
+	uint32_t hash, rev, strand_retained, div_unsure;
+	float div;
+};
+
+struct Mm355RegsOpt {       // from mm355_mapopt_t + the index
+	int64_t flag;
+	float mask_level, pri_ratio;
+	int32_t mask_len, best_n, min_diff, min_strand_sc, min_chain_score, seed;
+};
+
+struct Mm355RegsScratch {   // n_u entries each
+	Mm355Reg *r;
+	mm128 *z;
+	uint64_t *cov;
+	int32_t *w, *tmp;
+};
+
+// what a read hands back when the device may not decide it
+#define MM355_REGS_DEFER_LOG  1
+#define MM355_REGS_DEFER_POW  2
+
+MM_HD uint32_t mm355r_wang32(uint32_t key)
+{
+	key += ~(key << 15); key ^= (key >> 10); key += (key << 3); key ^= (key >> 6); key += ~(key << 11); key ^= (key >> 16);
+	return key;
+}
+MM_HD uint64_t mm355r_hash64(uint64_t key)
+{
+	key = (~key + (key << 21)); key = key ^ key >> 24; key = ((key + (key << 3)) + (key << 8)); key = key ^ key >> 14;
+	key = ((key + (key << 2)) + (key << 4)); key = key ^ key >> 28; key = (key + (key << 31));
+	return key;
+}
+// U:map.c::mm_map_frag: the read hash without a query name (the crate passes none)
+MM_HD uint32_t mm355r_read_hash(int32_t qlen, int32_t seed)
+{
+	uint32_t h = 0;
+	h ^= mm355r_wang32((uint32_t)qlen) + mm355r_wang32((uint32_t)seed);
+	return mm355r_wang32(h);
+}
+
+// in-place heap sort (the keys sorted here are unique as a whole, so any sort gives the radix sorts' order)
+MM_HD bool mm355r_lt(const mm128 &a, const mm128 &b) { return a.x < b.x || (a.x == b.x && a.y < b.y); }
+MM_HD bool mm355r_lt(uint64_t a, uint64_t b) { return a < b; }
+template <typename T>
+MM_HD void mm355r_sift(T *v, int i, int n)
+{
+	for (;;) {
+		int c = 2 * i + 1;
+		if (c >= n) return;
+		if (c + 1 < n && mm355r_lt(v[c], v[c + 1])) ++c;
+		if (!mm355r_lt(v[i], v[c])) return;
+		T t = v[i]; v[i] = v[c]; v[c] = t;
+		i = c;
+	}
+}
+template <typename T>
+MM_HD void mm355r_sort(T *v, int n)
+{
+	for (int i = n / 2 - 1; i >= 0; --i) mm355r_sift(v, i, n);
+	for (int e = n - 1; e > 0; --e) { T t = v[0]; v[0] = v[e]; v[e] = t; mm355r_sift(v, 0, e); }
+}
+
+MM_HD void mm355r_set_coor(Mm355Reg *r, int32_t qlen, const mm128 *a)
+{   // U:hit.c::mm_reg_set_coor + reg_fuzzy_len
+	int32_t k = r->as, q_span = (int32_t)(a[k].y >> 32 & 0xff);
+	r->rev = (uint32_t)(a[k].x >> 63);
+	r->rid = (int32_t)(a[k].x << 1 >> 33);
+	r->rs = (int32_t)a[k].x + 1 > q_span? (int32_t)a[k].x + 1 - q_span : 0;
+	r->re = (int32_t)a[k + r->cnt - 1].x + 1;
+	if (!r->rev) {
+		r->qs = (int32_t)a[k].y + 1 - q_span;
+		r->qe = (int32_t)a[k + r->cnt - 1].y + 1;
+	} else {
+		r->qs = qlen - ((int32_t)a[k + r->cnt - 1].y + 1);
+		r->qe = qlen - ((int32_t)a[k].y + 1 - q_span);
+	}
+	r->mlen = r->blen = 0;
+	if (r->cnt <= 0) return;
+	r->mlen = r->blen = (int32_t)(a[r->as].y >> 32 & 0xff);
+	for (int i = r->as + 1; i < r->as + r->cnt; ++i) {
+		int span = (int)(a[i].y >> 32 & 0xff);
+		int tl = (int32_t)a[i].x - (int32_t)a[i-1].x;
+		int ql = (int32_t)a[i].y - (int32_t)a[i-1].y;
+		r->blen += tl > ql? tl : ql;
+		r->mlen += tl > span && ql > span? span : tl < ql? tl : ql;
+	}
+}
+
+// U:hit.c::mm_gen_regs: radix_sort_128x on x (stable) then a reversal = x descending, equal x in descending index order.  z.y's high word
+// (the first anchor) grows with the index, so an ascending (x, y) sort followed by the same reversal gives that order.
+MM_HD int mm355r_gen_regs(uint32_t hash, int32_t qlen, int n_u, const uint64_t *u, const mm128 *a, mm128 *z, Mm355Reg *r)
+{
+	int k = 0;
+	for (int i = 0; i < n_u; ++i) {
+		uint32_t h = (uint32_t)mm355r_hash64((mm355r_hash64(a[k].x) + mm355r_hash64(a[k].y)) ^ hash);
+		z[i].x = u[i] ^ h;
+		z[i].y = (uint64_t)k << 32 | (uint32_t)(int32_t)u[i];
+		k += (int32_t)u[i];
+	}
+	mm355r_sort(z, n_u);
+	for (int i = 0; i < n_u; ++i) {
+		const mm128 zi = z[n_u - 1 - i];
+		Mm355Reg *ri = &r[i];
+		memset(ri, 0, sizeof(*ri));
+		ri->id = i;
+		ri->parent = MM355_PARENT_UNSET;
+		ri->score = ri->score0 = (int32_t)(zi.x >> 32);
+		ri->hash = (uint32_t)zi.x;
+		ri->cnt = (int32_t)zi.y;
+		ri->as = (int32_t)(zi.y >> 32);
+		ri->div = -1.0f;
+		mm355r_set_coor(ri, qlen, a);
+	}
+	return n_u;
+}
+
+// U:hit.c::mm_set_parent without extension results (r->p == NULL everywhere)
+MM_HD void mm355r_set_parent(float mask_level, int mask_len, int n, Mm355Reg *r, int hard_mask_level, uint64_t *cov, int32_t *w)
+{
+	if (n <= 0) return;
+	for (int i = 0; i < n; ++i) r[i].id = i;
+	int k = 1, j;
+	w[0] = 0, r[0].parent = 0;
+	for (int i = 1; i < n; ++i) {
+		Mm355Reg *ri = &r[i];
+		int si = ri->qs, ei = ri->qe, n_cov = 0, uncov_len = 0;
+		if (!hard_mask_level) {
+			for (j = 0; j < k; ++j) {
+				const Mm355Reg *rp = &r[w[j]];
+				int sj = rp->qs, ej = rp->qe;
+				if (ej <= si || sj >= ei) continue;
+				if (sj < si) sj = si;
+				if (ej > ei) ej = ei;
+				cov[n_cov++] = (uint64_t)sj << 32 | (uint32_t)ej;
+			}
+			if (n_cov == 0) {
+				w[k++] = i, ri->parent = i, ri->n_sub = 0;
+				continue;
+			}
+			int x = si;
+			mm355r_sort(cov, n_cov);
+			for (int jj = 0; jj < n_cov; ++jj) {
+				if ((int)(cov[jj] >> 32) > x) uncov_len += (int)(cov[jj] >> 32) - x;
+				x = (int32_t)cov[jj] > x? (int32_t)cov[jj] : x;
+			}
+			if (ei > x) uncov_len += ei - x;
+		}
+		for (j = 0; j < k; ++j) {
+			Mm355Reg *rp = &r[w[j]];
+			int sj = rp->qs, ej = rp->qe, min, max, ol;
+			if (ej <= si || sj >= ei) continue;
+			min = ej - sj < ei - si? ej - sj : ei - si;
+			max = ej - sj > ei - si? ej - sj : ei - si;
+			ol = si < sj? (ei < sj? 0 : ei < ej? ei - sj : ej - sj) : (ej < si? 0 : ej < ei? ej - si : ei - si);
+			if ((float)ol / min - (float)uncov_len / max > mask_level && uncov_len <= mask_len) {
+				const int sci = ri->score;
+				ri->parent = rp->parent;
+				rp->subsc = rp->subsc > sci? rp->subsc : sci;
+				if (ri->cnt >= rp->cnt) ++rp->n_sub;
+				break;
+			}
+		}
+		if (j == k) w[k++] = i, ri->parent = i, ri->n_sub = 0;
+	}
+}
+
+// U:hit.c::mm_sync_regs (ids are region indices here: tmp needs n entries)
+MM_HD void mm355r_sync_regs(int n, Mm355Reg *r, int32_t *tmp, int n_tmp)
+{
+	if (n <= 0) return;
+	for (int i = 0; i < n_tmp; ++i) tmp[i] = -1;
+	for (int i = 0; i < n; ++i) if (r[i].id >= 0 && r[i].id < n_tmp) tmp[r[i].id] = i;
+	for (int i = 0; i < n; ++i) {
+		Mm355Reg *ri = &r[i];
+		ri->id = i;
+		if (ri->parent == MM355_PARENT_TMP_PRI) ri->parent = i;
+		else if (ri->parent >= 0 && ri->parent < n_tmp && tmp[ri->parent] >= 0) ri->parent = tmp[ri->parent];
+		else ri->parent = MM355_PARENT_UNSET;
+	}
+}
+
+// U:hit.c::mm_select_sub with check_strand = 1 (the pre-extension call)
+MM_HD int mm355r_select_sub(float pri_ratio, int min_diff, int best_n, int min_strand_sc, int n, Mm355Reg *r, int32_t *tmp)
+{
+	if (!(pri_ratio > 0.0f && n > 0)) return n;
+	int k = 0, n_2nd = 0;
+	for (int i = 0; i < n; ++i) {
+		const int p = r[i].parent;
+		if (p == i) {
+			r[k++] = r[i];
+		} else if ((r[i].score >= r[p].score * pri_ratio || r[i].score + min_diff >= r[p].score) && n_2nd < best_n) {
+			if (!(r[i].qs == r[p].qs && r[i].qe == r[p].qe && r[i].rid == r[p].rid && r[i].rs == r[p].rs && r[i].re == r[p].re))
+				r[k++] = r[i], ++n_2nd;
+		} else if (n_2nd < best_n && r[i].score > min_strand_sc && r[p].rev != r[i].rev) {
+			r[i].strand_retained = 1;
+			r[k++] = r[i], ++n_2nd;
+		}
+	}
+	if (k != n) mm355r_sync_regs(k, r, tmp, n);
+	return k;
+}
+
+MM_HD int32_t mm355r_for_qpos(int32_t qlen, const mm128 *a)
+{
+	int32_t x = (int32_t)a->y, q_span = (int32_t)(a->y >> 32 & 0xff);
+	if (a->x >> 63) x = qlen - 1 - (x + 1 - q_span);
+	return x;
+}
+
+// U:esterr.c::mm_est_err; div_unsure marks a divergence that a few ulp of error in pow() could move to another float
+MM_HD void mm355r_est_err(const uint32_t *seq_len, int32_t qlen, int n, Mm355Reg *r, const mm128 *a, int32_t n_mini, const uint64_t *mini_pos)
+{
+	uint64_t sum_k = 0;
+	if (n_mini == 0) return;
+	for (int i = 0; i < n_mini; ++i) sum_k += mini_pos[i] >> 32 & 0xff;
+	const float avg_k = (float)sum_k / n_mini;
+	for (int i = 0; i < n; ++i) {
+		Mm355Reg *ri = &r[i];
+		int32_t st, en, j, k, n_match, n_tot, l_ref;
+		ri->div = -1.0f;
+		if (ri->cnt == 0) continue;
+		{   // get_mini_idx
+			int32_t x = mm355r_for_qpos(qlen, ri->rev? &a[ri->as + ri->cnt - 1] : &a[ri->as]), L = 0, R = n_mini - 1;
+			st = -1;
+			while (L <= R) {
+				int32_t m = (int32_t)(((uint64_t)L + R) >> 1), y = (int32_t)mini_pos[m];
+				if (y < x) L = m + 1; else if (y > x) R = m - 1; else { st = m; break; }
+			}
+		}
+		en = st;
+		if (st < 0) continue;
+		l_ref = (int32_t)seq_len[ri->rid];
+		for (k = 1, j = st + 1, n_match = 1; j < n_mini && k < ri->cnt; ++j) {
+			int32_t x = mm355r_for_qpos(qlen, ri->rev? &a[ri->as + ri->cnt - 1 - k] : &a[ri->as + k]);
+			if (x == (int32_t)mini_pos[j]) ++k, en = j, ++n_match;
+		}
+		n_tot = en - st + 1;
+		if (ri->qs > avg_k && ri->rs > avg_k) ++n_tot;
+		if (qlen - ri->qs > avg_k && l_ref - ri->re > avg_k) ++n_tot;
+		if (n_match >= n_tot) { ri->div = 0.0f; continue; }
+		const double pw = pow((double)n_match / n_tot, 1.0 / avg_k);
+		ri->div = (float)(1.0 - pw);
+		// pw lies in (0, 1): 1.0 - pw is exact for pw >= 0.5 and loses at most an ulp below; a relative error of 2^-48 in pw covers any
+		// correctly-rounded-within-a-few-ulp pow on either side
+		const float lo = (float)(1.0 - pw * (1.0 + 0x1p-48)), hi = (float)(1.0 - pw * (1.0 - 0x1p-48));
+		ri->div_unsure = lo != hi;
+	}
+}
+
+// U:hit.c::mm_filter_strand_retained; returns -1 when a comparison reads an unsure divergence
+MM_HD int mm355r_filter_strand_retained(int n, Mm355Reg *r)
+{
+	for (int i = 0; i < n; ++i)
+		if (r[i].strand_retained && (r[i].div_unsure || r[r[i].parent].div_unsure)) return -1;
+	int k = 0;
+	for (int i = 0; i < n; ++i) {
+		const int p = r[i].parent;
+		if (!r[i].strand_retained || r[i].div < r[p].div * 5.0f || r[i].div < 0.01f) {
+			if (k < i) r[k++] = r[i]; else ++k;
+		}
+	}
+	return k;
+}
+
+// logf of a positive integer from the host-filled table; false when the argument is beyond it
+MM_HD bool mm355r_logf(const float *tab, int32_t n_tab, int64_t x, float *out)
+{
+	if (x < 1 || x >= n_tab) return false;
+	*out = tab[x];
+	return true;
+}
+
+// U:hit.c::mm_set_mapq with r->p == NULL for every region and no inversion (set_inv_mapq has nothing to do); false: an argument of logf is
+// beyond the table
+MM_HD bool mm355r_set_mapq(int n, Mm355Reg *r, int min_chain_sc, int rep_len, const float *logt, int32_t n_logt, uint32_t *mapq)
+{
+	const float q_coef = 40.0f;
+	int64_t sum_sc = 0;
+	if (n == 0) return true;
+	for (int i = 0; i < n; ++i) if (r[i].parent == r[i].id) sum_sc += r[i].score;
+	const float uniq_ratio = (float)sum_sc / (sum_sc + rep_len);
+	for (int i = 0; i < n; ++i) {
+		const Mm355Reg *ri = &r[i];
+		if (ri->parent == ri->id) {
+			int q, subsc;
+			float pen_s1 = (ri->score > 100? 1.0f : 0.01f * ri->score) * uniq_ratio;
+			float pen_cm = ri->cnt > 10? 1.0f : 0.1f * ri->cnt;
+			pen_cm = pen_s1 < pen_cm? pen_s1 : pen_cm;
+			subsc = ri->subsc > min_chain_sc? ri->subsc : min_chain_sc;
+			const float x = (float)subsc / ri->score0;
+			float ls, ln;
+			if (!mm355r_logf(logt, n_logt, ri->score, &ls) || !mm355r_logf(logt, n_logt, (int64_t)ri->n_sub + 1, &ln)) return false;
+			q = (int)(pen_cm * q_coef * (1.0f - x) * ls);
+			q -= (int)(4.343f * ln + .499f);
+			q = q > 0? q : 0;
+			mapq[i] = q < 60? q : 60;
+		} else mapq[i] = 0;
+	}
+	return true;
+}
+
+MM_HD void mm355r_hit(const Mm355Reg *r, uint32_t mapq, const uint32_t *seq_len, mm355_hit_t *h)
+{
+	memset(h, 0, sizeof(*h));
+	h->query_start = r->qs; h->query_end = r->qe; h->strand = r->rev? -1 : 1; h->rid = r->rid;
+	h->target_len = (int32_t)seq_len[r->rid]; h->target_start = r->rs; h->target_end = r->re;
+	h->match_len = r->mlen; h->block_len = r->blen; h->mapq = mapq; h->is_primary = r->parent == r->id;
+	h->cs_len = h->md_len = -1;
+	h->score0 = r->score0; h->cnt = r->cnt; h->n_sub = r->n_sub; h->subsc = r->subsc;
+}
+
+// the whole tail of one read.  Returns the number of hit rows written to `out` (at most n_u), or -MM355_REGS_DEFER_* when the read must
+// take the host path.  `mapq` is scratch of n_u words.
+MM_HD int mm355_regs_read(const Mm355RegsOpt &o, const uint32_t *seq_len, int32_t qlen, int32_t rep_len, int n_u, const uint64_t *u, const mm128 *a,
+                          int32_t n_mini, const uint64_t *mini_pos, const float *logt, int32_t n_logt, const Mm355RegsScratch &s, uint32_t *mapq,
+                          mm355_hit_t *out)
+{
+	if (n_u <= 0 || qlen <= 0) return 0;
+	Mm355Reg *r = s.r;
+	int n = mm355r_gen_regs(mm355r_read_hash(qlen, o.seed), qlen, n_u, u, a, s.z, r);
+	if (!(o.flag & MMF_ALL_CHAINS)) {
+		mm355r_set_parent(o.mask_level, o.mask_len, n, r, (int)(o.flag & MMF_HARD_MLEVEL), s.cov, s.w);
+		n = mm355r_select_sub(o.pri_ratio, o.min_diff, o.best_n, o.min_strand_sc, n, r, s.tmp);
+	}
+	mm355r_est_err(seq_len, qlen, n, r, a, n_mini, mini_pos);
+	n = mm355r_filter_strand_retained(n, r);
+	if (n < 0) return -MM355_REGS_DEFER_POW;
+	if (!mm355r_set_mapq(n, r, o.min_chain_score, rep_len, logt, n_logt, mapq)) return -MM355_REGS_DEFER_LOG;
+	for (int i = 0; i < n; ++i) mm355r_hit(&r[i], mapq[i], seq_len, &out[i]);
+	return n;
+}

@@ -1,0 +1,190 @@
+// mm355_regs.hip -- the chain-only tail of a batch (mapping without MM_F_CIGAR, minimap2's default output mode): after the chainers
+// (mm355_run_rmq) the chains of every read are still in HBM (u / a at aoff, mini_pos at roff).  k_regs turns them into regions, selects
+// primaries and secondaries, estimates the divergence, computes MAPQ and writes the hit rows on the device (mm355_regs.h, a lane per read);
+// only the rows and one count per read come back.  Reads the device does not decide -- those the RMQ stage left to the host, and those
+// mm355_regs.h defers (logf argument beyond the table, a strand_retained comparison on an unsure divergence) -- are packed alone and run
+// through mm355_glue_regions + mm355_glue_chain_finish on the host pool.  MM355_REGS_HOST=1 sends every read that way.
+#include <stdio.h>
+#include <string.h>
+#include <mutex>
+#include "mm355_pipeline.h"
+#include "mm355_rmq.h"
+#include "mm355_glue.h"
+#include "mm355_regs.h"
+
+#define REGS_LOGT_N (1 << 22)     // logf(1 .. 2^22 - 1): chain scores of reads up to a few Mb (a chain scores at most about its query span)
+
+struct RegsRead {                 // per read of the batch
+	int64_t hoff;                 // first scratch / row slot (exclusive scan of n_u over the reads the device takes)
+	int32_t qlen, rep_len, n_u, n_mini;
+	int32_t run, pad;             // run: 1 = the device takes the read
+};
+
+__global__ __launch_bounds__(64) void k_regs(int n_reads, const RegsRead *rr, const int64_t *aoff, const int64_t *roff, const uint64_t *u,
+                                             const mm128 *a, const uint64_t *mini_pos, const uint32_t *seq_len, Mm355RegsOpt o,
+                                             const float *logt, int32_t n_logt, Mm355Reg *sr, mm128 *sz, uint64_t *scov, int32_t *sw,
+                                             int32_t *stmp, uint32_t *smq, mm355_hit_t *hits, int32_t *cnt)
+{
+	const int r = blockIdx.x * 64 + threadIdx.x;
+	if (r >= n_reads) return;
+	const RegsRead q = rr[r];
+	if (!q.run) { cnt[r] = 0; return; }
+	const int64_t h = q.hoff;     // every write of the read stays in [h, h + n_u) of each scratch array and of hits
+	Mm355RegsScratch s;
+	s.r = sr + h; s.z = sz + h; s.cov = scov + h; s.w = sw + h; s.tmp = stmp + h;
+	const int64_t ao = aoff[r];
+	cnt[r] = mm355_regs_read(o, seq_len, q.qlen, q.rep_len, q.n_u, u + ao, a + ao, q.n_mini, mini_pos + roff[r], logt, n_logt, s, smq + h, hits + h);
+}
+
+// u[], chained anchors and mini_pos[] of the listed reads into three dense arrays (k_pack_chains for a subset)
+__global__ __launch_bounds__(256) void k_pack_sel(int n_sel, const int32_t *sel, const int64_t *aoff, const int64_t *roff, const int32_t *n_u,
+                                                  const int32_t *n_v, const int32_t *n_mini, const int64_t *uo, const int64_t *vo, const int64_t *mo,
+                                                  const uint64_t *u, const mm128 *a, const uint64_t *mini_pos, uint64_t *pu, mm128 *pa, uint64_t *pm)
+{
+	const int j = blockIdx.x;
+	if (j >= n_sel) return;
+	const int r = sel[j];
+	const int64_t ao = aoff[r], ro = roff[r];
+	for (int i = threadIdx.x; i < n_u[r]; i += 256) pu[uo[j] + i] = u[ao + i];
+	for (int i = threadIdx.x; i < n_v[r]; i += 256) pa[vo[j] + i] = a[ao + i];
+	for (int i = threadIdx.x; i < n_mini[r]; i += 256) pm[mo[j] + i] = mini_pos[ro + i];
+}
+
+static const std::vector<float> &host_logt()
+{   // the host's logf of every table index, once per process (the values mm_set_mapq computes on the host)
+	static std::vector<float> t;
+	static std::once_flag once;
+	std::call_once(once, [] { t.resize(REGS_LOGT_N); t[0] = 0.0f; for (int32_t i = 1; i < REGS_LOGT_N; ++i) t[i] = logf((float)i); });
+	return t;
+}
+
+static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+int mm355_map_chain_only(mm355_ctx *c, const mm355_mapopt_t *mo, const std::vector<int32_t> &qlen, mm355_hits_t **out)
+{
+	*out = 0;
+	const mm355_index *mi = c->mi;
+	HostBatch &hb = c->hb;
+	const int64_t n_reads = hb.n_reads;
+	const bool rmq_chain = (mo->flag & MMF_RMQ) != 0;
+	const bool all_host = [] { const char *e = getenv("MM355_REGS_HOST"); return e && atoi(e) != 0; }();   // (read per call: the tests switch it)
+	// test hook: only the first n entries of the logf table count, so that reads with larger chain scores take the defer path
+	const int32_t n_logt = [] { const char *e = getenv("MM355_REGS_LOGT_N"); const long v = e? atol(e) : 0; return v > 1 && v < REGS_LOGT_N? (int32_t)v : (int32_t)REGS_LOGT_N; }();
+	// which reads the device takes, and their row slots
+	if (c->h_regs_in.ensure((size_t)(n_reads + 1) * sizeof(RegsRead))) return MM355_ENOMEM;
+	RegsRead *rr = (RegsRead*)c->h_regs_in.p;
+	int64_t tot = 0, n_run = 0;
+	for (int64_t i = 0; i < n_reads; ++i) {
+		RegsRead &q = rr[i];
+		memset(&q, 0, sizeof(q));
+		const int rst = hb.rmq_state.empty()? MM355_RMQ_HOST_ALL : (int)hb.rmq_state[i];
+		q.qlen = qlen[i]; q.rep_len = hb.rep_len[i]; q.n_u = hb.n_u[i]; q.n_mini = hb.n_mini[i];
+		q.run = !all_host && q.qlen > 0 && (rst == MM355_RMQ_KEEP || rst == MM355_RMQ_DONE);
+		q.hoff = tot;
+		if (q.run) { tot += q.n_u; ++n_run; }
+	}
+	const size_t nt = (size_t)(tot > 0? tot : 1);
+	const size_t o_z = al256(nt * sizeof(Mm355Reg)), o_cov = o_z + al256(nt * 16), o_w = o_cov + al256(nt * 8), o_tmp = o_w + al256(nt * 4),
+	             o_mq = o_tmp + al256(nt * 4), o_hit = o_mq + al256(nt * 4), o_cnt = o_hit + al256(nt * sizeof(mm355_hit_t)),
+	             scr_b = o_cnt + al256((size_t)(n_reads + 1) * 4);
+	const size_t out_b = al256(nt * sizeof(mm355_hit_t)) + (size_t)(n_reads + 1) * 4;
+	if (c->regs_scr.ensure(scr_b) || c->regs_in.ensure((size_t)(n_reads + 1) * sizeof(RegsRead)) || c->h_regs_out.ensure(out_b)) return MM355_ENOMEM;
+	char *scr = c->regs_scr.as<char>();
+	mm355_hit_t *h_rows = (mm355_hit_t*)c->h_regs_out.p;
+	int32_t *h_cnt = (int32_t*)((char*)c->h_regs_out.p + al256(nt * sizeof(mm355_hit_t)));
+	if (n_run > 0) {
+		if (!c->logt_ok) {
+			const std::vector<float> &t = host_logt();
+			if (c->logt.ensure(t.size() * 4, 1 << 30)) return MM355_ENOMEM;
+			HIPCHK(hipMemcpy(c->logt.p, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+			c->logt_ok = true;
+		}
+		Mm355RegsOpt o;
+		memset(&o, 0, sizeof(o));
+		o.flag = mo->flag; o.mask_level = mo->mask_level; o.pri_ratio = mo->pri_ratio; o.mask_len = mo->mask_len; o.best_n = mo->best_n;
+		o.min_diff = mi->k * 2; o.min_strand_sc = (int)(mo->max_gap * 0.8); o.min_chain_score = mo->min_chain_score; o.seed = mo->seed;
+		HIPCHK(hipMemcpyAsync(c->regs_in.p, rr, (size_t)n_reads * sizeof(RegsRead), hipMemcpyHostToDevice, c->st));
+		mm355_kt(c, KT_REGS, 0, c->st);
+		hipLaunchKernelGGL(k_regs, dim3((unsigned)((n_reads + 63) / 64)), dim3(64), 0, c->st, (int)n_reads, c->regs_in.as<RegsRead>(),
+		                   c->aoff.as<int64_t>(), c->roff.as<int64_t>(), c->u.as<uint64_t>(), c->a.as<mm128>(), c->mini_pos.as<uint64_t>(),
+		                   c->dix.seq_len, o, c->logt.as<float>(), n_logt, (Mm355Reg*)scr, (mm128*)(scr + o_z), (uint64_t*)(scr + o_cov),
+		                   (int32_t*)(scr + o_w), (int32_t*)(scr + o_tmp), (uint32_t*)(scr + o_mq), (mm355_hit_t*)(scr + o_hit), (int32_t*)(scr + o_cnt));
+		mm355_kt(c, KT_REGS, 1, c->st);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipMemcpyAsync(h_cnt, scr + o_cnt, (size_t)n_reads * 4, hipMemcpyDeviceToHost, c->st));
+		if (tot > 0) HIPCHK(hipMemcpyAsync(h_rows, scr + o_hit, (size_t)tot * sizeof(mm355_hit_t), hipMemcpyDeviceToHost, c->st));
+		HIPCHK(mm355_wait_stream(c->st));
+	}
+	// the host path: reads the device did not take or deferred
+	std::vector<int32_t> sel;
+	for (int64_t i = 0; i < n_reads; ++i) if (qlen[i] > 0 && (!rr[i].run || h_cnt[i] < 0)) sel.push_back((int32_t)i);
+	const int64_t n_sel = (int64_t)sel.size();
+	std::vector<std::vector<mm355_hit_t>> hh((size_t)n_sel);
+	if (n_sel > 0) {
+		std::vector<int64_t> offs((size_t)(n_sel + 1) * 3);
+		int64_t *uo = offs.data(), *vo = uo + n_sel + 1, *mo_ = vo + n_sel + 1;
+		int64_t tu = 0, tv = 0, tm = 0;
+		for (int64_t j = 0; j < n_sel; ++j) { const int r = sel[j]; uo[j] = tu; vo[j] = tv; mo_[j] = tm; tu += hb.n_u[r]; tv += hb.n_v[r]; tm += hb.n_mini[r]; }
+		uo[n_sel] = tu; vo[n_sel] = tv; mo_[n_sel] = tm;
+		if (c->h_pu.ensure((size_t)(tu + 1) * 8) || c->h_pm.ensure((size_t)(tm + 1) * 8) || c->h_pa.ensure((size_t)(tv + 1) * 16)) return MM355_ENOMEM;
+		uint64_t *pu = (uint64_t*)c->h_pu.p, *pm = (uint64_t*)c->h_pm.p; mm128 *pa = (mm128*)c->h_pa.p;
+		const size_t b_sel = al256((size_t)n_sel * 4), b_off = al256(offs.size() * 8);
+		const size_t b_u = al256((size_t)tu * 8), b_a = al256((size_t)tv * 16), b_m = al256((size_t)tm * 8);
+		if (c->regs_sel.ensure(b_sel + b_off + b_u + b_a + b_m + 256) || c->h_regs_sel.ensure(b_sel + b_off)) return MM355_ENOMEM;
+		char *d = c->regs_sel.as<char>(), *hs = (char*)c->h_regs_sel.p;
+		memcpy(hs, sel.data(), (size_t)n_sel * 4);
+		memcpy(hs + b_sel, offs.data(), offs.size() * 8);
+		HIPCHK(hipMemcpyAsync(d, hs, b_sel + offs.size() * 8, hipMemcpyHostToDevice, c->st));
+		const int64_t *d_off = (const int64_t*)(d + b_sel);
+		uint64_t *d_pu = (uint64_t*)(d + b_sel + b_off); mm128 *d_pa = (mm128*)(d + b_sel + b_off + b_u); uint64_t *d_pm = (uint64_t*)(d + b_sel + b_off + b_u + b_a);
+		mm355_kt(c, KT_PACK, 0, c->st);
+		hipLaunchKernelGGL(k_pack_sel, dim3((unsigned)n_sel), dim3(256), 0, c->st, (int)n_sel, (const int32_t*)d, c->aoff.as<int64_t>(), c->roff.as<int64_t>(),
+		                   c->n_u.as<int32_t>(), c->n_v.as<int32_t>(), c->n_mini.as<int32_t>(), d_off, d_off + n_sel + 1, d_off + 2 * (n_sel + 1),
+		                   c->u.as<uint64_t>(), c->a.as<mm128>(), c->mini_pos.as<uint64_t>(), d_pu, d_pa, d_pm);
+		mm355_kt(c, KT_PACK, 1, c->st);
+		HIPCHK(hipGetLastError());
+		if (tu) HIPCHK(hipMemcpyAsync(pu, d_pu, (size_t)tu * 8, hipMemcpyDeviceToHost, c->st));
+		if (tv) HIPCHK(hipMemcpyAsync(pa, d_pa, (size_t)tv * 16, hipMemcpyDeviceToHost, c->st));
+		if (tm) HIPCHK(hipMemcpyAsync(pm, d_pm, (size_t)tm * 8, hipMemcpyDeviceToHost, c->st));
+		HIPCHK(mm355_wait_stream(c->st));
+		auto one = [&](int64_t j) {
+			const int r = sel[j];
+			ReadState rs;
+			rs.qlen = qlen[r]; rs.rep_len = hb.rep_len[r];
+			rs.u.assign(pu + uo[j], pu + uo[j + 1]);
+			rs.a.assign(pa + vo[j], pa + vo[j + 1]);
+			rs.mini_pos.assign(pm + mo_[j], pm + mo_[j + 1]);
+			int rst = hb.rmq_state.empty()? MM355_RMQ_HOST_ALL : (int)hb.rmq_state[r];
+			if (rst == MM355_RMQ_HOST_ALL) { if (rmq_chain) mm355_glue_chain_rmq(mi, mo, rs); rst = -1; }   // every mg_lchain_rmq call of this read on the host
+			mm355_glue_regions(mi, mo, rs, rst);
+			mm355_glue_chain_finish(mi, mo, rs, hh[j]);
+		};
+		if (mm355_parallel_hook) mm355_parallel_hook(n_sel, one);
+		else for (int64_t j = 0; j < n_sel; ++j) one(j);
+	}
+	// the batch result, in read order
+	mm355_hits_t *H = (mm355_hits_t*)calloc(1, sizeof(mm355_hits_t));
+	if (H == 0) return MM355_ENOMEM;
+	H->n_reads = n_reads;
+	H->hit_off = (int64_t*)malloc((n_reads + 1) * 8);
+	H->status = (int32_t*)malloc((n_reads > 0? n_reads : 1) * 4);
+	int64_t nh = 0, n_dev = 0;
+	for (int64_t i = 0, j = 0; i < n_reads; ++i) {
+		H->hit_off[i] = nh; H->status[i] = hb.status[i];
+		if (j < n_sel && sel[j] == i) nh += (int64_t)hh[j++].size();
+		else if (rr[i].run) { nh += h_cnt[i]; ++n_dev; }
+	}
+	H->hit_off[n_reads] = nh; H->n_hits = nh; H->n_cigar = 0; H->n_str = 0;
+	H->hits = (mm355_hit_t*)malloc((nh > 0? nh : 1) * sizeof(mm355_hit_t));
+	H->cigar = (uint32_t*)malloc(4);
+	H->str = (char*)malloc(1);
+	if (!H->hit_off || !H->status || !H->hits || !H->cigar || !H->str) { mm355_free_hits(H); return MM355_ENOMEM; }
+	for (int64_t i = 0, j = 0; i < n_reads; ++i) {
+		mm355_hit_t *dst = H->hits + H->hit_off[i];
+		if (j < n_sel && sel[j] == i) { if (!hh[j].empty()) memcpy(dst, hh[j].data(), hh[j].size() * sizeof(mm355_hit_t)); ++j; }
+		else if (rr[i].run && h_cnt[i] > 0) memcpy(dst, h_rows + rr[i].hoff, (size_t)h_cnt[i] * sizeof(mm355_hit_t));
+	}
+	c->stats.n_regs_dev = n_dev; c->stats.n_regs_host = n_sel;
+	*out = H;
+	return 0;
+}

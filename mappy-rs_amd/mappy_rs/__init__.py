@@ -49,11 +49,12 @@ _HIT_DTYPE = np.dtype([(k, np.dtype(t)) for k, t in _ffi.Hit._fields_], align=Tr
 
 
 class _HitBatch:
-    """what the Mapping records of one mm355_hits_t share: the packed CIGAR words, the string arena, the contig names"""
-    __slots__ = ("cig", "sbuf", "names")
+    """what the Mapping records of one mm355_hits_t share: the packed CIGAR words, the string arena, the contig names, and whether the batch
+    was mapped without CIGARs (chain-only: no extension, records come from the chains)"""
+    __slots__ = ("cig", "sbuf", "names", "chain_only")
 
-    def __init__(self, cig, sbuf, names):
-        self.cig, self.sbuf, self.names = cig, sbuf, names
+    def __init__(self, cig, sbuf, names, chain_only=False):
+        self.cig, self.sbuf, self.names, self.chain_only = cig, sbuf, names, chain_only
 
 
 class Mapping:
@@ -76,7 +77,7 @@ class Mapping:
         self._r = None
         self._cig = list(cigar)
         self._own = (query_start, query_end, strand, target_name, target_len, target_start, target_end, match_len, block_len, mapq,
-                     bool(is_primary), NM, MD, cs)
+                     bool(is_primary), NM, MD, cs, False)
 
     @classmethod
     def _view(cls, batch, row):
@@ -104,11 +105,12 @@ class Mapping:
         """make the record independent of its sub-batch: copy its fields, CIGAR and cs / MD out of the shared arenas and drop the reference"""
         if self._own is None:
             r, b = self._r, self._b
-            w = b.cig[r[_CO]:r[_CO] + r[_NC]]
+            w = b.cig[r[_CO]:r[_CO] + r[_NC]] if r[_NC] > 0 else b.cig[:0]
             self._cig = list(zip((w >> 4).tolist(), (w & 0xf).tolist()))
             md = b.sbuf[r[_MDO]:r[_MDO] + r[_MDL]].decode() if r[_MDL] >= 0 else None
             cs = b.sbuf[r[_CSO]:r[_CSO] + r[_CSL]].decode() if r[_CSL] >= 0 else None
-            self._own = (r[_QS], r[_QE], r[_ST], b.names[r[_RID]], r[_TL], r[_TS], r[_TE], r[_ML], r[_BL], r[_MQ], bool(r[_PR]), r[_NM], md, cs)
+            self._own = (r[_QS], r[_QE], r[_ST], b.names[r[_RID]], r[_TL], r[_TS], r[_TE], r[_ML], r[_BL], r[_MQ], bool(r[_PR]), r[_NM], md, cs,
+                         b.chain_only)
             self._b = self._r = None
         return self
 
@@ -150,11 +152,12 @@ class Mapping:
             out.append("%d%s" % (n, _CIGAR_OPS[op]))
         return "".join(out)
 
-    def __str__(self):  # PAF-like, lib.rs:159-180
+    def __str__(self):  # PAF-like, lib.rs:159-180; a chain-only record has no cg:Z: field (minimap2 prints none without -c)
         tp = "tp:A:P" if self.is_primary else "tp:A:S"
-        return "\t".join(str(x) for x in (self.query_start, self.query_end, "+" if self.strand > 0 else "-",
-                                          self.target_name, self.target_len, self.target_start, self.target_end,
-                                          self.match_len, self.block_len, self.mapq, tp, "cg:Z:" + self.cigar_str))
+        chain_only = self._b.chain_only if self._own is None else self._own[14]
+        cols = (self.query_start, self.query_end, "+" if self.strand > 0 else "-", self.target_name, self.target_len, self.target_start,
+                self.target_end, self.match_len, self.block_len, self.mapq, tp)
+        return "\t".join(str(x) for x in (cols if chain_only else cols + ("cg:Z:" + self.cigar_str,)))
 
     def __repr__(self):
         return "Mapping(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in Mapping.FIELDS)
@@ -165,9 +168,10 @@ class Mapping:
     __hash__ = None
 
 
-def _batch_to_mappings(hp, n_reads, names):
+def _batch_to_mappings(hp, n_reads, names, chain_only=False):
     """all hits of one mm355_hits_t -> list (per read) of list[Mapping] or RuntimeError.  One bulk copy per array (hit rows, CIGAR words,
-    string arena); every Mapping is a view of its row (fields, cs / MD strings and the CIGAR list are produced on access)."""
+    string arena); every Mapping is a view of its row (fields, cs / MD strings and the CIGAR list are produced on access).  chain_only: the batch
+    was mapped without MM_F_CIGAR (no CIGAR words; the records print no cg:Z: field)."""
     h = hp.contents
     nh = int(h.n_hits)
     off = np.ctypeslib.as_array(h.hit_off, shape=(n_reads + 1,)).tolist()
@@ -176,9 +180,11 @@ def _batch_to_mappings(hp, n_reads, names):
     if nh:
         assert _HIT_DTYPE.itemsize == C.sizeof(_ffi.Hit)
         rows = np.frombuffer(C.string_at(h.hits, nh * C.sizeof(_ffi.Hit)), dtype=_HIT_DTYPE).tolist()
-        cig = np.ctypeslib.as_array(h.cigar, shape=(max(int(h.n_cigar), 1),)).copy()
+        # a chain-only batch has hits but no CIGAR words: the arena may be NULL or empty
+        n_cig = int(h.n_cigar)
+        cig = np.ctypeslib.as_array(h.cigar, shape=(n_cig,)).copy() if n_cig > 0 and h.cigar else np.zeros(0, np.uint32)
         sbuf = C.string_at(h.str, int(h.n_str)) if h.n_str else b""
-        B = _HitBatch(cig, sbuf, names)
+        B = _HitBatch(cig, sbuf, names, chain_only)
         view = Mapping._view
         ms = [view(B, r) for r in rows]
         out = [ms[off[i]:off[i + 1]] for i in range(n_reads)]
@@ -335,7 +341,7 @@ class Aligner:
 
     def __init__(self, fn_idx_in=None, preset=None, k=None, w=None, min_cnt=None, min_chain_score=None,
                  min_dp_score=None, bw=None, best_n=None, n_threads=3, fn_idx_out=None, max_frag_len=None,
-                 extra_flags=None, seq=None, scoring=None, device=0, devices=None):
+                 extra_flags=None, seq=None, scoring=None, device=0, devices=None, *, cigar=True):
         L = _ffi.lib()
         self._L = L
         self._idx = C.c_void_p()
@@ -358,7 +364,8 @@ class Aligner:
             if rc == _ffi.MM355_EUNSUP:
                 raise NotImplementedError("preset %r is not implemented by the MI355X mapping path (long-read presets only: map-ont, "
                                           "map-hifi, map-pb, asm5/asm10/asm20, ava-ont, ava-pb)" % (preset,))
-        mo.flag |= 4                       # MM_F_CIGAR, lib.rs:339
+        if cigar:
+            mo.flag |= 4                   # MM_F_CIGAR, lib.rs:339; cigar=False: chain-only mapping (minimap2 without -c), no extension
         io.batch_size |= 0x7fffffffffffffff  # lib.rs:340
         if k is not None: io.k = k
         if w is not None: io.w = w
@@ -459,7 +466,7 @@ class Aligner:
         if rc != 0:
             raise RuntimeError(L.mm355_strerror(rc).decode())
         try:
-            return _batch_to_mappings(hp, len(seqs), self._names())
+            return _batch_to_mappings(hp, len(seqs), self._names(), chain_only=not self._mo.flag & 4)
         finally:
             L.mm355_free_hits(hp)
 
@@ -493,6 +500,8 @@ class Aligner:
         if not isinstance(seq, str):
             raise TypeError("argument 'seq': 'bytes' object cannot be converted to 'PyString'" if isinstance(seq, bytes)
                             else "argument 'seq' must be str")
+        if (cs or MD) and not self._mo.flag & 4:
+            raise ValueError("cs / MD need base-level alignment: this Aligner was created with cigar=False")
         flags = (_ffi.OUT_CS if cs else 0) | (_ffi.OUT_MD if MD else 0)
         r = self._map_many([seq], flags)[0]
         if isinstance(r, Exception):
@@ -541,6 +550,7 @@ class Aligner:
         workers = st.threads
         self._names()                       # fill the name cache before the workers read it
         map_many, acquire, release = self._map_many, self._ctx_acquire, self._ctx_release
+        out_flags = _ffi.OUT_CS if self._mo.flag & 4 else 0        # chain-only: no cs string to produce
 
         # (the closures below capture `st`, never the iterator handed to the caller)
         def worker(slot):
@@ -556,7 +566,7 @@ class Aligner:
                         reads, items = work.popleft()
                         state["pending"] -= len(reads)
                         cv.notify_all()                                   # the producer may be waiting for room (back-off)
-                    maps = map_many(reads, _ffi.OUT_CS, ctx[1])           # cs=true, MD=false: lib.rs:589-590
+                    maps = map_many(reads, out_flags, ctx[1])             # cs=true, MD=false: lib.rs:589-590
                     st.t_sub_done.append(time.perf_counter())
                     # a worker error on one read => no result for that id (lib.rs:621-623)
                     out = [(m, it) for m, it in zip(maps, items) if not isinstance(m, Exception)]

@@ -1,0 +1,123 @@
+"""Chain-only mapping (no MM_F_CIGAR) against the CIGAR path on the same resident sub-batches: Mbases/s of mm355_map_resident, ms per
+sub-batch, reads whose region logic ran on the device / on the host, the region kernel's time (mm355_stats_t::ms_kernel[23]) next to the
+other kernels of the chain-only call (ms_kernel, the rest), and a sample of reads checked against the oracle (flag &= ~4).  One context,
+sub-batches of SUB reads, timed after a warm-up; the index is built on the device (as bench.py does).
+
+    python tools/chainonly_bench.py --workload ecoli [--preset map-ont] [--reads 18432] [--sub 9216] [--n50 N --lo L --hi H] [--out F]
+
+ecoli: bench.py's configs[1] genome and read model; human: its configs[2] genome (make_human_like, seed 3, --scale 1) and read model.
+--n50 / --lo / --hi override the read lengths (e.g. 150 kb - 1 Mb reads)."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "mappy-rs_amd"))
+
+import numpy as np  # noqa: E402
+
+import synthdata as S  # noqa: E402
+
+READS = {"ecoli": (2, dict(n50=8000, sigma=0.75, lo=500, hi=100000)), "human": (4, dict(n50=10000, sigma=0.75, lo=500, hi=100000))}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", default="ecoli", choices=sorted(READS))
+    ap.add_argument("--preset", default="map-ont")
+    ap.add_argument("--scale", type=float, default=1.0)
+    ap.add_argument("--reads", type=int, default=18432)
+    ap.add_argument("--sub", type=int, default=9216)
+    ap.add_argument("--n50", type=int, default=None)
+    ap.add_argument("--lo", type=int, default=None)
+    ap.add_argument("--hi", type=int, default=None)
+    ap.add_argument("--check", type=int, default=200)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import mappy_rs
+    from mappy_rs import _ffi
+    from oracle import oracle as O
+    L = _ffi.lib()
+    t0 = time.time()
+    if args.workload == "ecoli":
+        g, names = S.make_genome(1, [4641652], gc=0.508, repeats=((5000, 7, 0.01), (1300, 20, 0.01))), ["chrE"]
+    else:
+        g, names = S.make_human_like(3, args.scale)
+    seed, kw = READS[args.workload]
+    kw = dict(kw)
+    for k in ("n50", "lo", "hi"):
+        if getattr(args, k) is not None:
+            kw[k] = getattr(args, k)
+    reads, _ = S.make_reads(seed, g, args.reads, **kw)
+    print("[chainonly] genome + %d reads in %.1fs" % (len(reads), time.time() - t0), flush=True)
+    io, mo0 = _ffi.IdxOpt(), _ffi.MapOpt()
+    L.mm355_set_opt(None, C.byref(io), C.byref(mo0))
+    _ffi.check(L.mm355_set_opt(args.preset.encode(), C.byref(io), C.byref(mo0)))
+    ptrs = (C.c_char_p * len(g))(*[C.cast(c.ctypes.data, C.c_char_p) for c in g])
+    lens = (C.c_int64 * len(g))(*[len(c) for c in g]); nm = (C.c_char_p * len(g))(*[n.encode() for n in names])
+    idx = C.c_void_p()
+    _ffi.check(L.mm355_index_build_device(C.byref(io), len(g), ptrs, lens, nm, 0, C.byref(idx)))
+    L.mm355_mapopt_update(C.byref(mo0), idx)
+    ctx = C.c_void_p()
+    _ffi.check(L.mm355_ctx_create(idx, 0, C.byref(ctx)))
+    res = {"workload": args.workload, "preset": args.preset, "scale": args.scale, "read_model": kw, "n_reads": len(reads),
+           "sub_batch": args.sub, "bases": int(sum(map(len, reads)))}
+    subs = [reads[i:i + args.sub] for i in range(0, len(reads), args.sub)]
+    keep = []
+    for j, sb in enumerate(subs):
+        arr, rl, k = _ffi.pack_reads(sb)
+        keep.append(k)
+        _ffi.check(L.mm355_batch_select(ctx, j)); _ffi.check(L.mm355_batch_upload(ctx, len(sb), arr, rl))
+    names_l = list(names)
+    for mode in ("cigar", "chain_only"):
+        mo = _ffi.MapOpt.from_buffer_copy(mo0)
+        if mode == "cigar":
+            mo.flag |= 4
+        flags = _ffi.OUT_CS if mode == "cigar" else 0
+        hp = C.POINTER(_ffi.Hits)()
+        _ffi.check(L.mm355_batch_select(ctx, 0)); _ffi.check(L.mm355_map_resident(ctx, C.byref(mo), flags, C.byref(hp)))   # warm-up
+        L.mm355_free_hits(hp)
+        ms, n_dev, n_host, k_regs, k_other, n_hits = [], 0, 0, 0.0, 0.0, 0
+        st = _ffi.Stats()
+        for j, sb in enumerate(subs):
+            _ffi.check(L.mm355_batch_select(ctx, j))
+            t = time.perf_counter()
+            _ffi.check(L.mm355_map_resident(ctx, C.byref(mo), flags, C.byref(hp)))
+            ms.append((time.perf_counter() - t) * 1e3)
+            n_hits += int(hp.contents.n_hits)
+            if mode == "chain_only" and j == 0 and args.check:
+                first = mappy_rs._batch_to_mappings(hp, len(sb), names_l, chain_only=True)
+            L.mm355_free_hits(hp)
+            L.mm355_get_stats(ctx, C.byref(st))
+            n_dev += st.n_regs_dev; n_host += st.n_regs_host; k_regs += st.ms_kernel[23]; k_other += sum(st.ms_kernel[:23])
+        tot_s = sum(ms) / 1e3
+        res[mode] = {"mbases_per_s": round(res["bases"] / tot_s / 1e6, 1), "ms_per_sub_batch": [round(x, 1) for x in ms], "n_hits": n_hits}
+        if mode == "chain_only":
+            res[mode].update(n_regs_dev=n_dev, n_regs_host=n_host, ms_k_regs_per_sub_batch=round(k_regs / len(subs), 3),
+                             ms_other_kernels_per_sub_batch=round(k_other / len(subs), 3))
+            if args.check:
+                orc = O.OracleAligner(preset=args.preset, codes=g, names=names, n_threads=16)
+                orc.mo.flag &= ~4
+                bad = 0
+                for rd, gm in zip(subs[0][:args.check], first):
+                    exp = orc.map(rd)
+                    if [(m.ctg, m.r_st, m.r_en, m.q_st, m.q_en, m.strand, m.mlen, m.blen, m.mapq, m.is_primary) for m in gm] != \
+                            [(e["target_name"], e["target_start"], e["target_end"], e["query_start"], e["query_end"], e["strand"],
+                              e["match_len"], e["block_len"], e["mapq"], e["is_primary"]) for e in exp]:
+                        bad += 1
+                res[mode].update(checked=min(args.check, len(subs[0])), mismatching=bad)
+        print("[chainonly] %s: %s" % (mode, json.dumps(res[mode])), flush=True)
+    res["ratio_chain_only_to_cigar"] = round(res["chain_only"]["mbases_per_s"] / res["cigar"]["mbases_per_s"], 2)
+    L.mm355_ctx_destroy(ctx); L.mm355_index_free(idx)
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
