@@ -8,6 +8,7 @@ struct DpConst {            // scoring constants after ksw_extd2_sse's (q,e)/(q2
 	int32_t q, e, q2, e2, qe_preswap;
 	int8_t sc_mch, sc_mis, sc_N;
 	int32_t long_thres, long_diff, valid;
+	int32_t int8_ok;         // no int8 lane of ksw_extd2_sse wraps on a cell of the matrix (mm355_dpdomain.h): the row / band kernels' premise
 };
 
 struct DpJobDev {

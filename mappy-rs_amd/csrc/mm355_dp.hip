@@ -21,6 +21,7 @@
 #include <algorithm>
 #include "mm355_pipeline.h"
 #include "mm355_dp.h"
+#include "mm355_dpdomain.h"
 
 #define WAVE 64
 #define KSW_NEG_INF (-0x40000000)
@@ -444,6 +445,7 @@ DpConst mm355_dp_const(const mm355_mapopt_t *mo)
 	c.long_diff = c.long_thres * (e - e2) - (q2 - q) - e2;
 	int min_sc = b < amb? b : amb;
 	c.valid = !(-min_sc > 2 * (q + e));
+	c.int8_ok = mm355_dp_int8_domain(mo->a, mo->b, mo->sc_ambi, mo->q, mo->e, mo->q2, mo->e2);
 	return c;
 }
 
@@ -506,7 +508,9 @@ static int row_class(const DpConst &dc, int qlen, int tlen, int w_in, int flag)
 	// them, the kernel's clamp `z = min(z, sc_mch)` becomes active and the result is no longer the plain recurrence the row sweep
 	// computes (found by the option fuzzer: scoring=(4,10,3,3,12,3)); those options keep the literal anti-diagonal kernels.
 	const bool regular = dc.e > dc.e2 || (dc.e == dc.e2 && dc.q == dc.q2);
-	const bool row_kind = dc.valid && use_row && regular && (flag & EZ_APPROX_MAX) && !(flag & (EZ_APPROX_DROP | EZ_EXTZ_ONLY | EZ_SCORE_ONLY)) && w >= qlen + tlen;
+	// ... and only inside the int8 domain of the SSE kernel (mm355_dpdomain.h): beyond it, e.g. a gap sum (q + e) + (q2 + e2) above 128
+	// or a + q + 2e above 128, its lanes wrap on true cells and its result is no longer the plain recurrence either
+	const bool row_kind = dc.valid && dc.int8_ok && use_row && regular &&(flag & EZ_APPROX_MAX) && !(flag & (EZ_APPROX_DROP | EZ_EXTZ_ONLY | EZ_SCORE_ONLY)) && w >= qlen + tlen;
 	if (!row_kind) return 0;
 	// (the int16 value range is checked per problem: a user scoring such as e2 >= 7 or a large match score would wrap the packed halves)
 	if (tlen <= ROW_MAX_T) return qlen + tlen <= ROW_MAX_QT && rowl_range_ok(dc, qlen, tlen <= 256? 256 : tlen <= 512? 512 : 1024)? 1 : 0;

@@ -1,7 +1,8 @@
 // mm355_dpband.h -- the row sweep of mm355_dprow.h on a DIAGONAL BAND of the matrix, with a proof per problem that the band is enough.
 // Included by mm355_dp.hip.  Same problems as k_ksw_row / k_ksw_rowl: full-band approximate gap fills (KSW_EZ_APPROX_MAX without
-// KSW_EZ_APPROX_DROP, w >= qlen + tlen, regular two-piece cost) -- whose results are the score H(tlen - 1, qlen - 1) and the CIGAR of the
-// backtrack from that cell (U:ksw2_extd2_sse.c, reached from /root/reference/src/lib.rs:587 through mm_align1's gap fills).
+// KSW_EZ_APPROX_DROP, w >= qlen + tlen, regular two-piece cost inside the int8 domain of mm355_dpdomain.h, where the SSE kernel's lanes
+// never wrap and it computes the plain recurrence) -- whose results are the score H(tlen - 1, qlen - 1) and the CIGAR of the
+// backtrack from that cell (U:ksw2_extd2_sse.c, reached from R:src/lib.rs:587 through mm_align1's gap fills).
 //
 // Why a band gives the SAME result.  The reference fills the whole qlen x tlen matrix; a gap fill between two chained anchors is a pair of
 // nearly equal sequences, and its optimal path stays within a few dozen cells of the straight line from (0, 0) to the end cell.  Take the

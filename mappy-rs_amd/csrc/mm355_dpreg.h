@@ -471,7 +471,9 @@ __device__ __forceinline__ void dp_reg_body(const DpConst &dc, const DpJobDev *j
 	R.n_col = n_col_ * 16;
 	R.p = pbase + jb.p_off;
 	R.r_total = qlen + tlen - 1;
-	R.full = !EXACT && !(R.flag & EZ_APPROX_DROP) && R.w >= qlen + tlen;
+	// (the shortcut of the approximate score below sums exact cells: only inside the int8 domain, mm355_dpdomain.h -- beyond it, e.g. a
+	// match score of 121 with q = 4, e = 2, the u / v lanes wrap and the reference's v-or-u walk is what defines ez.score)
+	R.full = !EXACT && !(R.flag & EZ_APPROX_DROP) && R.w >= qlen + tlen && dc.int8_ok;
 	R.r = 0; R.last_st = R.last_en = -1; R.H0 = 0; R.last_H0_t = 0; R.cells = 0; R.qv = 0;
 	DpK K;
 	K.nqe = pk8(-R.q - R.e); K.nq2e2 = pk8(-R.q2 - R.e2); K.q = pk8(R.q); K.q2 = pk8(R.q2); K.qe = pk8(R.q + R.e); K.q2e2 = pk8(R.q2 + R.e2);

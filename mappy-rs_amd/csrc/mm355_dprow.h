@@ -10,7 +10,8 @@
 // is a function of those values alone --
 //     d & 7  = position of the first (KSW_EZ_RIGHT: last) maximum among (H(t-1,q-1) + s, E, F, E2, F2),
 //     0x08   = E  - H + q  > 0 (RIGHT: >= 0),   0x10 = F  - H + q  > 0,   0x20 = E2 - H + q2 > 0,   0x40 = F2 - H + q2 > 0
-// (the difference recurrences of the SSE kernel are these comparisons shifted by H(t-1,q-1); int8 never wraps on true cells).
+// (the difference recurrences of the SSE kernel are these comparisons shifted by H(t-1,q-1); its int8 lanes never wrap on true cells
+// INSIDE the domain of mm355_dpdomain.h -- (q + e) + (q2 + e2) <= 128, a + q + 2e <= 128, ... -- and row_class routes nothing else here).
 // So the matrix can be filled in any order.  Here: one wave per alignment, lane l of register set k owns target cells 128 k + 2 l, + 1
 // (two int16 halves per VGPR), and the sweep goes ROW by row of the query -- every lane of the target is useful on every step:
 //     F, F2 (gaps that consume query)  come from the row above in the same lane;

@@ -1,6 +1,8 @@
 """The claim k_ksw_row (mappy-rs_amd/csrc/mm355_dprow.h) rests on, checked on the CPU against the oracle's literal restatement of
-U:ksw2_extd2_sse.c: for a gap fill whose band never binds (KSW_EZ_APPROX_MAX, w >= qlen + tlen) and a regular two-piece cost (after
-ksw2's ordering e > e2, or two identical pieces) the SSE kernel's score and CIGAR are those of the plain two-piece affine recurrence
+U:ksw2_extd2_sse.c: for a gap fill whose band never binds (KSW_EZ_APPROX_MAX, w >= qlen + tlen), a regular two-piece cost (after
+ksw2's ordering e > e2, or two identical pieces) and a scoring inside the int8 domain of mappy-rs_amd/csrc/mm355_dpdomain.h (where none
+of the SSE kernel's int8 lanes wraps: (q + e) + (q2 + e2) <= 128, a + q + 2e <= 128, ...; tests/test_ksw_domain_model.py sweeps its
+edges) the SSE kernel's score and CIGAR are those of the plain two-piece affine recurrence
 evaluated in ANY order, with the direction byte of a cell a function of the true H / E / F / E2 / F2 --
     d & 7 = first (KSW_EZ_RIGHT: last) maximum among (H(t-1,q-1)+s, E, F, E2, F2);  0x08: E - H + q > 0 (RIGHT >= 0); 0x10: F; 0x20/0x40: E2, F2 with q2
 and E along a row an exclusive prefix maximum, E(t) = max_{k<t}(G(k) + k e) - q - t e with G = max(M, F, F2).

@@ -1,5 +1,5 @@
 """option fuzzing of the whole path against the oracle: random presets / k / w / chaining and DP thresholds / scoring tuples / extra_flags,
-24 reads per configuration (ordinary + chimeric).  python tools/optfuzz.py [seed=1] [n_configs=30] [noisy]   (needs the GPU)"""
+24 reads per configuration (ordinary + chimeric).  python tools/optfuzz.py [seed=1] [n_configs=30] [noisy | wide]   (needs the GPU)"""
 import os
 import sys
 
@@ -11,7 +11,23 @@ FIELDS = ("target_name", "target_start", "target_end", "query_start", "query_end
 FLAGS = (0x400, 0x800000, 0x10000000, 0x20000000, 0x4000000, 0x200000000, 0x100000, 0x200000)
 
 
-def random_config(rng):
+def wide_scoring(rng):
+    """a scoring tuple from the whole int8 range of ksw2 (every parameter 1..127, q + e <= 127, q2 + e2 <= 127, b and sc_ambi <= 2 (q + e)
+    after ksw2's ordering): half of them near the edges of the domain where its int8 lanes do not wrap (mm355_dpdomain.h), half anywhere"""
+    while True:
+        if rng.random() < 0.5:
+            e2 = int(rng.integers(1, 4)); e = int(rng.integers(e2, 12)); q = int(rng.integers(1, 60)); q2 = int(rng.integers(q, 124))
+            a = int(rng.integers(1, 128 - q - 2 * e + 4)) if rng.random() < 0.5 else int(rng.integers(1, 4))
+        else:
+            q, e, q2, e2, a = (int(v) for v in rng.integers(1, 128, 5))
+        if rng.random() < 0.2: q, e, q2, e2 = q2, e2, q, e            # pieces ksw2 swaps
+        if q + e > 127 or q2 + e2 > 127 or a > 127: continue
+        lim = 2 * min(q + e, q2 + e2)
+        b, amb = int(rng.integers(1, min(127, lim) + 1)), int(rng.integers(0, min(127, lim) + 1)) if rng.random() < 0.3 else 1
+        return (a, b, q, e, q2, e2, amb)
+
+
+def random_config(rng, wide=False):
     kw = dict(preset=str(rng.choice(["map-ont", "map-hifi", "asm20", "ava-ont"])))
     if rng.random() < 0.5: kw["k"] = int(rng.integers(11, 25))
     if rng.random() < 0.5: kw["w"] = int(rng.integers(3, 30))
@@ -21,7 +37,9 @@ def random_config(rng):
     if rng.random() < 0.5: kw["bw"] = int(rng.choice([50, 100, 250, 500, 1000, 3000]))
     if rng.random() < 0.4: kw["best_n"] = int(rng.integers(1, 12))
     if rng.random() < 0.3: kw["max_frag_len"] = int(rng.choice([800, 5000, 20000]))
-    if rng.random() < 0.6:
+    if wide:
+        kw["scoring"] = wide_scoring(rng)
+    elif rng.random() < 0.6:
         a, b, q, e = int(rng.integers(1, 6)), int(rng.integers(1, 12)), int(rng.integers(1, 14)), int(rng.integers(1, 5))
         sc = [a, b, q, e]
         if rng.random() < 0.7: sc += [int(rng.integers(q, 40)), int(rng.integers(1, e + 1))]
@@ -37,8 +55,8 @@ def random_config(rng):
     return kw
 
 
-def run(seed, n_configs, fa_path, verbose=False, noisy=False):
-    """returns (configurations run, hits compared, mismatching reads)"""
+def run(seed, n_configs, fa_path, verbose=False, noisy=False, wide=False):
+    """returns (configurations run, hits compared, mismatching reads); wide: scorings from the whole int8 range (wide_scoring)"""
     import mappy_rs
     import synthdata as S
     from oracle import oracle as O
@@ -48,7 +66,7 @@ def run(seed, n_configs, fa_path, verbose=False, noisy=False):
     comp = lambda c: np.where(c < 4, 3 - c, 4).astype(np.uint8)[::-1]
     tot_hits = tot_bad = 0
     for ci in range(n_configs):
-        kw = random_config(rng)
+        kw = random_config(rng, wide)
         if noisy: reads, _ = S.make_reads(int(rng.integers(1, 1 << 30)), g, 20, n50=9000, lo=300, sub=0.06, ins=0.04, dele=0.05)   # 15 % error
         else: reads, _ = S.make_reads(int(rng.integers(1, 1 << 30)), g, 20, n50=5000, lo=300)
         for _ in range(4):
@@ -83,4 +101,5 @@ if __name__ == "__main__":
     os.environ.setdefault("MM355_EXTRA_MIN_READS", "1")
     seed = int(sys.argv[1]) if len(sys.argv) > 1 else 1
     n = int(sys.argv[2]) if len(sys.argv) > 2 else 30
-    print("configs %d, hits %d, mismatching reads %d" % run(seed, n, "/tmp/optfuzz.fa", verbose=True, noisy=len(sys.argv) > 3 and sys.argv[3] == "noisy"))
+    mode = sys.argv[3] if len(sys.argv) > 3 else ""
+    print("configs %d, hits %d, mismatching reads %d" % run(seed, n, "/tmp/optfuzz.fa", verbose=True, noisy=mode == "noisy", wide=mode == "wide"))
