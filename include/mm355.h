@@ -80,6 +80,21 @@ typedef struct {
 	int32_t score0, dp_max, dp_max2, dp_score, cnt, n_sub, subsc, reserved;
 } mm355_hit_t;
 
+/* what minimap2's PAF writer prints besides the columns, per hit (MM355_OUT_TAGS): the fields of mm_reg1_t / mm_extra_t behind
+ * s1 / dv / de / rl / zd and the tp letter (cm, s2, ms, AS, nn come from mm355_hit_t: cnt, subsc, dp_max, dp_score, n_ambi below) */
+#define MM355_TAG_INV      1u       /* flags bit 0: r->inv (an inversion record, tp:A:I / i) */
+#define MM355_TAG_SAM_PRI  2u       /* flags bit 1: r->sam_pri (a primary without it is supplementary) */
+#define MM355_TAG_SPLIT_SHIFT 2     /* flags bits 2-3: r->split (zd) */
+typedef struct {
+	int32_t score;                  /* r->score (s1; differs from score0 on split regions) */
+	float div;                      /* r->div as mm_est_err left it; -1 = not estimated */
+	int32_t rep_len;                /* of the read, repeated on each of its hits (rl) */
+	int32_t n_ambi;
+	int32_t n_gap, n_gapo;          /* summed lengths / number of the I and D operations of the final CIGAR; 0 without a CIGAR */
+	uint32_t flags;
+	int32_t reserved;
+} mm355_tags_t;
+
 /* result of one batch; owned by the library until mm355_free_hits */
 typedef struct {
 	int64_t n_reads;
@@ -89,6 +104,7 @@ typedef struct {
 	uint32_t *cigar;
 	char *str;
 	int64_t n_hits, n_cigar, n_str;
+	mm355_tags_t *tags;             /* parallel to hits[]; NULL unless MM355_OUT_TAGS was asked for */
 } mm355_hits_t;
 
 /* --- options: replaces mm_set_opt (lib.rs:333,336) and mm_mapopt_update (lib.rs:414) --- */
@@ -125,12 +141,13 @@ int mm355_ctx_create(const mm355_index_t *idx, int device_id, mm355_ctx_t **out)
 void mm355_ctx_destroy(mm355_ctx_t *ctx);
 
 /* --- the hot path: replaces mm_map (+ mm_gen_cs / mm_gen_MD) for a whole batch of reads.
- * seqs[i] need not be NUL-terminated.  flags: bit0 = cs (short form), bit1 = MD.
+ * seqs[i] need not be NUL-terminated.  flags: bit0 = cs (short form), bit1 = MD, bit2 = tags (mm355_hits_t::tags; legal in both modes).
  * Without MM_F_CIGAR in mo->flag the call maps chain-only (minimap2 without -c): seeds, chains, regions, MAPQ from the chains, no extension.
  * Its hits have n_cigar = 0, cs_len = md_len = -1, NM = dp_max = dp_max2 = dp_score = 0; cs / MD flags are MM355_EINVAL; an index without
  * sequence (MM_I_NO_SEQ) is mappable.  The region logic runs on the device (k_regs); MM355_REGS_HOST=1 runs it on the host for every read. --- */
 #define MM355_OUT_CS 1
 #define MM355_OUT_MD 2
+#define MM355_OUT_TAGS 4
 int mm355_map_batch(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs,
                     const int32_t *lens, int flags, mm355_hits_t **out);
 /* the same call split in two, for callers that keep a batch resident in HBM (bench.py times mm355_map_resident):
@@ -183,7 +200,8 @@ typedef struct {
 	int64_t n_rounds_split;                      /* extension rounds whose direction matrices did not fit the HBM budget and were cut into several launches */
 	/* chain-only calls (mo->flag without MM_F_CIGAR): reads whose region logic ran on the device (k_regs, kernel time in ms_kernel[23]) /
 	   reads that took the host path (the RMQ stage left them to the host, an argument of logf beyond the device table, a strand_retained
-	   comparison on a divergence that pow() rounding could move, or MM355_REGS_HOST=1) */
+	   comparison on a divergence that pow() rounding could move -- with MM355_OUT_TAGS any reported divergence that it could move --, or
+	   MM355_REGS_HOST=1) */
 	int64_t n_regs_dev, n_regs_host;
 } mm355_stats_t;
 
@@ -228,7 +246,8 @@ int mm355_stage_dp(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_jobs, c
 /* the per-base walk of an aligned region (minimap2 align.c::mm_update_extra after mm_fix_cigar: mlen, blen, n_ambi, dp_max) and its cs
    string (format.c::write_cs_core, short form), as the mapping path runs them on the device for all regions of a batch (k_extra).
    Stage entry for parity tests: the query codes (0..4 per byte) come from the caller, the target from the index (contig rid, from t_st).
-   want_cs: bit 0 = cs, bit 1 = MD (format.c::write_MD_core); both strings land in `cs` (cs_off / md_off). */
+   want_cs: bit 0 = cs, bit 1 = MD (format.c::write_MD_core); both strings land in `cs` (cs_off / md_off); bit 2 = gap counts: `pad` returns
+   the number of I / D operations of the CIGAR (n_gapo) and `pad2` their summed lengths (n_gap); both stay 0 without the bit. */
 typedef struct { int64_t q_off; int64_t cigar_off; int32_t rid, t_st, n_cigar, pad; } mm355_extrajob_t;
 typedef struct { int32_t mlen, blen, n_ambi, dp_max; int64_t cs_off; int32_t cs_len, pad; int64_t md_off; int32_t md_len, pad2; } mm355_extrares_t;
 int mm355_stage_extra(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_regions, const mm355_extrajob_t *jobs,

@@ -971,7 +971,7 @@ __global__ __launch_bounds__(WAVE) void k_extra(DevIndex ix, const uint8_t *rq, 
 	char *o = cs + jb.cs_off, *om = cs + jb.md_off;
 	const bool want_cs = want & 1, want_md = want & 2;
 	int32_t n_out = 0, n_md = 0, qoff = 0, toff = 0, mlen = 0, blen = 0, n_ambi_tot = 0;
-	int32_t cs_lead = 0, md_lead = 0, flushed = 0, cs_pre = 0;
+	int32_t cs_lead = 0, md_lead = 0, flushed = 0, cs_pre = 0, n_gap = 0, n_gapo = 0;
 	unsigned run = 0, l_md = 0;      // matches pending for cs (inside the current match operation) and for MD (across operations)
 	double A = 0.0, m = 1e300, C = -1e300, P = -1e300;
 	const char *nt = "acgtn", *NT = "ACGTN";
@@ -1008,6 +1008,7 @@ __global__ __launch_bounds__(WAVE) void k_extra(DevIndex ix, const uint8_t *rq, 
 			if (want_cs) o[n_out++] = '+';
 			for (uint32_t l = 0; l < len; ++l) { const uint32_t cq = q[qoff + l]; if (cq > 3) ++n_ambi; if (want_cs) o[n_out++] = nt[cq]; }
 			blen += (int32_t)len - n_ambi; n_ambi_tot += n_ambi;
+			n_gap += (int32_t)len; ++n_gapo;
 			EX_STEP(-((double)sc.q + (double)sc.e * (double)mm_log2f_approx((float)(1.0 + (double)len))));
 			qoff += (int32_t)len;
 		} else if (op == 2) {
@@ -1016,6 +1017,7 @@ __global__ __launch_bounds__(WAVE) void k_extra(DevIndex ix, const uint8_t *rq, 
 			if (want_md) { EX_FLUSH_MD(); om[n_md++] = '^'; }
 			for (uint32_t l = 0; l < len; ++l) { const uint32_t ct = EX_T(toff + l); if (ct > 3) ++n_ambi; if (want_cs) o[n_out++] = nt[ct]; if (want_md) om[n_md++] = NT[ct]; }
 			blen += (int32_t)len - n_ambi; n_ambi_tot += n_ambi;
+			n_gap += (int32_t)len; ++n_gapo;
 			EX_STEP(-((double)sc.q + (double)sc.e * (double)mm_log2f_approx((float)(1.0 + (double)len))));
 			toff += (int32_t)len;
 		} else if (op == 3) toff += (int32_t)len;
@@ -1030,7 +1032,8 @@ __global__ __launch_bounds__(WAVE) void k_extra(DevIndex ix, const uint8_t *rq, 
 	r.cs_len = n_out; r.md_len = n_md; r.flushed = flushed;
 	r.cs_lead = (flushed & 1)? cs_lead : (int32_t)run; r.cs_tail = (flushed & 1)? (int32_t)run : 0;      // never flushed: everything it counted joins the carry
 	r.md_lead = (flushed & 2)? md_lead : (int32_t)l_md; r.md_tail = (flushed & 2)? (int32_t)l_md : 0;
-	r.cs_num = r.md_num = -1; r.cs_dense = r.md_dense = 0; r.cs_pre = (flushed & 1)? cs_pre : 0; r.pad = 0;
+	r.cs_num = r.md_num = -1; r.cs_dense = r.md_dense = 0; r.cs_pre = (flushed & 1)? cs_pre : 0;
+	r.n_gap = n_gap; r.n_gapo = n_gapo; r.pad = 0;
 	out[k] = r;
 }
 
@@ -1059,12 +1062,12 @@ __global__ __launch_bounds__(256) void k_extra_compose(Mm355ExtraSegOut *seg, co
 	const int k = blockIdx.x * 256 + threadIdx.x;
 	if (k >= n_regions) return;
 	double s = 0.0, mx = 0.0;
-	Mm355ExtraOut r; r.mlen = r.blen = r.n_ambi = 0; r.cs_len = r.md_len = 0; r.cs_dense = 0; r.md_end_num = -1; r.pad = 0;
+	Mm355ExtraOut r; r.mlen = r.blen = r.n_ambi = 0; r.cs_len = r.md_len = 0; r.cs_dense = 0; r.md_end_num = -1; r.n_gap = r.n_gapo = 0; r.pad = 0;
 	unsigned cs_carry = 0, md_carry = 0;
 	const int64_t g0 = seg_first[k], g1 = seg_first[k + 1];
 	for (int64_t g = g0; g < g1; ++g) {
 		const Mm355ExtraSegOut e = seg[g];
-		r.mlen += e.mlen; r.blen += e.blen; r.n_ambi += e.n_ambi;
+		r.mlen += e.mlen; r.blen += e.blen; r.n_ambi += e.n_ambi; r.n_gap += e.n_gap; r.n_gapo += e.n_gapo;
 		int32_t cs_num = -1, md_num = -1;
 		if (want & 1) {
 			if (e.flushed & 1) { const unsigned nn = cs_carry + (unsigned)e.cs_lead; if (nn) cs_num = (int32_t)nn; cs_carry = (unsigned)e.cs_tail; }
@@ -1230,7 +1233,7 @@ extern "C" int mm355_stage_dp(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t 
 	return 0;
 }
 
-// C-ABI: the device form of mm_update_extra's walk + cs / MD on caller-provided regions (parity tests).  want_cs: bit 0 cs, bit 1 MD
+// C-ABI: the device form of mm_update_extra's walk + cs / MD on caller-provided regions (parity tests).  want_cs: bit 0 cs, bit 1 MD, bit 2 gap counts (n_gapo in pad, n_gap in pad2)
 extern "C" int mm355_stage_extra(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_regions, const mm355_extrajob_t *jobs,
                                  const uint8_t *qcodes, int64_t n_q, const uint32_t *cigar, int64_t n_cigar, int want_cs,
                                  mm355_extrares_t *res, char *cs, int64_t cs_cap)
@@ -1265,8 +1268,8 @@ extern "C" int mm355_stage_extra(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64
 	int rc = mm355_extra_run(c, mo, segs, n_segs, first, (size_t)n_regions, (const uint32_t*)c->h_xcig.p, (size_t)n_cigar, (size_t)slot, want_cs & 3, &xo, &xcs);
 	if (rc) return rc;
 	for (int64_t k = 0; k < n_regions; ++k) {
-		mm355_extrares_t o; o.mlen = xo[k].mlen; o.blen = xo[k].blen; o.n_ambi = xo[k].n_ambi; o.dp_max = xo[k].dp_max; o.cs_off = xo[k].cs_dense; o.cs_len = (want_cs & 1)? xo[k].cs_len : 0; o.pad = 0;
-		o.md_off = xo[k].cs_dense + xo[k].cs_len; o.md_len = (want_cs & 2)? xo[k].md_len : 0; o.pad2 = 0;
+		mm355_extrares_t o; o.mlen = xo[k].mlen; o.blen = xo[k].blen; o.n_ambi = xo[k].n_ambi; o.dp_max = xo[k].dp_max; o.cs_off = xo[k].cs_dense; o.cs_len = (want_cs & 1)? xo[k].cs_len : 0; o.pad = (want_cs & 4)? xo[k].n_gapo : 0;
+		o.md_off = xo[k].cs_dense + xo[k].cs_len; o.md_len = (want_cs & 2)? xo[k].md_len : 0; o.pad2 = (want_cs & 4)? xo[k].n_gap : 0;
 		if (want_cs & 3) { if (o.cs_off + xo[k].cs_len + xo[k].md_len > cs_cap) return MM355_ENOMEM; memcpy(cs + o.cs_off, xcs + o.cs_off, (size_t)xo[k].cs_len + (size_t)xo[k].md_len); }
 		res[k] = o;
 	}

@@ -26,11 +26,14 @@ struct Mm355ExtraSegOut {
 	double A, m, C, P;
 	int32_t mlen, blen, n_ambi;
 	int32_t cs_len, cs_lead, cs_tail, md_len, md_lead, md_tail, flushed;   // *_len: body bytes in the slot; flushed: bit 0 cs, bit 1 MD
-	int32_t cs_pre, pad;           // cs bytes written BEFORE the first flush (the text of leading insertions / deletions): they stand in front of the number
+	int32_t cs_pre, n_gapo;        // cs bytes written BEFORE the first flush (the text of leading insertions / deletions): they stand in front of the number;
+	                               // n_gapo: I / D operations of the segment (a gap is never cut, so the counts of the segments add up)
 	int32_t cs_num, md_num;        // filled by k_extra_compose: the number in front of the body (-1: none)
+	int32_t n_gap, pad;            // summed lengths of those operations
 	int64_t cs_dense, md_dense;    // ... and where [number][body] goes inside the region's string
 };
-struct Mm355ExtraOut { int32_t mlen, blen, n_ambi, dp_max; int64_t cs_dense; int32_t cs_len, md_len, md_end_num, pad; };   // cs at cs_dense, MD right behind it
+struct Mm355ExtraOut { int32_t mlen, blen, n_ambi, dp_max; int64_t cs_dense; int32_t cs_len, md_len, md_end_num, n_gapo, n_gap, pad; };   // cs at cs_dense, MD right behind it;
+                                                                                          // n_gapo / n_gap: number / summed lengths of the region's I and D operations
 struct Mm355ExtraScore { int8_t mat[25]; int8_t q, e; };
 
 // Cuts one region into segments (at most MM355_EXTRA_SEG operations and MM355_EXTRA_SEG_COLS columns; a longer match operation is cut,

@@ -1180,6 +1180,7 @@ static void update_extra(Reg *r, const uint8_t *qseq, const uint8_t *tseq, const
 			int n_ambi = 0;
 			for (l = 0; l < len; ++l) if (qseq[qoff + l] > 3) ++n_ambi;
 			r->blen += len - n_ambi, p->n_ambi += n_ambi;
+			p->n_gap += (int32_t)len, ++p->n_gapo;
 			s -= q + (double)e * mm_log2f_approx((float)(1.0 + len));   // log_gap: long-read presets are never MM_F_SR
 			if (s < 0) s = 0;
 			qoff += len;
@@ -1187,6 +1188,7 @@ static void update_extra(Reg *r, const uint8_t *qseq, const uint8_t *tseq, const
 			int n_ambi = 0;
 			for (l = 0; l < len; ++l) if (tseq[toff + l] > 3) ++n_ambi;
 			r->blen += len - n_ambi, p->n_ambi += n_ambi;
+			p->n_gap += (int32_t)len, ++p->n_gapo;
 			s -= q + (double)e * mm_log2f_approx((float)(1.0 + len));
 			if (s < 0) s = 0;
 			toff += len;
@@ -1766,7 +1768,7 @@ static void gen_md(const Reg *r, const uint8_t *qseq, const uint8_t *tseq, std::
 
 // ================================================================== stage 3
 void mm355_glue_finish(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, int flags,
-                       std::vector<mm355_hit_t> &hits, std::vector<uint32_t> &cigar, std::string &str)
+                       std::vector<mm355_hit_t> &hits, std::vector<uint32_t> &cigar, std::string &str, std::vector<mm355_tags_t> *tags)
 {
 	int n = (int)rs.regs.size();
 	Reg *regs = rs.regs.data();
@@ -1798,13 +1800,21 @@ void mm355_glue_finish(const mm355_index *mi, const mm355_mapopt_t *opt, ReadSta
 			if (flags & MM355_OUT_MD) { h.md_off = (int64_t)str.size(); h.md_len = (int64_t)r->p->md.size(); str += r->p->md; str += '\0'; }
 		}
 		hits.push_back(h);
+		if (tags) {   // MM355_OUT_TAGS: what U:format.c::mm_write_paf reads of the region besides the columns
+			mm355_tags_t t;
+			memset(&t, 0, sizeof(t));
+			t.score = r->score; t.div = r->div; t.rep_len = rs.rep_len;
+			t.flags = (r->inv? MM355_TAG_INV : 0u) | (r->sam_pri? MM355_TAG_SAM_PRI : 0u) | (r->split & 3u) << MM355_TAG_SPLIT_SHIFT;
+			if (r->p) { t.n_ambi = (int32_t)r->p->n_ambi; t.n_gap = r->p->n_gap; t.n_gapo = r->p->n_gapo; }
+			tags->push_back(t);
+		}
 	}
 }
 
 // ================================================================== chain-only (no MM_F_CIGAR): U:map.c::align_regs returns at once, then
 // U:hit.c::mm_set_mapq on its r->p == NULL branch -- no filter_regs, hit_sort or second set_parent.  The host path of the reads that the
 // device's region stage (mm355_regs.h) does not take.
-void mm355_glue_chain_finish(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, std::vector<mm355_hit_t> &hits)
+void mm355_glue_chain_finish(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, std::vector<mm355_hit_t> &hits, std::vector<mm355_tags_t> *tags)
 {
 	const int n = (int)rs.regs.size();
 	set_mapq(n, rs.regs.data(), opt->min_chain_score, opt->a, rs.rep_len);
@@ -1817,6 +1827,12 @@ void mm355_glue_chain_finish(const mm355_index *mi, const mm355_mapopt_t *opt, R
 		mm355_hit_t h;
 		mm355r_hit(&t, r->mapq, mi->seq_len.data(), &h);
 		hits.push_back(h);
+		if (tags) {
+			t.score = r->score; t.div = r->div; t.sam_pri = (uint16_t)r->sam_pri;
+			mm355_tags_t g;
+			mm355r_tags(&t, rs.rep_len, &g);
+			tags->push_back(g);
+		}
 	}
 }
 
@@ -1851,6 +1867,7 @@ void mm355_glue_extra_apply(ReadState &rs, const Mm355ExtraOut *out, const char 
 	for (Reg &r : rs.regs) if (r.p && r.p->deferred) {
 		const Mm355ExtraOut &o = out[k++];
 		r.mlen = o.mlen; r.blen = o.blen; r.p->n_ambi += (uint32_t)o.n_ambi; r.p->dp_max = o.dp_max;
+		r.p->n_gap += o.n_gap; r.p->n_gapo += o.n_gapo;
 		if (want & MM355_OUT_CS) r.p->cs.assign(cs + o.cs_dense, (size_t)o.cs_len);
 		if (want & MM355_OUT_MD) r.p->md.assign(cs + o.cs_dense + o.cs_len, (size_t)o.md_len);
 		r.p->deferred = false;

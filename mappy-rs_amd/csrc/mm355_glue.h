@@ -11,6 +11,7 @@
 struct Extra {
 	int32_t dp_score = 0, dp_max = 0, dp_max2 = 0;
 	uint32_t n_ambi = 0;
+	int32_t n_gap = 0, n_gapo = 0;   // summed lengths / number of the I and D operations, counted by the same walk as n_ambi (MM355_OUT_TAGS: the de tag)
 	std::vector<uint32_t> cigar;
 	std::string cs, md;     // written when the region is committed (the code strings are at hand there)
 	// deferred = the per-base walk of U:align.c::mm_update_extra (mlen / blen / n_ambi / dp_max) and the cs string are left to the device
@@ -92,13 +93,14 @@ void mm355_glue_pre_align(const mm355_index *mi, const mm355_mapopt_t *opt, Read
 // its first half alone: re-chain (if triggered), gen_regs, set_parent + select_sub, est_err, filter_strand_retained -> rs.regs
 void mm355_glue_regions(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, int rmq_state);
 // chain-only (no MM_F_CIGAR), after mm355_glue_regions: MAPQ from the chains and the hit records, in the order of rs.regs
-void mm355_glue_chain_finish(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, std::vector<mm355_hit_t> &hits);
+// (tags != 0: one mm355_tags_t per record as well, MM355_OUT_TAGS)
+void mm355_glue_chain_finish(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, std::vector<mm355_hit_t> &hits, std::vector<mm355_tags_t> *tags = 0);
 // stage 2: advance the skeleton of one read as far as cached DP results allow; appends missing DP problems to `reqs`.
 // returns true when the read needs no more DP.
 bool mm355_glue_align_step(const mm355_index *mi, const mm355_mapopt_t *opt, int read_id, ReadState &rs, std::vector<DpReq> &reqs, int flags);
 // stage 3: post-DP filtering, sorting, selection and MAPQ; emits hit records
 void mm355_glue_finish(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, int flags,
-                       std::vector<mm355_hit_t> &hits, std::vector<uint32_t> &cigar, std::string &str);
+                       std::vector<mm355_hit_t> &hits, std::vector<uint32_t> &cigar, std::string &str, std::vector<mm355_tags_t> *tags = 0);
 void mm355_glue_release(ReadState &rs);
 // between the last extension round and stage 3, when rs.defer_extra: the regions whose walk was left to the device.
 // count: number of such regions, of their CIGAR operations and of cs bytes to reserve; fill: descriptors + CIGARs at the given offsets;

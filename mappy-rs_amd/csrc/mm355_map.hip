@@ -364,7 +364,7 @@ extern "C" int mm355_map_resident(mm355_ctx_t *c, const mm355_mapopt_t *mo, int 
 	if (chain_only) {   // the chains are on the device: regions, MAPQ and records there (mm355_regs.hip); no pack, no extension rounds
 		tv_front = now_ms() - tv0; trace_add(c, "front", tv0, now_ms());
 		const double tr0 = now_ms();
-		if ((rc = mm355_map_chain_only(c, mo, dl, out))) return rc;
+		if ((rc = mm355_map_chain_only(c, mo, dl, flags, out))) return rc;
 		trace_add(c, "regs", tr0, now_ms());
 		mm355_timers_resolve(c);
 		if (verbose) fprintf(stderr, "[mm355] map_resident (chain-only): front %.1f ms | regions %.1f (%lld reads on the device, %lld on the host) | total %.1f\n",
@@ -488,9 +488,11 @@ extern "C" int mm355_map_resident(mm355_ctx_t *c, const mm355_mapopt_t *mo, int 
 	std::vector<std::vector<mm355_hit_t>> rh(n_reads);
 	std::vector<std::vector<uint32_t>> rc_(n_reads);
 	std::vector<std::string> rstr(n_reads);
+	const bool want_tags = (flags & MM355_OUT_TAGS) != 0;
+	std::vector<std::vector<mm355_tags_t>> rt(want_tags? (size_t)n_reads : 0);   // parallel to rh
 	parallel_for(n_reads, nt, [&](int64_t i, int) {
 		ProfScope pf(PF_FINISH);
-		if (rs[i].qlen > 0) mm355_glue_finish(mi, mo, rs[i], flags, rh[i], rc_[i], rstr[i]);
+		if (rs[i].qlen > 0) mm355_glue_finish(mi, mo, rs[i], flags, rh[i], rc_[i], rstr[i], want_tags? &rt[i] : 0);
 		mm355_glue_release(rs[i]);
 	});
 	tv_fin = now_ms() - th1; trace_add(c, "finish", th1, now_ms()); tv0 = now_ms();
@@ -504,6 +506,10 @@ extern "C" int mm355_map_resident(mm355_ctx_t *c, const mm355_mapopt_t *mo, int 
 	H->hits = (mm355_hit_t*)malloc((nh > 0? nh : 1) * sizeof(mm355_hit_t));
 	H->cigar = (uint32_t*)malloc((nc > 0? nc : 1) * 4);
 	H->str = (char*)malloc(ns > 0? ns : 1);
+	if (want_tags) {
+		H->tags = (mm355_tags_t*)malloc((nh > 0? nh : 1) * sizeof(mm355_tags_t));
+		for (int64_t i = 0; i < n_reads; ++i) if (!rt[i].empty()) memcpy(H->tags + H->hit_off[i], rt[i].data(), rt[i].size() * sizeof(mm355_tags_t));
+	}
 	nh = nc = ns = 0;
 	for (int64_t i = 0; i < n_reads; ++i) {
 		for (mm355_hit_t h : rh[i]) {
@@ -541,5 +547,5 @@ extern "C" int mm355_map_resident(mm355_ctx_t *c, const mm355_mapopt_t *mo, int 
 extern "C" void mm355_free_hits(mm355_hits_t *h)
 {
 	if (h == 0) return;
-	free(h->hit_off); free(h->status); free(h->hits); free(h->cigar); free(h->str); free(h);
+	free(h->hit_off); free(h->status); free(h->hits); free(h->cigar); free(h->str); free(h->tags); free(h);
 }

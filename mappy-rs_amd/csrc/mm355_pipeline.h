@@ -131,7 +131,7 @@ int mm355_run_chain_skip(mm355_ctx *c);
 int mm355_run_rmq(mm355_ctx *c, const mm355_mapopt_t *mo, const DevParams &pr);   // mg_lchain_rmq on the device: long-join re-chain, or the primary chainer of MM_F_RMQ presets
 // chain-only tail of a batch (mo->flag without MM_F_CIGAR), after mm355_run_rmq: regions, MAPQ and hit records on the device (k_regs), the
 // reads it does not take on the host; qlen[i] = 0 for reads that are not mapped (empty, longer than max_qlen)
-int mm355_map_chain_only(mm355_ctx *c, const mm355_mapopt_t *mo, const std::vector<int32_t> &qlen, mm355_hits_t **out);
+int mm355_map_chain_only(mm355_ctx *c, const mm355_mapopt_t *mo, const std::vector<int32_t> &qlen, int flags, mm355_hits_t **out);
 
 // time one launch group on the context's stream with HIP events (the stream the kernels are launched on)
 // Stage timers.  EvTimer records a pair of events around the launches of a stage and does NOT synchronise: the pairs are turned into

@@ -11,6 +11,8 @@
 //         An argument beyond the table sends the read to the host.
 //   pow   (mm_est_err): the result only reaches the records through filter_strand_retained's comparisons.  A region whose float divergence
 //         could change under a few ulp of error in pow is marked; a read whose comparisons read a marked divergence goes to the host.
+//         With tags rows requested (MM355_OUT_TAGS) the divergence itself is reported: then a read goes to the host as soon as any region
+//         that survives to a hit row is marked.
 #pragma once
 #include "../../include/mm355.h"
 #include "mm355_core.h"
@@ -22,7 +24,8 @@
 struct Mm355Reg {           // the fields of U:minimap.h::mm_reg1_t the chain-only tail reads or writes
 	int32_t id, parent, cnt, rid, score, score0;
 	int32_t qs, qe, rs, re, as, mlen, blen, subsc, n_sub;
-	uint32_t hash, rev, strand_retained, div_unsure;
+	uint32_t hash, rev, strand_retained;
+	uint16_t div_unsure, sam_pri;
 	float div;
 };
 
@@ -188,18 +191,21 @@ MM_HD void mm355r_set_parent(float mask_level, int mask_len, int n, Mm355Reg *r,
 	}
 }
 
-// U:hit.c::mm_sync_regs (ids are region indices here: tmp needs n entries)
+// U:hit.c::mm_sync_regs (ids are region indices here: tmp needs n entries), with its closing mm_set_sam_pri: the first primary gets sam_pri.
+// Chain-only mapping has no other call of mm_set_sam_pri, so a read whose select_sub drops nothing keeps sam_pri = 0 everywhere.
 MM_HD void mm355r_sync_regs(int n, Mm355Reg *r, int32_t *tmp, int n_tmp)
 {
 	if (n <= 0) return;
 	for (int i = 0; i < n_tmp; ++i) tmp[i] = -1;
 	for (int i = 0; i < n; ++i) if (r[i].id >= 0 && r[i].id < n_tmp) tmp[r[i].id] = i;
+	int n_pri = 0;
 	for (int i = 0; i < n; ++i) {
 		Mm355Reg *ri = &r[i];
 		ri->id = i;
 		if (ri->parent == MM355_PARENT_TMP_PRI) ri->parent = i;
 		else if (ri->parent >= 0 && ri->parent < n_tmp && tmp[ri->parent] >= 0) ri->parent = tmp[ri->parent];
 		else ri->parent = MM355_PARENT_UNSET;
+		ri->sam_pri = ri->parent == i && ++n_pri == 1;
 	}
 }
 
@@ -333,11 +339,33 @@ MM_HD void mm355r_hit(const Mm355Reg *r, uint32_t mapq, const uint32_t *seq_len,
 	h->score0 = r->score0; h->cnt = r->cnt; h->n_sub = r->n_sub; h->subsc = r->subsc;
 }
 
+// the tags row of a chain-only hit (MM355_OUT_TAGS): no CIGAR, so no n_ambi / gap counts; no inversion or split regions before extension
+MM_HD void mm355r_tags(const Mm355Reg *r, int32_t rep_len, mm355_tags_t *t)
+{
+	memset(t, 0, sizeof(*t));
+	t->score = r->score; t->div = r->div; t->rep_len = rep_len;
+	t->flags = r->sam_pri? MM355_TAG_SAM_PRI : 0u;
+}
+
+// the second half of the tail, on the regions est_err left: filter_strand_retained, the pow rules, MAPQ, the rows (and the tags rows)
+MM_HD int mm355r_finish(const Mm355RegsOpt &o, const uint32_t *seq_len, int32_t rep_len, int n, Mm355Reg *r, const float *logt, int32_t n_logt,
+                        uint32_t *mapq, mm355_hit_t *out, mm355_tags_t *tags)
+{
+	n = mm355r_filter_strand_retained(n, r);
+	if (n < 0) return -MM355_REGS_DEFER_POW;
+	if (tags) for (int i = 0; i < n; ++i) if (r[i].div_unsure) return -MM355_REGS_DEFER_POW;   // the divergence itself is reported
+	if (!mm355r_set_mapq(n, r, o.min_chain_score, rep_len, logt, n_logt, mapq)) return -MM355_REGS_DEFER_LOG;
+	for (int i = 0; i < n; ++i) mm355r_hit(&r[i], mapq[i], seq_len, &out[i]);
+	if (tags) for (int i = 0; i < n; ++i) mm355r_tags(&r[i], rep_len, &tags[i]);
+	return n;
+}
+
 // the whole tail of one read.  Returns the number of hit rows written to `out` (at most n_u), or -MM355_REGS_DEFER_* when the read must
-// take the host path.  `mapq` is scratch of n_u words.
+// take the host path.  `mapq` is scratch of n_u words.  tags != 0: one tags row per hit row, and the stricter pow rule (a reported
+// divergence must not depend on the device's pow).
 MM_HD int mm355_regs_read(const Mm355RegsOpt &o, const uint32_t *seq_len, int32_t qlen, int32_t rep_len, int n_u, const uint64_t *u, const mm128 *a,
                           int32_t n_mini, const uint64_t *mini_pos, const float *logt, int32_t n_logt, const Mm355RegsScratch &s, uint32_t *mapq,
-                          mm355_hit_t *out)
+                          mm355_hit_t *out, mm355_tags_t *tags = nullptr)
 {
 	if (n_u <= 0 || qlen <= 0) return 0;
 	Mm355Reg *r = s.r;
@@ -347,9 +375,5 @@ MM_HD int mm355_regs_read(const Mm355RegsOpt &o, const uint32_t *seq_len, int32_
 		n = mm355r_select_sub(o.pri_ratio, o.min_diff, o.best_n, o.min_strand_sc, n, r, s.tmp);
 	}
 	mm355r_est_err(seq_len, qlen, n, r, a, n_mini, mini_pos);
-	n = mm355r_filter_strand_retained(n, r);
-	if (n < 0) return -MM355_REGS_DEFER_POW;
-	if (!mm355r_set_mapq(n, r, o.min_chain_score, rep_len, logt, n_logt, mapq)) return -MM355_REGS_DEFER_LOG;
-	for (int i = 0; i < n; ++i) mm355r_hit(&r[i], mapq[i], seq_len, &out[i]);
-	return n;
+	return mm355r_finish(o, seq_len, rep_len, n, r, logt, n_logt, mapq, out, tags);
 }

@@ -2,8 +2,9 @@
 // (mm355_run_rmq) the chains of every read are still in HBM (u / a at aoff, mini_pos at roff).  k_regs turns them into regions, selects
 // primaries and secondaries, estimates the divergence, computes MAPQ and writes the hit rows on the device (mm355_regs.h, a lane per read);
 // only the rows and one count per read come back.  Reads the device does not decide -- those the RMQ stage left to the host, and those
-// mm355_regs.h defers (logf argument beyond the table, a strand_retained comparison on an unsure divergence) -- are packed alone and run
-// through mm355_glue_regions + mm355_glue_chain_finish on the host pool.  MM355_REGS_HOST=1 sends every read that way.
+// mm355_regs.h defers (logf argument beyond the table, a strand_retained comparison on an unsure divergence, with MM355_OUT_TAGS any
+// reported divergence that is unsure) -- are packed alone and run through mm355_glue_regions + mm355_glue_chain_finish on the host pool.
+// MM355_REGS_HOST=1 sends every read that way.  With MM355_OUT_TAGS a tags row (mm355_tags_t) goes with every hit row on both paths.
 #include <stdio.h>
 #include <string.h>
 #include <mutex>
@@ -20,21 +21,33 @@ struct RegsRead {                 // per read of the batch
 	int32_t run, pad;             // run: 1 = the device takes the read
 };
 
-__global__ __launch_bounds__(64) void k_regs(int n_reads, const RegsRead *rr, const int64_t *aoff, const int64_t *roff, const uint64_t *u,
-                                             const mm128 *a, const uint64_t *mini_pos, const uint32_t *seq_len, Mm355RegsOpt o,
-                                             const float *logt, int32_t n_logt, Mm355Reg *sr, mm128 *sz, uint64_t *scov, int32_t *sw,
-                                             int32_t *stmp, uint32_t *smq, mm355_hit_t *hits, int32_t *cnt)
+#define K_REGS_ARGS int n_reads, const RegsRead *rr, const int64_t *aoff, const int64_t *roff, const uint64_t *u,                     \
+                    const mm128 *a, const uint64_t *mini_pos, const uint32_t *seq_len, Mm355RegsOpt o,                           \
+                    const float *logt, int32_t n_logt, Mm355Reg *sr, mm128 *sz, uint64_t *scov, int32_t *sw,                     \
+                    int32_t *stmp, uint32_t *smq, mm355_hit_t *hits, int32_t *cnt
+__device__ __forceinline__ void regs_lane(K_REGS_ARGS, mm355_tags_t *tags)
 {
 	const int r = blockIdx.x * 64 + threadIdx.x;
 	if (r >= n_reads) return;
 	const RegsRead q = rr[r];
 	if (!q.run) { cnt[r] = 0; return; }
-	const int64_t h = q.hoff;     // every write of the read stays in [h, h + n_u) of each scratch array and of hits
+	const int64_t h = q.hoff;     // every write of the read stays in [h, h + n_u) of each scratch array, of hits and of tags
 	Mm355RegsScratch s;
 	s.r = sr + h; s.z = sz + h; s.cov = scov + h; s.w = sw + h; s.tmp = stmp + h;
 	const int64_t ao = aoff[r];
-	cnt[r] = mm355_regs_read(o, seq_len, q.qlen, q.rep_len, q.n_u, u + ao, a + ao, q.n_mini, mini_pos + roff[r], logt, n_logt, s, smq + h, hits + h);
+	cnt[r] = mm355_regs_read(o, seq_len, q.qlen, q.rep_len, q.n_u, u + ao, a + ao, q.n_mini, mini_pos + roff[r], logt, n_logt, s, smq + h, hits + h,
+	                         tags? tags + h : nullptr);
 }
+// two entry points over one body: without MM355_OUT_TAGS the kernel takes the arguments and runs the code it always did
+__global__ __launch_bounds__(64) void k_regs(K_REGS_ARGS)
+{
+	regs_lane(n_reads, rr, aoff, roff, u, a, mini_pos, seq_len, o, logt, n_logt, sr, sz, scov, sw, stmp, smq, hits, cnt, nullptr);
+}
+__global__ __launch_bounds__(64) void k_regs_tags(K_REGS_ARGS, mm355_tags_t *tags)
+{
+	regs_lane(n_reads, rr, aoff, roff, u, a, mini_pos, seq_len, o, logt, n_logt, sr, sz, scov, sw, stmp, smq, hits, cnt, tags);
+}
+#undef K_REGS_ARGS
 
 // u[], chained anchors and mini_pos[] of the listed reads into three dense arrays (k_pack_chains for a subset)
 __global__ __launch_bounds__(256) void k_pack_sel(int n_sel, const int32_t *sel, const int64_t *aoff, const int64_t *roff, const int32_t *n_u,
@@ -60,9 +73,10 @@ static const std::vector<float> &host_logt()
 
 static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-int mm355_map_chain_only(mm355_ctx *c, const mm355_mapopt_t *mo, const std::vector<int32_t> &qlen, mm355_hits_t **out)
+int mm355_map_chain_only(mm355_ctx *c, const mm355_mapopt_t *mo, const std::vector<int32_t> &qlen, int flags, mm355_hits_t **out)
 {
 	*out = 0;
+	const bool want_tags = (flags & MM355_OUT_TAGS) != 0;
 	const mm355_index *mi = c->mi;
 	HostBatch &hb = c->hb;
 	const int64_t n_reads = hb.n_reads;
@@ -86,12 +100,14 @@ int mm355_map_chain_only(mm355_ctx *c, const mm355_mapopt_t *mo, const std::vect
 	const size_t nt = (size_t)(tot > 0? tot : 1);
 	const size_t o_z = al256(nt * sizeof(Mm355Reg)), o_cov = o_z + al256(nt * 16), o_w = o_cov + al256(nt * 8), o_tmp = o_w + al256(nt * 4),
 	             o_mq = o_tmp + al256(nt * 4), o_hit = o_mq + al256(nt * 4), o_cnt = o_hit + al256(nt * sizeof(mm355_hit_t)),
-	             scr_b = o_cnt + al256((size_t)(n_reads + 1) * 4);
-	const size_t out_b = al256(nt * sizeof(mm355_hit_t)) + (size_t)(n_reads + 1) * 4;
+	             o_tag = o_cnt + al256((size_t)(n_reads + 1) * 4), scr_b = o_tag + (want_tags? al256(nt * sizeof(mm355_tags_t)) : 0);
+	const size_t ho_tag = al256(nt * sizeof(mm355_hit_t)) + al256((size_t)(n_reads + 1) * 4);
+	const size_t out_b = ho_tag + (want_tags? nt * sizeof(mm355_tags_t) : 0);
 	if (c->regs_scr.ensure(scr_b) || c->regs_in.ensure((size_t)(n_reads + 1) * sizeof(RegsRead)) || c->h_regs_out.ensure(out_b)) return MM355_ENOMEM;
 	char *scr = c->regs_scr.as<char>();
 	mm355_hit_t *h_rows = (mm355_hit_t*)c->h_regs_out.p;
 	int32_t *h_cnt = (int32_t*)((char*)c->h_regs_out.p + al256(nt * sizeof(mm355_hit_t)));
+	mm355_tags_t *h_tags = want_tags? (mm355_tags_t*)((char*)c->h_regs_out.p + ho_tag) : 0;
 	if (n_run > 0) {
 		if (!c->logt_ok) {
 			const std::vector<float> &t = host_logt();
@@ -105,14 +121,18 @@ int mm355_map_chain_only(mm355_ctx *c, const mm355_mapopt_t *mo, const std::vect
 		o.min_diff = mi->k * 2; o.min_strand_sc = (int)(mo->max_gap * 0.8); o.min_chain_score = mo->min_chain_score; o.seed = mo->seed;
 		HIPCHK(hipMemcpyAsync(c->regs_in.p, rr, (size_t)n_reads * sizeof(RegsRead), hipMemcpyHostToDevice, c->st));
 		mm355_kt(c, KT_REGS, 0, c->st);
-		hipLaunchKernelGGL(k_regs, dim3((unsigned)((n_reads + 63) / 64)), dim3(64), 0, c->st, (int)n_reads, c->regs_in.as<RegsRead>(),
-		                   c->aoff.as<int64_t>(), c->roff.as<int64_t>(), c->u.as<uint64_t>(), c->a.as<mm128>(), c->mini_pos.as<uint64_t>(),
-		                   c->dix.seq_len, o, c->logt.as<float>(), n_logt, (Mm355Reg*)scr, (mm128*)(scr + o_z), (uint64_t*)(scr + o_cov),
-		                   (int32_t*)(scr + o_w), (int32_t*)(scr + o_tmp), (uint32_t*)(scr + o_mq), (mm355_hit_t*)(scr + o_hit), (int32_t*)(scr + o_cnt));
+#define K_REGS_ACTUALS (int)n_reads, c->regs_in.as<RegsRead>(), c->aoff.as<int64_t>(), c->roff.as<int64_t>(), c->u.as<uint64_t>(), c->a.as<mm128>(),    \
+		               c->mini_pos.as<uint64_t>(), c->dix.seq_len, o, c->logt.as<float>(), n_logt, (Mm355Reg*)scr, (mm128*)(scr + o_z),                    \
+		               (uint64_t*)(scr + o_cov), (int32_t*)(scr + o_w), (int32_t*)(scr + o_tmp), (uint32_t*)(scr + o_mq), (mm355_hit_t*)(scr + o_hit),      \
+		               (int32_t*)(scr + o_cnt)
+		if (want_tags) hipLaunchKernelGGL(k_regs_tags, dim3((unsigned)((n_reads + 63) / 64)), dim3(64), 0, c->st, K_REGS_ACTUALS, (mm355_tags_t*)(scr + o_tag));
+		else hipLaunchKernelGGL(k_regs, dim3((unsigned)((n_reads + 63) / 64)), dim3(64), 0, c->st, K_REGS_ACTUALS);
+#undef K_REGS_ACTUALS
 		mm355_kt(c, KT_REGS, 1, c->st);
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipMemcpyAsync(h_cnt, scr + o_cnt, (size_t)n_reads * 4, hipMemcpyDeviceToHost, c->st));
 		if (tot > 0) HIPCHK(hipMemcpyAsync(h_rows, scr + o_hit, (size_t)tot * sizeof(mm355_hit_t), hipMemcpyDeviceToHost, c->st));
+		if (tot > 0 && want_tags) HIPCHK(hipMemcpyAsync(h_tags, scr + o_tag, (size_t)tot * sizeof(mm355_tags_t), hipMemcpyDeviceToHost, c->st));
 		HIPCHK(mm355_wait_stream(c->st));
 	}
 	// the host path: reads the device did not take or deferred
@@ -120,6 +140,7 @@ int mm355_map_chain_only(mm355_ctx *c, const mm355_mapopt_t *mo, const std::vect
 	for (int64_t i = 0; i < n_reads; ++i) if (qlen[i] > 0 && (!rr[i].run || h_cnt[i] < 0)) sel.push_back((int32_t)i);
 	const int64_t n_sel = (int64_t)sel.size();
 	std::vector<std::vector<mm355_hit_t>> hh((size_t)n_sel);
+	std::vector<std::vector<mm355_tags_t>> ht(want_tags? (size_t)n_sel : 0);
 	if (n_sel > 0) {
 		std::vector<int64_t> offs((size_t)(n_sel + 1) * 3);
 		int64_t *uo = offs.data(), *vo = uo + n_sel + 1, *mo_ = vo + n_sel + 1;
@@ -157,7 +178,7 @@ int mm355_map_chain_only(mm355_ctx *c, const mm355_mapopt_t *mo, const std::vect
 			int rst = hb.rmq_state.empty()? MM355_RMQ_HOST_ALL : (int)hb.rmq_state[r];
 			if (rst == MM355_RMQ_HOST_ALL) { if (rmq_chain) mm355_glue_chain_rmq(mi, mo, rs); rst = -1; }   // every mg_lchain_rmq call of this read on the host
 			mm355_glue_regions(mi, mo, rs, rst);
-			mm355_glue_chain_finish(mi, mo, rs, hh[j]);
+			mm355_glue_chain_finish(mi, mo, rs, hh[j], want_tags? &ht[j] : 0);
 		};
 		if (mm355_parallel_hook) mm355_parallel_hook(n_sel, one);
 		else for (int64_t j = 0; j < n_sel; ++j) one(j);
@@ -178,11 +199,17 @@ int mm355_map_chain_only(mm355_ctx *c, const mm355_mapopt_t *mo, const std::vect
 	H->hits = (mm355_hit_t*)malloc((nh > 0? nh : 1) * sizeof(mm355_hit_t));
 	H->cigar = (uint32_t*)malloc(4);
 	H->str = (char*)malloc(1);
-	if (!H->hit_off || !H->status || !H->hits || !H->cigar || !H->str) { mm355_free_hits(H); return MM355_ENOMEM; }
+	if (want_tags) H->tags = (mm355_tags_t*)malloc((nh > 0? nh : 1) * sizeof(mm355_tags_t));
+	if (!H->hit_off || !H->status || !H->hits || !H->cigar || !H->str || (want_tags && !H->tags)) { mm355_free_hits(H); return MM355_ENOMEM; }
 	for (int64_t i = 0, j = 0; i < n_reads; ++i) {
 		mm355_hit_t *dst = H->hits + H->hit_off[i];
 		if (j < n_sel && sel[j] == i) { if (!hh[j].empty()) memcpy(dst, hh[j].data(), hh[j].size() * sizeof(mm355_hit_t)); ++j; }
 		else if (rr[i].run && h_cnt[i] > 0) memcpy(dst, h_rows + rr[i].hoff, (size_t)h_cnt[i] * sizeof(mm355_hit_t));
+	}
+	if (want_tags) for (int64_t i = 0, j = 0; i < n_reads; ++i) {   // the same merge for the tags rows
+		mm355_tags_t *dst = H->tags + H->hit_off[i];
+		if (j < n_sel && sel[j] == i) { if (!ht[j].empty()) memcpy(dst, ht[j].data(), ht[j].size() * sizeof(mm355_tags_t)); ++j; }
+		else if (rr[i].run && h_cnt[i] > 0) memcpy(dst, h_tags + rr[i].hoff, (size_t)h_cnt[i] * sizeof(mm355_tags_t));
 	}
 	c->stats.n_regs_dev = n_dev; c->stats.n_regs_host = n_sel;
 	*out = H;

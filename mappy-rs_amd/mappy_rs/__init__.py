@@ -27,7 +27,7 @@ import numpy as np
 
 from . import _ffi
 
-__all__ = ["Aligner", "Mapping", "shard_by_bases", "order_by_length"]
+__all__ = ["Aligner", "Mapping", "paf_line", "shard_by_bases", "order_by_length"]
 
 _CIGAR_OPS = "MIDNSHP=X"
 
@@ -46,15 +46,22 @@ _HIT_DTYPE = np.dtype([(k, np.dtype(t)) for k, t in _ffi.Hit._fields_], align=Tr
 (_QS, _QE, _ST, _RID, _TL, _TS, _TE, _ML, _BL, _MQ, _PR, _NM, _NC, _CO, _CSO, _CSL, _MDO, _MDL) = (_F[k] for k in (
     "query_start", "query_end", "strand", "rid", "target_len", "target_start", "target_end", "match_len", "block_len", "mapq",
     "is_primary", "NM", "n_cigar", "cigar_off", "cs_off", "cs_len", "md_off", "md_len"))
+# a record mapped with tags=True: the row of the mm355_tags_t array stands behind the hit row in the same tuple
+_TAG_DTYPE = np.dtype([(k, np.dtype(t)) for k, t in _ffi.Tags._fields_], align=True)
+_T0 = len(_HIT_FIELDS)
+_TAG_HIT = tuple(_F[k] for k in ("subsc", "cnt", "dp_max", "dp_score"))
+# what a record keeps of its tags (view: built on access, detached: _own[15]):
+# (s1, div, rl, n_ambi, n_gap, n_gapo, flags, s2, cm, ms, AS)
+(_G_S1, _G_DIV, _G_RL, _G_NN, _G_GAP, _G_GAPO, _G_FL, _G_S2, _G_CM, _G_MS, _G_AS) = range(11)
 
 
 class _HitBatch:
     """what the Mapping records of one mm355_hits_t share: the packed CIGAR words, the string arena, the contig names, and whether the batch
     was mapped without CIGARs (chain-only: no extension, records come from the chains)"""
-    __slots__ = ("cig", "sbuf", "names", "chain_only")
+    __slots__ = ("cig", "sbuf", "names", "chain_only", "tags")
 
-    def __init__(self, cig, sbuf, names, chain_only=False):
-        self.cig, self.sbuf, self.names, self.chain_only = cig, sbuf, names, chain_only
+    def __init__(self, cig, sbuf, names, chain_only=False, tags=False):
+        self.cig, self.sbuf, self.names, self.chain_only, self.tags = cig, sbuf, names, chain_only, tags
 
 
 class Mapping:
@@ -77,7 +84,7 @@ class Mapping:
         self._r = None
         self._cig = list(cigar)
         self._own = (query_start, query_end, strand, target_name, target_len, target_start, target_end, match_len, block_len, mapq,
-                     bool(is_primary), NM, MD, cs, False)
+                     bool(is_primary), NM, MD, cs, False, None)
 
     @classmethod
     def _view(cls, batch, row):
@@ -110,7 +117,7 @@ class Mapping:
             md = b.sbuf[r[_MDO]:r[_MDO] + r[_MDL]].decode() if r[_MDL] >= 0 else None
             cs = b.sbuf[r[_CSO]:r[_CSO] + r[_CSL]].decode() if r[_CSL] >= 0 else None
             self._own = (r[_QS], r[_QE], r[_ST], b.names[r[_RID]], r[_TL], r[_TS], r[_TE], r[_ML], r[_BL], r[_MQ], bool(r[_PR]), r[_NM], md, cs,
-                         b.chain_only)
+                         b.chain_only, self._tags())
             self._b = self._r = None
         return self
 
@@ -132,6 +139,67 @@ class Mapping:
         if self._own is None:
             self.detach()
         return self._cig
+
+    # ---- minimap2's PAF tags (Aligner(tags=True)); every one is None on a record mapped without tags
+    def _tags(self):
+        if self._own is not None:
+            return self._own[15]
+        if not self._b.tags:
+            return None
+        r = self._r
+        return r[_T0:_T0 + 7] + tuple(r[i] for i in _TAG_HIT)
+
+    def _tag(self, i):
+        t = self._tags()
+        return None if t is None else t[i]
+
+    def _has_cigar(self):
+        return not (self._b.chain_only if self._own is None else self._own[14])
+
+    s1 = property(lambda s: s._tag(_G_S1), doc="chaining score of the region (r->score)")
+    s2 = property(lambda s: s._tag(_G_S2), doc="chaining score of the best secondary (r->subsc)")
+    cm = property(lambda s: s._tag(_G_CM), doc="number of minimizers on the chain (r->cnt)")
+    ms = property(lambda s: s._tag(_G_MS), doc="DP score of the max-scoring segment (r->p->dp_max)")
+    AS = property(lambda s: s._tag(_G_AS), doc="DP alignment score (r->p->dp_score)")
+    nn = property(lambda s: s._tag(_G_NN), doc="ambiguous bases in the alignment (r->p->n_ambi)")
+    rl = property(lambda s: s._tag(_G_RL), doc="length of query regions harbouring repetitive seeds (per read)")
+
+    @property
+    def zd(self):
+        """r->split: bit 0 = the region was split on its right, bit 1 = on its left (0: not split; minimap2 prints zd only then)"""
+        t = self._tags()
+        return None if t is None else t[_G_FL] >> _ffi.TAG_SPLIT_SHIFT & 3
+
+    @property
+    def dv(self):
+        """approximate per-base divergence from the chain (mm_est_err); None with a CIGAR (minimap2 prints de instead) or when not estimated"""
+        t = self._tags()
+        if t is None or self._has_cigar() or not 0.0 <= t[_G_DIV] <= 1.0:
+            return None
+        return t[_G_DIV]
+
+    @property
+    def de(self):
+        """gap-compressed per-base divergence, 1 - mlen / (blen + n_ambi - n_gap + n_gapo); None without a CIGAR"""
+        t = self._tags()
+        if t is None or not self._has_cigar():
+            return None
+        return 1.0 - float(self.match_len) / (self.block_len + t[_G_NN] - t[_G_GAP] + t[_G_GAPO])
+
+    @property
+    def tp(self):
+        """'P' primary, 'S' secondary, 'I' / 'i' the same for an inversion record"""
+        t = self._tags()
+        if t is None:
+            return None
+        inv = t[_G_FL] & _ffi.TAG_INV
+        return ("I" if inv else "P") if self.is_primary else ("i" if inv else "S")
+
+    @property
+    def is_supplementary(self):
+        """a primary record that is not the read's first one (SAM flag 0x800: parent == id without sam_pri)"""
+        t = self._tags()
+        return None if t is None else bool(self.is_primary and not t[_G_FL] & _ffi.TAG_SAM_PRI)
 
     # mappy aliases (lib.rs:196-284)
     ctg = property(lambda s: s.target_name)
@@ -184,7 +252,12 @@ def _batch_to_mappings(hp, n_reads, names, chain_only=False):
         n_cig = int(h.n_cigar)
         cig = np.ctypeslib.as_array(h.cigar, shape=(n_cig,)).copy() if n_cig > 0 and h.cigar else np.zeros(0, np.uint32)
         sbuf = C.string_at(h.str, int(h.n_str)) if h.n_str else b""
-        B = _HitBatch(cig, sbuf, names, chain_only)
+        has_tags = bool(h.tags)
+        if has_tags:    # the tags row of a hit goes behind its hit row
+            assert _TAG_DTYPE.itemsize == C.sizeof(_ffi.Tags)
+            trows = np.frombuffer(C.string_at(h.tags, nh * C.sizeof(_ffi.Tags)), dtype=_TAG_DTYPE).tolist()
+            rows = [r + t for r, t in zip(rows, trows)]
+        B = _HitBatch(cig, sbuf, names, chain_only, has_tags)
         view = Mapping._view
         ms = [view(B, r) for r in rows]
         out = [ms[off[i]:off[i + 1]] for i in range(n_reads)]
@@ -193,6 +266,47 @@ def _batch_to_mappings(hp, n_reads, names, chain_only=False):
     for i in empty:
         out[i] = RuntimeError("Sequence is empty")
     return out
+
+
+def _f4(x):
+    return "0" if x == 0.0 else "%.4f" % x
+
+
+def paf_line(m, name, qlen):
+    """one PAF line of the record `m` of the read `name` (length `qlen`): the twelve columns and the tags in the order of minimap2's PAF
+    writer (format.c::mm_write_paf + write_tags).  Needs a record mapped with Aligner(tags=True): ValueError otherwise.
+
+    name qlen qs qe +/- target tlen ts te mlen blen mapq, then with a CIGAR NM:i ms:i AS:i nn:i, then tp:A cm:i s1:i and, on primary records,
+    s2:i; de:f with a CIGAR, otherwise dv:f when the divergence was estimated ("0" when exactly zero, else %.4f); zd:i on split regions;
+    rl:i; with a CIGAR cg:Z, then cs:Z / MD:Z when the record has them.
+
+    The layout is written from knowledge of mm_write_paf: the minimap2 sources and binary are not part of this repository, so the line has
+    not been diffed against minimap2's own output.  The values behind it are checked against the oracle field by field."""
+    t = m._tags()
+    if t is None:
+        raise ValueError("paf_line needs a record mapped with Aligner(tags=True)")
+    has_cigar = m._has_cigar()
+    f = [name, qlen, m.query_start, m.query_end, "+" if m.strand > 0 else "-", m.target_name, m.target_len, m.target_start, m.target_end,
+         m.match_len, m.block_len, m.mapq]
+    if has_cigar:
+        f += ["NM:i:%d" % m.NM, "ms:i:%d" % t[_G_MS], "AS:i:%d" % t[_G_AS], "nn:i:%d" % t[_G_NN]]
+    f += ["tp:A:" + m.tp, "cm:i:%d" % t[_G_CM], "s1:i:%d" % t[_G_S1]]
+    if m.is_primary:
+        f.append("s2:i:%d" % t[_G_S2])
+    if has_cigar:
+        f.append("de:f:" + _f4(m.de))
+    elif 0.0 <= t[_G_DIV] <= 1.0:
+        f.append("dv:f:" + _f4(t[_G_DIV]))
+    if m.zd:
+        f.append("zd:i:%d" % m.zd)
+    f.append("rl:i:%d" % t[_G_RL])
+    if has_cigar:
+        f.append("cg:Z:" + m.cigar_str)
+        if m.cs is not None:
+            f.append("cs:Z:" + m.cs)
+        if m.MD is not None:
+            f.append("MD:Z:" + m.MD)
+    return "\t".join(str(x) for x in f)
 
 
 def shard_by_bases(lengths, n_shards):
@@ -341,7 +455,7 @@ class Aligner:
 
     def __init__(self, fn_idx_in=None, preset=None, k=None, w=None, min_cnt=None, min_chain_score=None,
                  min_dp_score=None, bw=None, best_n=None, n_threads=3, fn_idx_out=None, max_frag_len=None,
-                 extra_flags=None, seq=None, scoring=None, device=0, devices=None, *, cigar=True):
+                 extra_flags=None, seq=None, scoring=None, device=0, devices=None, *, cigar=True, tags=False):
         L = _ffi.lib()
         self._L = L
         self._idx = C.c_void_p()
@@ -354,6 +468,8 @@ class Aligner:
         self._device = self._devices[0]
         self._n_threads = 0
         self._lock = threading.Lock()
+        # tags=True: every mapping call asks for the mm355_tags_t rows (MM355_OUT_TAGS): the records carry minimap2's PAF tags (s1, dv, de, rl ...)
+        self._tag_flag = _ffi.OUT_TAGS if tags else 0
         io, mo = _ffi.IdxOpt(), _ffi.MapOpt()
         L.mm355_set_opt(None, C.byref(io), C.byref(mo))
         if preset is not None:
@@ -502,7 +618,7 @@ class Aligner:
                             else "argument 'seq' must be str")
         if (cs or MD) and not self._mo.flag & 4:
             raise ValueError("cs / MD need base-level alignment: this Aligner was created with cigar=False")
-        flags = (_ffi.OUT_CS if cs else 0) | (_ffi.OUT_MD if MD else 0)
+        flags = (_ffi.OUT_CS if cs else 0) | (_ffi.OUT_MD if MD else 0) | self._tag_flag
         r = self._map_many([seq], flags)[0]
         if isinstance(r, Exception):
             raise r
@@ -550,7 +666,7 @@ class Aligner:
         workers = st.threads
         self._names()                       # fill the name cache before the workers read it
         map_many, acquire, release = self._map_many, self._ctx_acquire, self._ctx_release
-        out_flags = _ffi.OUT_CS if self._mo.flag & 4 else 0        # chain-only: no cs string to produce
+        out_flags = (_ffi.OUT_CS if self._mo.flag & 4 else 0) | self._tag_flag        # chain-only: no cs string to produce
 
         # (the closures below capture `st`, never the iterator handed to the caller)
         def worker(slot):

@@ -15,7 +15,8 @@ LIB_PATH = os.environ.get("MM355_LIB_PATH") or os.path.join(os.path.dirname(_HER
 
 MM355_ENODEV, MM355_EINVAL, MM355_ENOMEM, MM355_EIO, MM355_ENOIDX, MM355_EEMPTY, MM355_EUNSUP, MM355_EHIP = \
     -1, -2, -3, -4, -5, -6, -7, -8
-OUT_CS, OUT_MD = 1, 2
+OUT_CS, OUT_MD, OUT_TAGS = 1, 2, 4
+TAG_INV, TAG_SAM_PRI, TAG_SPLIT_SHIFT = 1, 2, 2      # mm355_tags_t::flags
 
 
 class IdxOpt(C.Structure):
@@ -51,10 +52,16 @@ class Hit(C.Structure):
                 ("cnt", C.c_int32), ("n_sub", C.c_int32), ("subsc", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Tags(C.Structure):
+    _fields_ = [("score", C.c_int32), ("div", C.c_float), ("rep_len", C.c_int32), ("n_ambi", C.c_int32),
+                ("n_gap", C.c_int32), ("n_gapo", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_int32)]
+
+
 class Hits(C.Structure):
     _fields_ = [("n_reads", C.c_int64), ("hit_off", C.POINTER(C.c_int64)), ("status", C.POINTER(C.c_int32)),
                 ("hits", C.POINTER(Hit)), ("cigar", C.POINTER(C.c_uint32)), ("str", C.POINTER(C.c_char)),
-                ("n_hits", C.c_int64), ("n_cigar", C.c_int64), ("n_str", C.c_int64)]
+                ("n_hits", C.c_int64), ("n_cigar", C.c_int64), ("n_str", C.c_int64),
+                ("tags", C.POINTER(Tags))]      # parallel to hits; NULL unless OUT_TAGS was asked for
 
 
 class Stats(C.Structure):

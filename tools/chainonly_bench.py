@@ -4,6 +4,10 @@ other kernels of the chain-only call (ms_kernel, the rest), and a sample of read
 sub-batches of SUB reads, timed after a warm-up; the index is built on the device (as bench.py does).
 
     python tools/chainonly_bench.py --workload ecoli [--preset map-ont] [--reads 18432] [--sub 9216] [--n50 N --lo L --hi H] [--out F]
+                                    [--tags] [--reps R]
+
+--tags adds a third leg: chain-only with MM355_OUT_TAGS (the tags rows of every hit come back as well).  --reps R times every leg R times
+and reports each pass (the spread between passes is what a difference between two builds has to exceed); the rate is the median pass.
 
 ecoli: bench.py's configs[1] genome and read model; human: its configs[2] genome (make_human_like, seed 3, --scale 1) and read model.
 --n50 / --lo / --hi override the read lengths (e.g. 150 kb - 1 Mb reads)."""
@@ -37,6 +41,8 @@ def main():
     ap.add_argument("--hi", type=int, default=None)
     ap.add_argument("--check", type=int, default=200)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--tags", action="store_true")
+    ap.add_argument("--reps", type=int, default=1)
     args = ap.parse_args()
     import mappy_rs
     from mappy_rs import _ffi
@@ -73,16 +79,23 @@ def main():
         keep.append(k)
         _ffi.check(L.mm355_batch_select(ctx, j)); _ffi.check(L.mm355_batch_upload(ctx, len(sb), arr, rl))
     names_l = list(names)
-    for mode in ("cigar", "chain_only"):
+    for mode in ("cigar", "chain_only") + (("chain_only_tags",) if args.tags else ()):
         mo = _ffi.MapOpt.from_buffer_copy(mo0)
         if mode == "cigar":
             mo.flag |= 4
-        flags = _ffi.OUT_CS if mode == "cigar" else 0
+        flags = _ffi.OUT_CS if mode == "cigar" else _ffi.OUT_TAGS if mode == "chain_only_tags" else 0
         hp = C.POINTER(_ffi.Hits)()
         _ffi.check(L.mm355_batch_select(ctx, 0)); _ffi.check(L.mm355_map_resident(ctx, C.byref(mo), flags, C.byref(hp)))   # warm-up
         L.mm355_free_hits(hp)
-        ms, n_dev, n_host, k_regs, k_other, n_hits = [], 0, 0, 0.0, 0.0, 0
         st = _ffi.Stats()
+        rates = []
+        for _rep in range(max(1, args.reps) - 1):      # the earlier passes: rate only
+            t = time.perf_counter()
+            for j in range(len(subs)):
+                _ffi.check(L.mm355_batch_select(ctx, j)); _ffi.check(L.mm355_map_resident(ctx, C.byref(mo), flags, C.byref(hp)))
+                L.mm355_free_hits(hp)
+            rates.append(round(res["bases"] / (time.perf_counter() - t) / 1e6, 1))
+        ms, n_dev, n_host, k_regs, k_other, n_hits = [], 0, 0, 0.0, 0.0, 0
         for j, sb in enumerate(subs):
             _ffi.check(L.mm355_batch_select(ctx, j))
             t = time.perf_counter()
@@ -95,11 +108,14 @@ def main():
             L.mm355_get_stats(ctx, C.byref(st))
             n_dev += st.n_regs_dev; n_host += st.n_regs_host; k_regs += st.ms_kernel[23]; k_other += sum(st.ms_kernel[:23])
         tot_s = sum(ms) / 1e3
-        res[mode] = {"mbases_per_s": round(res["bases"] / tot_s / 1e6, 1), "ms_per_sub_batch": [round(x, 1) for x in ms], "n_hits": n_hits}
-        if mode == "chain_only":
+        rates.append(round(res["bases"] / tot_s / 1e6, 1))
+        res[mode] = {"mbases_per_s": sorted(rates)[len(rates) // 2], "ms_per_sub_batch": [round(x, 1) for x in ms], "n_hits": n_hits}
+        if len(rates) > 1:
+            res[mode]["mbases_per_s_passes"] = rates
+        if mode != "cigar":
             res[mode].update(n_regs_dev=n_dev, n_regs_host=n_host, ms_k_regs_per_sub_batch=round(k_regs / len(subs), 3),
                              ms_other_kernels_per_sub_batch=round(k_other / len(subs), 3))
-            if args.check:
+            if args.check and mode == "chain_only":
                 orc = O.OracleAligner(preset=args.preset, codes=g, names=names, n_threads=16)
                 orc.mo.flag &= ~4
                 bad = 0
