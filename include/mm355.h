@@ -156,6 +156,17 @@ int mm355_batch_upload(mm355_ctx_t *ctx, int64_t n_reads, const char *const *seq
 /* several resident batches per context: make batch `slot` (0..63) the current one; upload / map_resident act on the current batch */
 int mm355_batch_select(mm355_ctx_t *ctx, int slot);
 int mm355_map_resident(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int flags, mm355_hits_t **out);
+/* The same calls with query names (minimap2's mm_map(..., qname); mappy's map(seq, name=...)).  names[i] is NUL-terminated; names == NULL
+ * or names[i] == NULL: that read has no name and maps exactly as through the calls above.  A name does two things:
+ *   - it enters the read hash that orders regions of equal score (X31 of the name, unless MM_F_NO_HASH_NAME 0x400000000 is set);
+ *   - with MM_F_NO_DIAG (0x1) / MM_F_NO_DUAL (0x2), which the ava-ont / ava-pb presets set, seeds are filtered by the contig's name
+ *     (U:map.c::skip_seed): NO_DIAG drops the diagonal of a read against its own copy (equal name and equal length), NO_DUAL drops every
+ *     contig whose name sorts before the read's (strcmp order), so that an all-vs-all run reports each pair once.  On an index without
+ *     names (MM_I_NO_NAME) only the hash applies.
+ * A batch uploaded with names keeps them while it is resident: mm355_map_resident uses them. */
+int mm355_map_batch_named(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs,
+                          const int32_t *lens, const char *const *names, int flags, mm355_hits_t **out);
+int mm355_batch_upload_named(mm355_ctx_t *ctx, int64_t n_reads, const char *const *seqs, const int32_t *lens, const char *const *names);
 void mm355_free_hits(mm355_hits_t *hits);
 
 /* --- per-stage entry points (same kernels as mm355_map_batch; used by the parity tests and
@@ -215,6 +226,11 @@ int mm355_stage_sketch(mm355_ctx_t *ctx, int64_t n_reads, const char *const *seq
 int mm355_stage_anchors(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs,
                         const int32_t *lens, int sorted, int64_t *a_off, uint64_t *a, int64_t a_cap,
                         int32_t *rep_len, int32_t *n_mini_pos);
+/* the same with query names (see mm355_map_batch_named); anchors a named read generates against its own copy off the diagonal carry
+ * MM_SEED_SELF (bit 43 of y) */
+int mm355_stage_anchors_named(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs,
+                              const int32_t *lens, const char *const *names, int sorted, int64_t *a_off, uint64_t *a, int64_t a_cap,
+                              int32_t *rep_len, int32_t *n_mini_pos);
 /* chaining DP fill (mg_lchain_dp) on the sorted anchors: f, p, v per anchor (p as int32, -1 = none) */
 int mm355_stage_chain(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs,
                       const int32_t *lens, int64_t *a_off, uint64_t *a, int32_t *f, int32_t *p, int32_t *v, int64_t a_cap);

@@ -20,9 +20,12 @@ struct mm128 { uint64_t x, y; };
 #define MM355_SEED_LONG_JOIN (1ULL<<40)
 #define MM355_SEED_IGNORE    (1ULL<<41)
 #define MM355_SEED_TANDEM    (1ULL<<42)
+#define MM355_SEED_SELF      (1ULL<<43)   // U:minimap.h::MM_SEED_SELF: the anchor pairs a named read with itself, same strand, off the diagonal
 #define MM355_SEED_SEG_SHIFT 48
 
 // flags the path tests (U:minimap.h)
+#define MMF_NO_DIAG      0x001LL
+#define MMF_NO_DUAL      0x002LL
 #define MMF_CIGAR        0x004LL
 #define MMF_SPLICE       0x080LL
 #define MMF_NO_LJOIN     0x400LL
@@ -37,6 +40,8 @@ struct mm128 { uint64_t x, y; };
 #define MMF_RMQ          0x80000000LL
 #define MMF_QSTRAND      0x100000000LL
 #define MMF_NO_INV       0x200000000LL
+#define MMF_NO_HASH_NAME 0x400000000LL
+#define MMI_NO_NAME      4            // U:minimap.h::MM_I_NO_NAME (index flag)
 
 // ---- base encoding (U:sketch.c::seq_nt4_table): A/a 0, C/c 1, G/g 2, T/t/U/u 3, else 4 ----
 MM_HD int mm_nt4(uint8_t c)

@@ -1,6 +1,7 @@
 // mm355_dev.h -- device-side structs and kernel launch prototypes (host <-> .hip boundary inside the library)
 #pragma once
 #include "mm355_core.h"
+#include "mm355_names.h"
 
 struct DevIndex {
 	const mm355_slot *slots;   // n_lines * 8 slots, 128-B lines
@@ -69,6 +70,13 @@ struct DevSeeds {
 	unsigned long long *counters; // [8]: n_hit, n_a_multi, probes, chain_pairs ...
 };
 
+// The query-name rules of U:map.c::skip_seed for a batch with named reads (mm355_names.h); only the named entry points of the two seed
+// kernels take it -- the unnamed kernels keep their arguments.
+struct DevNames {
+	const uint64_t *key;       // [n_reads] lb | eq << 32 | named << 33; 0 = unnamed read
+	const uint32_t *name_rank; // [n_seq] rank of the contig's name among the distinct contig names
+};
+
 struct DevAnchors {
 	const int64_t *aoff;       // [n_reads+1] anchor offsets
 	mm128 *a;                  // anchors (generation order, then sorted in place)
@@ -98,8 +106,9 @@ void mm355_launch_sketch(const DevIndex &ix, const DevBatch &bt, DevSeeds &sd, c
 void mm355_launch_mzflt(const DevParams &pr, const DevBatch &bt, DevSeeds &sd, hipStream_t st, void *kt = 0);
 void mm355_launch_seed_lookup(const DevIndex &ix, const DevBatch &bt, DevSeeds &sd, const int32_t *chunk_read, const int32_t *chunk_start, int n_chunks,
                               unsigned long long *hit_ctr, unsigned int *tile_ctr, hipStream_t st, void *kt = 0);
-void mm355_launch_seed_select(const DevIndex &ix, const DevParams &pr, const DevBatch &bt, DevSeeds &sd, hipStream_t st, void *kt = 0);
-void mm355_launch_seed_expand(const DevIndex &ix, const DevParams &pr, const DevBatch &bt, DevSeeds &sd, DevAnchors &an, hipStream_t st, void *kt = 0);
+// nm != 0: the named entry points (k_seed_select_named / k_seed_expand_named)
+void mm355_launch_seed_select(const DevIndex &ix, const DevParams &pr, const DevBatch &bt, DevSeeds &sd, hipStream_t st, void *kt = 0, const DevNames *nm = 0);
+void mm355_launch_seed_expand(const DevIndex &ix, const DevParams &pr, const DevBatch &bt, DevSeeds &sd, DevAnchors &an, hipStream_t st, void *kt = 0, const DevNames *nm = 0);
 struct SortTask { int32_t read; uint32_t beg, end; int32_t s; };   // a bucket [beg, end) of one read's array, to be sorted from byte shift s
 int mm355_launch_sort(const DevBatch &bt, DevAnchors &an, int *err, const void *h_tasks, int n_big, int n_med, int n_small, size_t n_elems, void *task_buf, size_t task_cap, hipStream_t st, void *kt = 0, int n_levels = 0);
 int mm355_sort_heavy_threshold(void);

@@ -16,6 +16,7 @@
 #include "mm355_glue.h"
 #include "mm355_prof.h"
 #include "mm355_regs.h"
+#include "mm355_selfclamp.h"
 #include <atomic>
 #include <chrono>
 #include <string.h>
@@ -813,7 +814,7 @@ void mm355_glue_chain_rmq(const mm355_index *mi, const mm355_mapopt_t *opt, Read
 void mm355_glue_regions(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, int rmq_state)
 {
 	const int qlen = rs.qlen;
-	uint32_t hash = 0;   // qname is NULL through the reference (the L2 crate passes null)
+	uint32_t hash = rs.name_hash;   // X31(qname); 0 without a name (the L2 crate passes null)
 	hash ^= wang32((uint32_t)qlen) + wang32((uint32_t)opt->seed);
 	hash = wang32(hash);
 	const float pen_gap = (float)(opt->chain_gap_scale * 0.01 * mi->k), pen_skip = (float)(opt->chain_skip_scale * 0.01 * mi->k);
@@ -1406,6 +1407,7 @@ static void task_prepare(const mm355_index *mi, const mm355_mapopt_t *opt, ReadS
 		re1 = re1 < re_ + l? re1 : re_ + l;
 		re0 = re0 > re1? re0 : re1;
 	} else re0 = re_, qe0 = qe_;
+	if (a[r->as].y & MM355_SEED_SELF) mm355_self_clamp(r->rs, r->qs, r->re, r->qe, &rs0, &qs0, &re0, &qe0);
 	T.rs = rs_, T.qs = qs_, T.re = re_, T.qe = qe_;
 	T.rs0 = rs0, T.qs0 = qs0, T.re0 = re0, T.qe0 = qe0;
 	T.res.clear(); T.res.reserve(40);

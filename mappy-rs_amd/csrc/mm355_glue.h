@@ -73,6 +73,7 @@ struct ReadState {
 	std::vector<uint64_t> u;
 	std::vector<uint64_t> mini_pos;
 	int32_t rep_len = 0, n_a = 0;
+	uint32_t name_hash = 0;            // X31 of the query name as mm_map_frag hashes it (0: unnamed read, or MM_F_NO_HASH_NAME)
 	std::vector<Reg> regs;
 	std::vector<AlnTask> tasks;
 	int cursor = 0;                    // U:align.c::mm_align_skeleton loop index

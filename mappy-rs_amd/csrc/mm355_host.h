@@ -7,10 +7,11 @@
 #include <mutex>
 #include "../../include/mm355.h"
 #include "mm355_core.h"
+#include "mm355_names.h"
 
 // HBM copy of the index on one device (flat table, pos[], the reference packed to 2 bits per base + its sorted N-run intervals, contig
 // offsets/lengths).  Every context of that device shares it.  S (the .mmi's 4-bit image) only exists while the replica is being made.
-struct mm355_replica { int dev = -1; void *slots = 0, *pos = 0, *S = 0, *seq_off = 0, *seq_len = 0, *S2 = 0, *nr = 0; uint32_t n_nr = 0; };
+struct mm355_replica { int dev = -1; void *slots = 0, *pos = 0, *S = 0, *seq_off = 0, *seq_len = 0, *S2 = 0, *nr = 0, *name_rank = 0; uint32_t n_nr = 0; };
 
 struct mm355_index {
 	int32_t b, w, k, flag;
@@ -24,6 +25,9 @@ struct mm355_index {
 	std::vector<uint64_t> pos;          // positions of multi-occurrence minimizers
 	int64_t n_minimizers, n_distinct;
 	std::unordered_map<std::string, int> name2id;
+	// query-name rules (mm355_names.h): the distinct contig names in strcmp order and the rank of every contig's name in that list
+	std::vector<std::string> names_sorted;
+	std::vector<uint32_t> name_rank;
 	// device-built index (mm355_index_build_device): table and positions live only in HBM of device `dev_id`
 	bool dev_resident = false; int dev_id = -1;
 	void *d_slots = 0, *d_pos = 0, *d_S = 0; uint64_t n_pos = 0;

@@ -146,6 +146,7 @@ extern "C" int mm355_index_build_device(const mm355_idxopt_t *io, int n_seq, con
 		sum_len += lens[i]; max_len = std::max(max_len, lens[i]);
 	}
 	for (uint32_t i = 0; i < mi->n_seq; ++i) mi->name2id.emplace(mi->names[i], (int)i);
+	mm355_name_ranks(mi->names, mi->names_sorted, mi->name_rank);
 	const uint64_t cap = (uint64_t)((double)sum_len * 2.0 / (mi->w + 1) * 1.25) + (1u << 20);
 	const int64_t max_chunks = (max_len + SK_CHUNK - 1) / SK_CHUNK;
 	DBuf d_seq, d_slots16, d_cn, d_co, d_keys, d_vals, d_keys2, d_vals2, d_tmp, d_err;
@@ -267,16 +268,22 @@ extern "C" int mm355_index_build_device(const mm355_idxopt_t *io, int n_seq, con
 	mi->dev_resident = true; mi->dev_id = device;
 	{   // the build device holds the first replica; other devices get peer copies (mm355_upload / mm355_ctx_create)
 		mm355_replica rp; rp.dev = device; rp.slots = mi->d_slots; rp.pos = mi->d_pos; rp.S = mi->d_S;
-		if (hipMalloc(&rp.seq_off, (size_t)n_seq * 8) != hipSuccess || hipMalloc(&rp.seq_len, (size_t)n_seq * 4) != hipSuccess) { if (rp.seq_off) (void)hipFree(rp.seq_off); mi->dev_resident = false; FAIL(MM355_ENOMEM); }
+		if (hipMalloc(&rp.seq_off, (size_t)n_seq * 8) != hipSuccess || hipMalloc(&rp.seq_len, (size_t)n_seq * 4) != hipSuccess ||
+		    hipMalloc(&rp.name_rank, (size_t)n_seq * 4) != hipSuccess) {
+			if (rp.seq_off) (void)hipFree(rp.seq_off); if (rp.seq_len) (void)hipFree(rp.seq_len); mi->dev_resident = false; FAIL(MM355_ENOMEM);
+		}
 		(void)hipMemcpy(rp.seq_off, mi->seq_off.data(), (size_t)n_seq * 8, hipMemcpyHostToDevice);
 		(void)hipMemcpy(rp.seq_len, mi->seq_len.data(), (size_t)n_seq * 4, hipMemcpyHostToDevice);
+		if (mi->name_rank.size() != (size_t)n_seq || hipMemcpy(rp.name_rank, mi->name_rank.data(), (size_t)n_seq * 4, hipMemcpyHostToDevice) != hipSuccess) {
+			(void)hipFree(rp.seq_off); (void)hipFree(rp.seq_len); (void)hipFree(rp.name_rank); mi->dev_resident = false; FAIL(MM355_EHIP);
+		}
 		{   // 2-bit image + N-run table for the kernels; the 4-bit image leaves HBM (the host keeps it for mm_idx_getseq and the .mmi)
 			std::lock_guard<std::mutex> lk(mi->rep_mu);
 			rc = mm355_replica_pack2(mi, &rp);
 			mi->d_S = rp.S;
 		}
 		if (rc) {   // (the table buffers still belong to the build: free_build_buffers releases them, the replica only its own pieces)
-			(void)hipFree(rp.seq_off); (void)hipFree(rp.seq_len); if (rp.S2) (void)hipFree(rp.S2); if (rp.nr) (void)hipFree(rp.nr);
+			(void)hipFree(rp.seq_off); (void)hipFree(rp.seq_len); (void)hipFree(rp.name_rank); if (rp.S2) (void)hipFree(rp.S2); if (rp.nr) (void)hipFree(rp.nr);
 			mi->dev_resident = false; goto done;
 		}
 		mi->replicas.push_back(rp);

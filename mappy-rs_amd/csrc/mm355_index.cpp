@@ -323,6 +323,7 @@ static mm355_index *build_from_fastx(const char *path, const mm355_idxopt_t *io,
 static void finish_index(mm355_index *mi)
 {
 	for (uint32_t i = 0; i < mi->n_seq; ++i) mi->name2id.emplace(mi->names[i], (int)i);   // first wins, as a hash put would report a duplicate
+	mm355_name_ranks(mi->names, mi->names_sorted, mi->name_rank);
 }
 
 extern "C" int mm355_index_load(const char *path, const mm355_idxopt_t *io, int n_threads, mm355_index_t **out)

@@ -344,10 +344,28 @@ __device__ inline void heapdown_u64(uint32_t i, uint32_t n, uint64_t *l)
 	l[i] = tmp;
 }
 
-// U:map.c::skip_seed (qname is NULL through the reference, so only the strand filters remain): 1 = the hit becomes an anchor
+// U:map.c::skip_seed, strand part (all there is for a read without a name): 1 = the hit becomes an anchor
 __device__ __forceinline__ uint32_t mm355_keep_strand(int64_t flag, bool forward)
 {
 	return forward? !(flag & MMF_REV_ONLY) : !(flag & MMF_FOR_ONLY);
+}
+// U:map.c::skip_seed, whole, for occurrence rk of a seed at q_pos (pos << 1 | strand) of a read with name word `key` (mm355_names.h; 0 =
+// unnamed).  The name branch comes first, as in the reference: against the read's own copy in the index (equal name and equal length)
+// MM_F_NO_DIAG drops the diagonal on either strand and marks what is left of the same strand (self -> MM_SEED_SELF); MM_F_NO_DUAL drops
+// every contig whose name sorts before the read's.  Integer only: strcmp(qname, contig) > 0 <=> rank < lb, == 0 <=> eq && rank == lb.
+__device__ __forceinline__ bool mm355_keep_named(int64_t flag, uint64_t key, const uint32_t *name_rank, const uint32_t *seq_len, int32_t qlen,
+                                                 uint64_t rk, uint32_t q_pos, bool &self)
+{
+	self = false;
+	if (key & MM355_NAME_NAMED) {
+		const uint32_t rid = (uint32_t)(rk >> 32), rank = name_rank[rid], lb = (uint32_t)key;
+		if ((flag & MMF_NO_DIAG) && (key & MM355_NAME_EQ) && rank == lb && seq_len[rid] == (uint32_t)qlen) {
+			if ((uint32_t)rk >> 1 == q_pos >> 1) return false;
+			if ((rk & 1) == (q_pos & 1)) self = true;
+		}
+		if ((flag & MMF_NO_DUAL) && rank < lb) return false;
+	}
+	return mm355_keep_strand(flag, (rk & 1) == (q_pos & 1)) != 0;
 }
 
 // One wave per read; nothing is done lane by lane except the heap of U:seed.c::mm_seed_select on streaks that are LONGER than the
@@ -363,7 +381,10 @@ __device__ __forceinline__ uint32_t mm355_keep_strand(int64_t flag, bool forward
 // The dense arrays alias the outputs (soff <- counts, mini_pos <- query words, hl <- minimizer index): a tile is read completely before
 // its (never more numerous) kept entries are written at or below its own range.
 #define SEL_MASK_TILES 1024          // tiles of 64 hits whose mask is kept in LDS (reads up to ~0.6 Mb); later tiles are recomputed on the fly
-__global__ __launch_bounds__(WAVE) void k_seed_select(DevIndex ix, DevParams pr, DevBatch bt, DevSeeds sd)
+// NAMED: the batch has named reads and MM_F_NO_DIAG / MM_F_NO_DUAL is set -- part 3 counts the occurrences skip_seed admits, one lane per
+// kept seed walking its occurrence list once (the count is all k_seed_expand_named needs: it compacts the admitted occurrences itself).
+template <bool NAMED>
+__device__ __forceinline__ void seed_select_read(const DevIndex &ix, const DevParams &pr, const DevBatch &bt, const DevSeeds &sd, const DevNames &nm)
 {
 	MM355_LATENCY_KERNEL();
 	__shared__ uint64_t heap[128];
@@ -459,6 +480,7 @@ __global__ __launch_bounds__(WAVE) void k_seed_select(DevIndex ix, DevParams pr,
 	KPROF(5);
 	// 3. mm_collect_matches tail
 	const bool strand_flt = (pr.flag & (MMF_FOR_ONLY | MMF_REV_ONLY)) != 0;
+	const uint64_t nkey = NAMED? nm.key[r] : 0;
 	int n_kept = 0;
 	uint32_t n_a = 0;
 	unsigned long long multi = 0;
@@ -487,7 +509,14 @@ __global__ __launch_bounds__(WAVE) void k_seed_select(DevIndex ix, DevParams pr,
 		// kept seeds
 		const bool keep = in && !flt;
 		uint32_t c_eff = keep? c : 0;
-		if (keep && strand_flt) {                  // U:map.c::skip_seed: hits of the excluded strand produce no anchor
+		if (NAMED && keep && (strand_flt || nkey)) {
+			const uint64_t v = sd.sv[off + j];
+			c_eff = 0;
+			for (uint32_t kq = 0; kq < c; ++kq) {
+				bool self;
+				c_eff += mm355_keep_named(pr.flag, nkey, nm.name_rank, ix.seq_len, qlen, c == 1? v : ix.pos[v + kq], q_pos, self);
+			}
+		} else if (!NAMED && keep && strand_flt) { // U:map.c::skip_seed: hits of the excluded strand produce no anchor
 			const uint64_t v = sd.sv[off + j];
 			c_eff = 0;
 			for (uint32_t kq = 0; kq < c; ++kq) {
@@ -514,6 +543,14 @@ __global__ __launch_bounds__(WAVE) void k_seed_select(DevIndex ix, DevParams pr,
 		if (multi) atomicAdd(&sd.counters[1], multi);
 	}
 	KPROF(6);
+}
+__global__ __launch_bounds__(WAVE) void k_seed_select(DevIndex ix, DevParams pr, DevBatch bt, DevSeeds sd)
+{
+	seed_select_read<false>(ix, pr, bt, sd, DevNames());
+}
+__global__ __launch_bounds__(WAVE) void k_seed_select_named(DevIndex ix, DevParams pr, DevBatch bt, DevSeeds sd, DevNames nm)
+{
+	seed_select_read<true>(ix, pr, bt, sd, nm);
 }
 
 // ------------------------------------------------------------------ a5: collect_seed_hits (anchor expansion)
@@ -574,6 +611,72 @@ __global__ __launch_bounds__(256) void k_seed_expand(DevIndex ix, DevParams pr, 
 			}
 			if (yw >> 63) o.y |= MM355_SEED_TANDEM;
 			a[t] = o;
+		}
+	}
+}
+
+// The named form (k_seed_select_named counted the admitted occurrences of every kept seed into soff).  A group of EXN_G lanes per kept seed
+// walks the seed's RAW occurrence list once, EXN_G entries at a time, tests each with skip_seed and writes the admitted ones behind one
+// another from the seed's offset (ballot compaction inside the group): generation order, linear work per seed.  The strand-filter form
+// above, where every anchor rescans its seed's list, is quadratic in the occurrence count -- here that count is the read coverage of an
+// all-vs-all set and the filter is on for every read.
+#define EXN_G 16
+__global__ __launch_bounds__(256) void k_seed_expand_named(DevIndex ix, DevParams pr, DevBatch bt, DevSeeds sd, DevAnchors an, DevNames nm)
+{
+	const int r = blockIdx.x;
+	const int na = sd.n_a[r], nk = sd.n_mini[r], nmz = sd.n_mz[r], qlen = bt.rlen[r];
+	if (na == 0) return;
+	const int64_t off = bt.roff[r];
+	const mm128 *mz = sd.mz + off;
+	const int32_t *hl = sd.hl + off;
+	const uint32_t *soff = sd.soff + off;
+	mm128 *a = an.a + an.aoff[r];
+	const uint64_t nkey = nm.key[r];
+	const int gl = threadIdx.x & (EXN_G - 1), gsh = (threadIdx.x & 63) & ~(EXN_G - 1);
+	const unsigned long long gmask = (1ULL << EXN_G) - 1;
+	const int n_grp = 256 / EXN_G;
+	// (every lane of a wave runs the same number of outer and inner iterations: the ballots below are reached by whole waves)
+	for (int k0 = 0; k0 < nk; k0 += n_grp) {
+		const int k = k0 + (int)(threadIdx.x / EXN_G);
+		const bool live = k < nk;
+		uint32_t c = 0, o0 = 0, o1 = 0; uint64_t v = 0, yw = 0; bool tandem = false;
+		if (live) {
+			const int j = hl[k];
+			const mm128 m = mz[j];
+			tandem = (j > 0 && (mz[j-1].x >> 8) == (m.x >> 8)) || (j < nmz - 1 && (mz[j+1].x >> 8) == (m.x >> 8));
+			c = sd.sn[off + j]; v = sd.sv[off + j]; yw = (m.x & 0xff) << 32 | (uint32_t)m.y;
+			o0 = soff[k]; o1 = k + 1 < nk? soff[k + 1] : (uint32_t)na;
+		}
+		const uint32_t q_pos = (uint32_t)yw, q_span = (uint32_t)(yw >> 32) & 0xff;
+		uint32_t cmax = c;                            // the longest list among the wave's four seeds
+		for (int o2 = 32; o2 >= EXN_G; o2 >>= 1) { const uint32_t x = (uint32_t)__shfl_xor((int)cmax, o2); cmax = x > cmax? x : cmax; }
+		uint32_t w = o0;                              // next free anchor slot of the seed
+		for (uint32_t kk0 = 0; kk0 < cmax; kk0 += EXN_G) {
+			const uint32_t kk = kk0 + (uint32_t)gl;
+			bool keep = false, self = false; uint64_t rk = 0;
+			if (live && kk < c) {
+				rk = c == 1? v : ix.pos[v + kk];
+				keep = mm355_keep_named(pr.flag, nkey, nm.name_rank, ix.seq_len, qlen, rk, q_pos, self);
+			}
+			const unsigned long long gm = __ballot(keep) >> gsh & gmask;
+			if (keep) {
+				const uint32_t t = w + (uint32_t)__popcll(gm & ((1ULL << gl) - 1));
+				if (t < o1) {                             // (always: k_seed_select_named counted with the same test)
+					const uint32_t rpos = (uint32_t)rk >> 1;
+					mm128 o;
+					if ((rk & 1) == (q_pos & 1)) {   // forward strand
+						o.x = (rk & 0xffffffff00000000ULL) | rpos;
+						o.y = (uint64_t)q_span << 32 | q_pos >> 1;
+					} else {                          // reverse strand
+						o.x = 1ULL << 63 | (rk & 0xffffffff00000000ULL) | rpos;
+						o.y = (uint64_t)q_span << 32 | (uint32_t)(qlen - (int)((q_pos >> 1) + 1 - q_span) - 1);
+					}
+					if (tandem) o.y |= MM355_SEED_TANDEM;
+					if (self) o.y |= MM355_SEED_SELF;
+					a[t] = o;
+				}
+			}
+			w += (uint32_t)__popcll(gm);
 		}
 	}
 }
@@ -1258,17 +1361,19 @@ void mm355_launch_seed_lookup(const DevIndex &ix, const DevBatch &bt, DevSeeds &
 	const int grid = n_chunks < lk_grid? n_chunks : lk_grid;   // resident blocks walk the live tiles
 	hipLaunchKernelGGL(k_seed_lookup, dim3(grid), dim3(256), 0, st, ix, bt, sd, (const int4*)tiles, (const unsigned int*)tile_ctr, hit_ctr);
 }
-void mm355_launch_seed_select(const DevIndex &ix, const DevParams &pr, const DevBatch &bt, DevSeeds &sd, hipStream_t st, void *kt)
+void mm355_launch_seed_select(const DevIndex &ix, const DevParams &pr, const DevBatch &bt, DevSeeds &sd, hipStream_t st, void *kt, const DevNames *nm)
 {
 	if (bt.n_reads == 0) return;
 	KtScope ks(kt, KT_SELECT, st);
-	hipLaunchKernelGGL(k_seed_select, dim3(bt.n_reads), dim3(WAVE), 0, st, ix, pr, bt, sd);
+	if (nm) hipLaunchKernelGGL(k_seed_select_named, dim3(bt.n_reads), dim3(WAVE), 0, st, ix, pr, bt, sd, *nm);
+	else hipLaunchKernelGGL(k_seed_select, dim3(bt.n_reads), dim3(WAVE), 0, st, ix, pr, bt, sd);
 }
-void mm355_launch_seed_expand(const DevIndex &ix, const DevParams &pr, const DevBatch &bt, DevSeeds &sd, DevAnchors &an, hipStream_t st, void *kt)
+void mm355_launch_seed_expand(const DevIndex &ix, const DevParams &pr, const DevBatch &bt, DevSeeds &sd, DevAnchors &an, hipStream_t st, void *kt, const DevNames *nm)
 {
 	if (bt.n_reads == 0) return;
 	KtScope ks(kt, KT_EXPAND, st);
-	hipLaunchKernelGGL(k_seed_expand, dim3(bt.n_reads), dim3(256), 0, st, ix, pr, bt, sd, an);
+	if (nm) hipLaunchKernelGGL(k_seed_expand_named, dim3(bt.n_reads), dim3(256), 0, st, ix, pr, bt, sd, an, *nm);
+	else hipLaunchKernelGGL(k_seed_expand, dim3(bt.n_reads), dim3(256), 0, st, ix, pr, bt, sd, an);
 }
 // Literal radix_sort_128x of the listed reads.  h_tasks: the initial whole-read tasks (byte 56) grouped by size class -- n_big entries
 // (> MW_BIG anchors: 1024-thread levels), then n_med (> MW_MED: 256-thread levels), then n_small (one wave each) -- in pinned or otherwise

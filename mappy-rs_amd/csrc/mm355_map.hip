@@ -296,19 +296,33 @@ static const bool g_parallel_hook_set = [] { mm355_parallel_hook = [](int64_t n,
 
 extern "C" int mm355_batch_upload(mm355_ctx_t *c, int64_t n_reads, const char *const *seqs, const int32_t *lens)
 {
+	return mm355_batch_upload_named(c, n_reads, seqs, lens, 0);
+}
+
+// names[i]: the query name of read i (NUL-terminated), or null; the batch keeps them (hashes and rank words, not the strings) while it is resident
+extern "C" int mm355_batch_upload_named(mm355_ctx_t *c, int64_t n_reads, const char *const *seqs, const int32_t *lens, const char *const *names)
+{
 	if (c == 0 || n_reads < 0) return MM355_EINVAL;
 	std::vector<int32_t> dl(lens, lens + n_reads);
 	c->hb.status.assign(n_reads, 0);
 	for (int64_t i = 0; i < n_reads; ++i)
 		if (lens[i] <= 0) { c->hb.status[i] = MM355_EEMPTY; dl[i] = 0; }   // "Sequence is empty" (L2 crate)
-	return mm355_run_pack(c, n_reads, seqs, dl.data());
+	const int rc = mm355_run_pack(c, n_reads, seqs, dl.data());
+	if (rc == 0) mm355_set_names(c, n_reads, names);
+	return rc;
 }
 
 extern "C" int mm355_map_batch(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens, int flags, mm355_hits_t **out)
 {
+	return mm355_map_batch_named(c, mo, n_reads, seqs, lens, 0, flags, out);
+}
+
+extern "C" int mm355_map_batch_named(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
+                                     const char *const *names, int flags, mm355_hits_t **out)
+{
 	*out = 0;
 	if (mo && !(mo->flag & MMF_CIGAR) && (flags & (MM355_OUT_CS | MM355_OUT_MD))) return MM355_EINVAL;   // cs / MD need the base-level alignment
-	int rc = mm355_batch_upload(c, n_reads, seqs, lens);
+	int rc = mm355_batch_upload_named(c, n_reads, seqs, lens, names);
 	if (rc) return rc;
 	return mm355_map_resident(c, mo, flags, out);
 }
@@ -420,7 +434,7 @@ extern "C" int mm355_map_resident(mm355_ctx_t *c, const mm355_mapopt_t *mo, int 
 	struct RegGuard { std::vector<ReadState> &v; ~RegGuard() { for (ReadState &r : v) mm355_glue_release(r); } } reg_guard{rs};   // every return below frees the regions' Extra records
 	parallel_for(n_reads, nt, [&](int64_t i, int) {
 		ReadState &r = rs[i];
-		r.qlen = dl[i]; r.seq = seqs[i]; r.rep_len = hb.rep_len[i]; r.defer_extra = defer_extra;
+		r.qlen = dl[i]; r.seq = seqs[i]; r.rep_len = hb.rep_len[i]; r.defer_extra = defer_extra; r.name_hash = mm355_read_name_hash(hb, mo->flag, i);
 		{ ProfScope pf(PF_PRE_COPY);
 		r.u.assign(pu + uo[i], pu + uo[i + 1]);
 		r.a.assign(pa + vo[i], pa + vo[i + 1]);

@@ -45,6 +45,9 @@ struct HostBatch {            // packed reads of one sub-batch
 	std::vector<uint8_t> rmq_state;   // per read after mm355_run_rmq: MM355_RMQ_KEEP / _DONE / _HOST (empty: the stage did not run, the host decides)
 	std::vector<int64_t> aoff;
 	int64_t tot_a = 0;
+	// query names (mm355_set_names; both empty when no read of the batch has one): X31 of the name and the word of the named seed kernels
+	// (mm355_names.h; 0 = an unnamed read)
+	std::vector<uint32_t> name_x31; std::vector<uint64_t> name_key;
 };
 
 // a batch of reads resident in HBM that is not the context's current one (mm355_batch_select): the packed reads, their tables and
@@ -78,8 +81,10 @@ struct mm355_ctx {
 	int dev = 0;
 	hipStream_t st = 0;
 	DevIndex dix;
+	const uint32_t *d_name_rank = 0;       // the replica's name_rank[] (named seed kernels)
 	// per-batch device buffers
 	DBuf heavy, seq, roff, rlen, order, ck_read, ck_start, ck_n, ck_r0;
+	DBuf name_key;                         // HostBatch::name_key of the current call (uploaded only when the named seed kernels run)
 	int64_t n_chunks = 0;
 	int prio_low = 0, prio_high = 0; bool use_prio = false; int ord = 0;   // ord: creation ordinal of the context
 	DBuf sort_flag, tie_list, n_keep, aoff2, cs_list, tie_a, tie_b, tie_f, tie_p, tie_t8, tie_tcnt; HBuf h_cs;   // cull + sort of anchor-rich batches (mm355_cullsort.hip)
@@ -121,6 +126,12 @@ int mm355_check_opts(const mm355_mapopt_t *mo, const mm355_index *mi);
 extern "C" int mm355_map_resident(mm355_ctx_t *c, const mm355_mapopt_t *mo, int flags, mm355_hits_t **out);
 extern void (*mm355_parallel_hook)(int64_t n, const std::function<void(int64_t)> &f);   // the host pool's parallel loop (mm355_map.hip), or null
 int mm355_run_pack(mm355_ctx *ctx, int64_t n_reads, const char *const *seqs, const int32_t *lens);
+// the query names of the batch mm355_run_pack has just packed (names == 0 or names[i] == 0: unnamed); they stay with the batch
+void mm355_set_names(mm355_ctx *ctx, int64_t n_reads, const char *const *names);
+// U:map.c::mm_map_frag: X31(qname) unless the read is unnamed or MM_F_NO_HASH_NAME is set
+inline uint32_t mm355_read_name_hash(const HostBatch &hb, int64_t flag, int64_t i) { return hb.name_x31.empty() || (flag & MMF_NO_HASH_NAME)? 0u : hb.name_x31[i]; }
+// the named seed kernels run when a read has a name, skip_seed's name branch is switched on and the index kept its contig names
+inline bool mm355_name_filter_on(const mm355_ctx *c, const DevParams &pr) { return mm355_name_filter_applies(!c->hb.name_key.empty(), pr.flag, c->mi->flag); }
 int mm355_run_sketch(mm355_ctx *ctx);
 int mm355_run_seeds(mm355_ctx *ctx, const DevParams &pr);                  // mz_flt + lookup + select (+ D2H counts, anchor offsets)
 int mm355_run_expand(mm355_ctx *ctx, const DevParams &pr);

@@ -212,6 +212,7 @@ extern "C" int mm355_ctx_create(const mm355_index_t *mi, int device_id, mm355_ct
 	c->dix.pos = (const uint64_t*)rp.pos; c->dix.S2 = (const uint32_t*)rp.S2; c->dix.nr = (const uint64_t*)rp.nr; c->dix.n_nr = rp.n_nr;
 	c->dix.seq_off = (const uint64_t*)rp.seq_off; c->dix.seq_len = (const uint32_t*)rp.seq_len;
 	c->dix.k = mi->k; c->dix.w = mi->w; c->dix.b = mi->b; c->dix.flag = mi->flag; c->dix.n_seq = mi->n_seq;
+	c->d_name_rank = (const uint32_t*)rp.name_rank;
 	if (c->counters.ensure(CTR_BYTES) || c->err.ensure(16)) { mm355_ctx_destroy(c); return MM355_ENOMEM; }
 	if (getenv("MM355_KPROF")) { if (c->kprof.ensure(512)) { mm355_ctx_destroy(c); return MM355_ENOMEM; } HIPCHK(hipMemset(c->kprof.p, 0, 512)); }
 	c->n_tpend = 0; memset(&c->stats, 0, sizeof(c->stats));
@@ -295,9 +296,10 @@ int mm355_index_replica(const mm355_index *mi, int dev, mm355_replica *out)
 	uint64_t sum_len = mi->n_seq? mi->seq_off[mi->n_seq - 1] + mi->seq_len[mi->n_seq - 1] : 0;
 	const size_t Sw = (sum_len + 7) / 8 + 2, Sb = Sw * 4;
 	auto fail = [&](int code) { if (rp.slots) (void)hipFree(rp.slots); if (rp.pos) (void)hipFree(rp.pos); if (rp.S) (void)hipFree(rp.S); if (rp.S2) (void)hipFree(rp.S2); if (rp.nr) (void)hipFree(rp.nr);
-	                            if (rp.seq_off) (void)hipFree(rp.seq_off); if (rp.seq_len) (void)hipFree(rp.seq_len); (void)hipSetDevice(prev); return code; };
+	                            if (rp.seq_off) (void)hipFree(rp.seq_off); if (rp.seq_len) (void)hipFree(rp.seq_len); if (rp.name_rank) (void)hipFree(rp.name_rank); (void)hipSetDevice(prev); return code; };
 	if (hipMalloc(&rp.slots, sb) != hipSuccess || hipMalloc(&rp.pos, pb) != hipSuccess || hipMalloc(&rp.S, Sb + 16) != hipSuccess ||
-	    hipMalloc(&rp.seq_off, (size_t)mi->n_seq * 8 + 8) != hipSuccess || hipMalloc(&rp.seq_len, (size_t)mi->n_seq * 4 + 8) != hipSuccess) return fail(MM355_ENOMEM);
+	    hipMalloc(&rp.seq_off, (size_t)mi->n_seq * 8 + 8) != hipSuccess || hipMalloc(&rp.seq_len, (size_t)mi->n_seq * 4 + 8) != hipSuccess ||
+	    hipMalloc(&rp.name_rank, (size_t)mi->n_seq * 4 + 8) != hipSuccess) return fail(MM355_ENOMEM);
 	if (hipMemset(rp.S, 0, Sb + 16) != hipSuccess) return fail(MM355_EHIP);
 	if (mi->dev_resident) {   // table and pos[] exist only in HBM of the build device: device-to-device over xGMI (or through the host if peers are not connected)
 		const mm355_replica *src = 0;
@@ -312,6 +314,8 @@ int mm355_index_replica(const mm355_index *mi, int dev, mm355_replica *out)
 	if (!mi->S.empty() && hipMemcpy(rp.S, mi->S.data(), std::min(Sb, mi->S.size() * 4), hipMemcpyHostToDevice) != hipSuccess) return fail(MM355_EHIP);
 	if (hipMemcpy(rp.seq_off, mi->seq_off.data(), (size_t)mi->n_seq * 8, hipMemcpyHostToDevice) != hipSuccess ||
 	    hipMemcpy(rp.seq_len, mi->seq_len.data(), (size_t)mi->n_seq * 4, hipMemcpyHostToDevice) != hipSuccess) return fail(MM355_EHIP);
+	if (mi->name_rank.size() != mi->n_seq) return fail(MM355_EINVAL);
+	if (hipMemcpy(rp.name_rank, mi->name_rank.data(), (size_t)mi->n_seq * 4, hipMemcpyHostToDevice) != hipSuccess) return fail(MM355_EHIP);
 	{ const int rc2 = mm355_replica_pack2(mi, &rp); if (rc2) return fail(rc2); }
 	mi->replicas.push_back(rp);
 	(void)hipSetDevice(prev);
@@ -327,6 +331,7 @@ void mm355_index_free_replicas(mm355_index *mi)
 		(void)hipSetDevice(r.dev);
 		if (r.slots) (void)hipFree(r.slots); if (r.pos) (void)hipFree(r.pos); if (r.S) (void)hipFree(r.S);
 		if (r.seq_off) (void)hipFree(r.seq_off); if (r.seq_len) (void)hipFree(r.seq_len); if (r.S2) (void)hipFree(r.S2); if (r.nr) (void)hipFree(r.nr);
+		if (r.name_rank) (void)hipFree(r.name_rank);
 	}
 	if (!mi->replicas.empty()) (void)hipSetDevice(prev);
 	mi->replicas.clear();
@@ -353,7 +358,7 @@ extern "C" void mm355_ctx_destroy(mm355_ctx_t *c)
 {
 	if (c == 0) return;
 	(void)hipSetDevice(c->dev);
-	DBuf *bufs[] = { &c->sort_tasks, &c->sort_flag, &c->tie_list, &c->n_keep, &c->aoff2, &c->cs_list, &c->tie_a, &c->tie_b, &c->tie_f, &c->tie_p, &c->tie_t8, &c->tie_tcnt, &c->heavy, &c->seq, &c->roff, &c->rlen, &c->order, &c->ck_read, &c->ck_start, &c->ck_n, &c->ck_r0,
+	DBuf *bufs[] = { &c->sort_tasks, &c->sort_flag, &c->tie_list, &c->n_keep, &c->aoff2, &c->cs_list, &c->tie_a, &c->tie_b, &c->tie_f, &c->tie_p, &c->tie_t8, &c->tie_tcnt, &c->heavy, &c->name_key, &c->seq, &c->roff, &c->rlen, &c->order, &c->ck_read, &c->ck_start, &c->ck_n, &c->ck_r0,
 		&c->mz, &c->mz_tmp, &c->n_mz, &c->sn, &c->sv, &c->sflt, &c->hl, &c->soff, &c->n_a, &c->rep_len, &c->n_mini, &c->mini_pos, &c->counters, &c->err,
 		&c->aoff, &c->a, &c->f, &c->p, &c->v, &c->z, &c->t8, &c->vi, &c->b, &c->wk, &c->u, &c->u2, &c->n_u, &c->n_v,
 		&c->kprof, &c->d_chunks, &c->dp_jobs, &c->dp_res, &c->dp_q, &c->dp_t, &c->dp_bt, &c->dp_bt2, &c->dp_fail, &c->dp_cig, &c->dp_work, &c->dp_H, &c->rq, &c->dp_dense, &c->dp_gather, &c->pack, &c->rmq_list, &c->rmq_flag, &c->x_jobs, &c->x_cig, &c->x_cs, &c->x_out, &c->x_dense,
@@ -474,16 +479,45 @@ int mm355_run_sketch(mm355_ctx *c)
 	return 0;
 }
 
+void mm355_set_names(mm355_ctx *c, int64_t n_reads, const char *const *names)
+{
+	HostBatch &hb = c->hb;
+	hb.name_x31.clear(); hb.name_key.clear();
+	bool any = false;
+	for (int64_t i = 0; names && i < n_reads; ++i) if (names[i]) { any = true; break; }
+	if (!any) return;
+	hb.name_x31.assign(n_reads, 0); hb.name_key.assign(n_reads, 0);
+	for (int64_t i = 0; i < n_reads; ++i) {
+		if (names[i] == 0) continue;
+		hb.name_x31[i] = mm355_x31(names[i]); hb.name_key[i] = mm355_name_key(c->mi->names_sorted, names[i]);
+	}
+}
+
+// the argument of the named seed kernels, after uploading the reads' name words (8 B per read, only on this path)
+static int dev_names(mm355_ctx *c, DevNames *nm, bool upload)
+{
+	const size_t n = c->hb.name_key.size();
+	if (c->d_name_rank == 0) return MM355_EINVAL;   // a replica without the rank table must never reach a kernel
+	if (upload) {
+		if (c->name_key.ensure(n * 8 + 8)) return MM355_ENOMEM;
+		HIPCHK(hipMemcpyAsync(c->name_key.p, c->hb.name_key.data(), n * 8, hipMemcpyHostToDevice, c->st));   // (the vector lives with the batch; the stage synchronises before it returns)
+	}
+	nm->key = c->name_key.as<uint64_t>(); nm->name_rank = c->d_name_rank;
+	return 0;
+}
+
 static int upload_heavy_order(mm355_ctx *c);
 int mm355_run_seeds(mm355_ctx *c, const DevParams &pr)
 {
 	DevBatch b = dev_batch(c); DevSeeds s = dev_seeds(c);
 	HostBatch &hb = c->hb;
+	DevNames nm; const bool named = mm355_name_filter_on(c, pr);
+	if (named) { const int rcn = dev_names(c, &nm, true); if (rcn) return rcn; }
 	{ EvTimer t(c, &c->stats.ms_seed); mm355_launch_mzflt(pr, b, s, c->st, c); }
 	{ EvTimer t(c, &c->stats.ms_seed_lookup); mm355_launch_seed_lookup(c->dix, b, s, c->ck_read.as<int32_t>(), c->ck_start.as<int32_t>(), (int)c->n_chunks,
 	                                                                   c->counters.as<unsigned long long>() + CTR_HITS_OFF, (unsigned int*)(c->counters.as<unsigned long long>() + 2), c->st, c); }
 	++c->stats.n_launch_seed;
-	{ EvTimer t(c, &c->stats.ms_seed); mm355_launch_seed_select(c->dix, pr, b, s, c->st, c); }
+	{ EvTimer t(c, &c->stats.ms_seed); mm355_launch_seed_select(c->dix, pr, b, s, c->st, c, named? &nm : 0); }
 	HIPCHK(hipGetLastError());
 	int64_t n = hb.n_reads;
 	hb.n_mz.resize(n); hb.n_a.resize(n); hb.rep_len.resize(n); hb.n_mini.resize(n); hb.aoff.resize(n + 1);
@@ -516,7 +550,9 @@ int mm355_run_seeds(mm355_ctx *c, const DevParams &pr)
 int mm355_run_expand(mm355_ctx *c, const DevParams &pr)
 {
 	DevBatch b = dev_batch(c); DevSeeds s = dev_seeds(c); DevAnchors a = dev_anchors(c);
-	{ EvTimer t(c, &c->stats.ms_seed_expand); mm355_launch_seed_expand(c->dix, pr, b, s, a, c->st, c); }
+	DevNames nm; const bool named = mm355_name_filter_on(c, pr);
+	if (named) { const int rcn = dev_names(c, &nm, false); if (rcn) return rcn; }   // (uploaded by mm355_run_seeds)
+	{ EvTimer t(c, &c->stats.ms_seed_expand); mm355_launch_seed_expand(c->dix, pr, b, s, a, c->st, c, named? &nm : 0); }
 	HIPCHK(hipGetLastError());
 	return 0;
 }
@@ -756,12 +792,14 @@ int mm355_run_rmq(mm355_ctx *c, const mm355_mapopt_t *mo, const DevParams &pr)
 }
 
 // ------------------------------------------------------------------ per-stage C-ABI (tests + bench)
-static int stage_prologue(mm355_ctx *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens, DevParams *pr)
+static int stage_prologue(mm355_ctx *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens, DevParams *pr, const char *const *names = 0)
 {
 	if (c == 0) return MM355_EINVAL;
 	if (mo) { int rc = mm355_check_opts(mo, c->mi); if (rc) return rc; *pr = mm355_make_params(mo, c->mi); }
 	c->n_tpend = 0; memset(&c->stats, 0, sizeof(c->stats));
-	return mm355_run_pack(c, n_reads, seqs, lens);
+	const int rc = mm355_run_pack(c, n_reads, seqs, lens);
+	if (rc == 0) mm355_set_names(c, n_reads, names);
+	return rc;
 }
 
 extern "C" int mm355_stage_sketch(mm355_ctx_t *c, int64_t n_reads, const char *const *seqs, const int32_t *lens, int64_t *mz_off, uint64_t *mz, int64_t mz_cap)
@@ -785,8 +823,14 @@ extern "C" int mm355_stage_sketch(mm355_ctx_t *c, int64_t n_reads, const char *c
 extern "C" int mm355_stage_anchors(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens, int sorted,
                                    int64_t *a_off, uint64_t *a, int64_t a_cap, int32_t *rep_len, int32_t *n_mini_pos)
 {
+	return mm355_stage_anchors_named(c, mo, n_reads, seqs, lens, 0, sorted, a_off, a, a_cap, rep_len, n_mini_pos);
+}
+
+extern "C" int mm355_stage_anchors_named(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
+                                         const char *const *names, int sorted, int64_t *a_off, uint64_t *a, int64_t a_cap, int32_t *rep_len, int32_t *n_mini_pos)
+{
 	DevParams pr; int rc;
-	if ((rc = stage_prologue(c, mo, n_reads, seqs, lens, &pr))) return rc;
+	if ((rc = stage_prologue(c, mo, n_reads, seqs, lens, &pr, names))) return rc;
 	if ((rc = mm355_run_sketch(c))) return rc;
 	if ((rc = mm355_run_seeds(c, pr))) return rc;
 	if ((rc = mm355_run_expand(c, pr))) return rc;

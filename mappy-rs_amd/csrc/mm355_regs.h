@@ -57,10 +57,10 @@ MM_HD uint64_t mm355r_hash64(uint64_t key)
 	key = ((key + (key << 2)) + (key << 4)); key = key ^ key >> 28; key = (key + (key << 31));
 	return key;
 }
-// U:map.c::mm_map_frag: the read hash without a query name (the crate passes none)
-MM_HD uint32_t mm355r_read_hash(int32_t qlen, int32_t seed)
+// U:map.c::mm_map_frag: the read hash; name_hash = X31(qname), 0 for a read without a name or under MM_F_NO_HASH_NAME
+MM_HD uint32_t mm355r_read_hash(int32_t qlen, int32_t seed, uint32_t name_hash = 0)
 {
-	uint32_t h = 0;
+	uint32_t h = name_hash;
 	h ^= mm355r_wang32((uint32_t)qlen) + mm355r_wang32((uint32_t)seed);
 	return mm355r_wang32(h);
 }
@@ -365,11 +365,11 @@ MM_HD int mm355r_finish(const Mm355RegsOpt &o, const uint32_t *seq_len, int32_t 
 // divergence must not depend on the device's pow).
 MM_HD int mm355_regs_read(const Mm355RegsOpt &o, const uint32_t *seq_len, int32_t qlen, int32_t rep_len, int n_u, const uint64_t *u, const mm128 *a,
                           int32_t n_mini, const uint64_t *mini_pos, const float *logt, int32_t n_logt, const Mm355RegsScratch &s, uint32_t *mapq,
-                          mm355_hit_t *out, mm355_tags_t *tags = nullptr)
+                          mm355_hit_t *out, mm355_tags_t *tags = nullptr, uint32_t name_hash = 0)
 {
 	if (n_u <= 0 || qlen <= 0) return 0;
 	Mm355Reg *r = s.r;
-	int n = mm355r_gen_regs(mm355r_read_hash(qlen, o.seed), qlen, n_u, u, a, s.z, r);
+	int n = mm355r_gen_regs(mm355r_read_hash(qlen, o.seed, name_hash), qlen, n_u, u, a, s.z, r);
 	if (!(o.flag & MMF_ALL_CHAINS)) {
 		mm355r_set_parent(o.mask_level, o.mask_len, n, r, (int)(o.flag & MMF_HARD_MLEVEL), s.cov, s.w);
 		n = mm355r_select_sub(o.pri_ratio, o.min_diff, o.best_n, o.min_strand_sc, n, r, s.tmp);

@@ -18,7 +18,8 @@
 struct RegsRead {                 // per read of the batch
 	int64_t hoff;                 // first scratch / row slot (exclusive scan of n_u over the reads the device takes)
 	int32_t qlen, rep_len, n_u, n_mini;
-	int32_t run, pad;             // run: 1 = the device takes the read
+	int32_t run;                  // 1 = the device takes the read
+	uint32_t name_hash;           // X31 of the query name as U:map.c::mm_map_frag hashes it; 0 for an unnamed read (the word was padding before)
 };
 
 #define K_REGS_ARGS int n_reads, const RegsRead *rr, const int64_t *aoff, const int64_t *roff, const uint64_t *u,                     \
@@ -36,7 +37,7 @@ __device__ __forceinline__ void regs_lane(K_REGS_ARGS, mm355_tags_t *tags)
 	s.r = sr + h; s.z = sz + h; s.cov = scov + h; s.w = sw + h; s.tmp = stmp + h;
 	const int64_t ao = aoff[r];
 	cnt[r] = mm355_regs_read(o, seq_len, q.qlen, q.rep_len, q.n_u, u + ao, a + ao, q.n_mini, mini_pos + roff[r], logt, n_logt, s, smq + h, hits + h,
-	                         tags? tags + h : nullptr);
+	                         tags? tags + h : nullptr, q.name_hash);
 }
 // two entry points over one body: without MM355_OUT_TAGS the kernel takes the arguments and runs the code it always did
 __global__ __launch_bounds__(64) void k_regs(K_REGS_ARGS)
@@ -92,7 +93,7 @@ int mm355_map_chain_only(mm355_ctx *c, const mm355_mapopt_t *mo, const std::vect
 		RegsRead &q = rr[i];
 		memset(&q, 0, sizeof(q));
 		const int rst = hb.rmq_state.empty()? MM355_RMQ_HOST_ALL : (int)hb.rmq_state[i];
-		q.qlen = qlen[i]; q.rep_len = hb.rep_len[i]; q.n_u = hb.n_u[i]; q.n_mini = hb.n_mini[i];
+		q.qlen = qlen[i]; q.rep_len = hb.rep_len[i]; q.n_u = hb.n_u[i]; q.n_mini = hb.n_mini[i]; q.name_hash = mm355_read_name_hash(hb, mo->flag, i);
 		q.run = !all_host && q.qlen > 0 && (rst == MM355_RMQ_KEEP || rst == MM355_RMQ_DONE);
 		q.hoff = tot;
 		if (q.run) { tot += q.n_u; ++n_run; }
@@ -171,7 +172,7 @@ int mm355_map_chain_only(mm355_ctx *c, const mm355_mapopt_t *mo, const std::vect
 		auto one = [&](int64_t j) {
 			const int r = sel[j];
 			ReadState rs;
-			rs.qlen = qlen[r]; rs.rep_len = hb.rep_len[r];
+			rs.qlen = qlen[r]; rs.rep_len = hb.rep_len[r]; rs.name_hash = mm355_read_name_hash(hb, mo->flag, r);
 			rs.u.assign(pu + uo[j], pu + uo[j + 1]);
 			rs.a.assign(pa + vo[j], pa + vo[j + 1]);
 			rs.mini_pos.assign(pm + mo_[j], pm + mo_[j + 1]);

@@ -455,7 +455,7 @@ class Aligner:
 
     def __init__(self, fn_idx_in=None, preset=None, k=None, w=None, min_cnt=None, min_chain_score=None,
                  min_dp_score=None, bw=None, best_n=None, n_threads=3, fn_idx_out=None, max_frag_len=None,
-                 extra_flags=None, seq=None, scoring=None, device=0, devices=None, *, cigar=True, tags=False):
+                 extra_flags=None, seq=None, scoring=None, device=0, devices=None, *, cigar=True, tags=False, name_key=None):
         L = _ffi.lib()
         self._L = L
         self._idx = C.c_void_p()
@@ -470,6 +470,8 @@ class Aligner:
         self._lock = threading.Lock()
         # tags=True: every mapping call asks for the mm355_tags_t rows (MM355_OUT_TAGS): the records carry minimap2's PAF tags (s1, dv, de, rl ...)
         self._tag_flag = _ffi.OUT_TAGS if tags else 0
+        # name_key: map_batch passes item[name_key] as the read's query name (mappy's map(seq, name=...)); a missing key or None = unnamed
+        self._name_key = name_key
         io, mo = _ffi.IdxOpt(), _ffi.MapOpt()
         L.mm355_set_opt(None, C.byref(io), C.byref(mo))
         if preset is not None:
@@ -569,16 +571,22 @@ class Aligner:
                 raise RuntimeError("mm355: " + self._L.mm355_strerror(rc).decode())
         return self._ctx
 
-    def _map_many(self, seqs, flags, ctx=None):
-        """one mm355_map_batch call; returns list of list[Mapping].  ctx: a pipeline worker's own context (no lock needed)"""
+    def _map_many(self, seqs, flags, ctx=None, names=None):
+        """one mm355_map_batch call; returns list of list[Mapping].  ctx: a pipeline worker's own context (no lock needed).
+        names: query names (str or None per read); None or all None = the unnamed call"""
         L = self._L
         arr, lens, keep = _ffi.pack_reads(seqs)
         hp = C.POINTER(_ffi.Hits)()
+        narr = _ffi.pack_names(names)
+        if narr is None:
+            call = lambda c: L.mm355_map_batch(c, C.byref(self._mo), len(seqs), arr, lens, flags, C.byref(hp))
+        else:
+            call = lambda c: L.mm355_map_batch_named(c, C.byref(self._mo), len(seqs), arr, lens, narr, flags, C.byref(hp))
         if ctx is None:
             with self._lock:
-                rc = L.mm355_map_batch(self._context(), C.byref(self._mo), len(seqs), arr, lens, flags, C.byref(hp))
+                rc = call(self._context())
         else:
-            rc = L.mm355_map_batch(ctx, C.byref(self._mo), len(seqs), arr, lens, flags, C.byref(hp))
+            rc = call(ctx)
         if rc != 0:
             raise RuntimeError(L.mm355_strerror(rc).decode())
         try:
@@ -610,7 +618,9 @@ class Aligner:
             self._wctx.setdefault(dev_ctx[0], []).append(dev_ctx[1])
 
     # ---- single read (lib.rs:473-514)
-    def map(self, seq, seq2=None, cs=False, MD=False):
+    def map(self, seq, seq2=None, cs=False, MD=False, *, name=None):
+        """name: the read's query name (mappy's `name`): it enters the hash that orders regions of equal score, and with the ava-ont / ava-pb
+        presets (MM_F_NO_DIAG / MM_F_NO_DUAL) it filters self hits and the second report of every pair.  None = an unnamed read."""
         if seq2 is not None:
             raise NotImplementedError("Using `seq2` is not implemented")
         if not isinstance(seq, str):
@@ -618,8 +628,10 @@ class Aligner:
                             else "argument 'seq' must be str")
         if (cs or MD) and not self._mo.flag & 4:
             raise ValueError("cs / MD need base-level alignment: this Aligner was created with cigar=False")
+        if name is not None and not isinstance(name, str):
+            raise ValueError("`name` must be a string")
         flags = (_ffi.OUT_CS if cs else 0) | (_ffi.OUT_MD if MD else 0) | self._tag_flag
-        r = self._map_many([seq], flags)[0]
+        r = self._map_many([seq], flags, names=None if name is None else [name])[0]
         if isinstance(r, Exception):
             raise r
         return r
@@ -666,6 +678,18 @@ class Aligner:
         workers = st.threads
         self._names()                       # fill the name cache before the workers read it
         map_many, acquire, release = self._map_many, self._ctx_acquire, self._ctx_release
+        name_key = self._name_key
+
+        def names_of(items):
+            """query names of a sub-batch (None without name_key or when no item has one); a name that is not str: ValueError, like `seq`"""
+            if name_key is None:
+                return None
+            names = [it.get(name_key) for it in items]
+            if all(nm is None for nm in names):
+                return None
+            if not all(nm is None or isinstance(nm, str) for nm in names):
+                raise ValueError("`%s` must be a string" % (name_key,))
+            return names
         out_flags = (_ffi.OUT_CS if self._mo.flag & 4 else 0) | self._tag_flag        # chain-only: no cs string to produce
 
         # (the closures below capture `st`, never the iterator handed to the caller)
@@ -679,10 +703,11 @@ class Aligner:
                             cv.wait(0.2)
                         if st.cancel.is_set() or not work:
                             return
-                        reads, items = work.popleft()
+                        reads, items, names = work.popleft()
                         state["pending"] -= len(reads)
                         cv.notify_all()                                   # the producer may be waiting for room (back-off)
-                    maps = map_many(reads, out_flags, ctx[1])             # cs=true, MD=false: lib.rs:589-590
+                    # cs=true, MD=false: lib.rs:589-590
+                    maps = map_many(reads, out_flags, ctx[1]) if names is None else map_many(reads, out_flags, ctx[1], names=names)
                     st.t_sub_done.append(time.perf_counter())
                     # a worker error on one read => no result for that id (lib.rs:621-623)
                     out = [(m, it) for m, it in zip(maps, items) if not isinstance(m, Exception)]
@@ -696,6 +721,7 @@ class Aligner:
                     release(ctx)
 
         def dispatch(reads, items):
+            names = names_of(items)           # (raises in the caller's thread, before the sub-batch is queued)
             with cv:
                 # the reference's work queue holds 50 000 reads (lib.rs:429): with back-off the producer sleeps until the workers have
                 # made room (lib.rs:870-888), so a huge iterable never sits in memory as pending sub-batches
@@ -703,7 +729,7 @@ class Aligner:
                 while (back_off and state["pending"] > 0 and state["pending"] + len(reads) > WORK_QUEUE_CAP and not st.cancel.is_set()
                        and len(st.ch) < RESULT_CHANNEL_CAP):
                     cv.wait(0.05)
-                work.append((reads, items))
+                work.append((reads, items, names))
                 state["pending"] += len(reads)
                 state["n_sub"] += 1
                 cv.notify()

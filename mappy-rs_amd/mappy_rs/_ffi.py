@@ -104,6 +104,7 @@ EXPORTS = [
     "mm355_index_get", "mm355_index_stat", "mm355_upload", "mm355_ctx_create", "mm355_ctx_destroy", "mm355_map_batch",
     "mm355_free_hits", "mm355_batch_upload", "mm355_batch_select", "mm355_map_resident", "mm355_stage_sketch", "mm355_stage_anchors", "mm355_stage_chain", "mm355_stage_chains", "mm355_stage_rmq",
     "mm355_stage_dp", "mm355_stage_extra", "mm355_get_stats", "mm355_device_count", "mm355_device_synchronize", "mm355_strerror", "mm355_version",
+    "mm355_map_batch_named", "mm355_batch_upload_named", "mm355_stage_anchors_named",
 ]
 
 _LIB = None
@@ -139,6 +140,9 @@ def lib():
     L.mm355_ctx_create.argtypes = [vp, C.c_int, C.POINTER(vp)]
     L.mm355_ctx_destroy.argtypes = [vp]
     L.mm355_map_batch.argtypes = [vp, C.POINTER(MapOpt), C.c_int64, C.POINTER(C.c_char_p), i32p, C.c_int, C.POINTER(C.POINTER(Hits))]
+    L.mm355_map_batch_named.argtypes = [vp, C.POINTER(MapOpt), C.c_int64, C.POINTER(C.c_char_p), i32p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.POINTER(Hits))]
+    L.mm355_batch_upload_named.argtypes = [vp, C.c_int64, C.POINTER(C.c_char_p), i32p, C.POINTER(C.c_char_p)]
+    L.mm355_stage_anchors_named.argtypes = [vp, C.POINTER(MapOpt), C.c_int64, C.POINTER(C.c_char_p), i32p, C.POINTER(C.c_char_p), C.c_int, vp, vp, C.c_int64, vp, vp]
     L.mm355_free_hits.argtypes = [C.POINTER(Hits)]
     L.mm355_batch_upload.argtypes = [vp, C.c_int64, C.POINTER(C.c_char_p), i32p]
     L.mm355_batch_select.argtypes = [vp, C.c_int]
@@ -192,6 +196,14 @@ def pack_reads(seqs):
     return arr, lens, bs
 
 
+def pack_names(names):
+    """list of str / bytes / None -> char** array (None -> NULL: an unnamed read), or None when no read has a name.  str is encoded as UTF-8."""
+    if names is None or all(nm is None for nm in names):
+        return None
+    bs = [None if nm is None else nm if isinstance(nm, (bytes, bytearray)) else nm.encode("utf-8") for nm in names]
+    return (C.c_char_p * len(bs))(*bs)
+
+
 class StageRunner:
     """Per-stage view of the device path for the parity tests and the kernel bench."""
 
@@ -226,15 +238,20 @@ class StageRunner:
         check(self.L.mm355_stage_sketch(self.ctx, n, arr, lens, off.ctypes.data, mz.ctypes.data, cap))
         return [mz[off[i]:off[i + 1]].copy() for i in range(n)]
 
-    def anchors(self, seqs, sorted_=True, cap=None):
+    def anchors(self, seqs, sorted_=True, cap=None, names=None):
+        """names: None = mm355_stage_anchors; a list (str / bytes / None per read) = mm355_stage_anchors_named"""
         arr, lens, keep = pack_reads(seqs)
         n = len(seqs)
         cap = cap or (64 * sum(len(b) for b in keep) + 1024)
         off = np.zeros(n + 1, np.int64)
         a = np.zeros((cap, 2), np.uint64)
         rep = np.zeros(n, np.int32); nmp = np.zeros(n, np.int32)
-        check(self.L.mm355_stage_anchors(self.ctx, C.byref(self.mo), n, arr, lens, int(sorted_), off.ctypes.data,
-                                         a.ctypes.data, cap, rep.ctypes.data, nmp.ctypes.data))
+        if names is None:
+            check(self.L.mm355_stage_anchors(self.ctx, C.byref(self.mo), n, arr, lens, int(sorted_), off.ctypes.data,
+                                             a.ctypes.data, cap, rep.ctypes.data, nmp.ctypes.data))
+        else:
+            check(self.L.mm355_stage_anchors_named(self.ctx, C.byref(self.mo), n, arr, lens, pack_names(names), int(sorted_), off.ctypes.data,
+                                                   a.ctypes.data, cap, rep.ctypes.data, nmp.ctypes.data))
         return [a[off[i]:off[i + 1]].copy() for i in range(n)], rep, nmp
 
     def chain(self, seqs, cap=None):

@@ -10,7 +10,15 @@ sub-batches of SUB reads, timed after a warm-up; the index is built on the devic
 and reports each pass (the spread between passes is what a difference between two builds has to exceed); the rate is the median pass.
 
 ecoli: bench.py's configs[1] genome and read model; human: its configs[2] genome (make_human_like, seed 3, --scale 1) and read model.
---n50 / --lo / --hi override the read lengths (e.g. 150 kb - 1 Mb reads)."""
+--n50 / --lo / --hi override the read lengths (e.g. 150 kb - 1 Mb reads).
+
+    python tools/chainonly_bench.py --ava 8192 [--workload ecoli] [--preset ava-ont] [--reps R] [--out F]
+
+--ava N is the read-vs-read mode: the first N reads of the read set are indexed as their own targets (contig names r0, r1 ...) and mapped
+chain-only against that index as ONE resident batch, once without names (mm355_batch_upload: every read hits itself and every pair is
+reported from both sides) and once with them (mm355_batch_upload_named: skip_seed's NO_DIAG / NO_DUAL filter on the device).  Reported for
+both: Mbases/s of mm355_map_resident (median pass), hits, anchors generated (n_a), and ms_kernel[3] / [4] (k_seed_select, k_seed_expand)
+next to the sum of the other kernels."""
 import argparse
 import ctypes as C
 import json
@@ -29,6 +37,60 @@ import synthdata as S  # noqa: E402
 READS = {"ecoli": (2, dict(n50=8000, sigma=0.75, lo=500, hi=100000)), "human": (4, dict(n50=10000, sigma=0.75, lo=500, hi=100000))}
 
 
+def ava_main(args):
+    from mappy_rs import _ffi
+    L = _ffi.lib()
+    t0 = time.time()
+    g = S.make_genome(1, [4641652], gc=0.508, repeats=((5000, 7, 0.01), (1300, 20, 0.01))) if args.workload == "ecoli" else S.make_human_like(3, args.scale)[0]
+    seed, kw = READS[args.workload]
+    reads, _ = S.make_reads(seed, g, args.ava, **kw)
+    names = ["r%d" % i for i in range(len(reads))]
+    preset = args.preset if args.preset.startswith("ava") else "ava-ont"
+    io, mo = _ffi.IdxOpt(), _ffi.MapOpt()
+    L.mm355_set_opt(None, C.byref(io), C.byref(mo))
+    _ffi.check(L.mm355_set_opt(preset.encode(), C.byref(io), C.byref(mo)))
+    arr, rl, keep = _ffi.pack_reads(reads)
+    narr = _ffi.pack_names(names)
+    lens64 = (C.c_int64 * len(reads))(*[len(r) for r in reads])
+    idx = C.c_void_p()
+    _ffi.check(L.mm355_index_build(C.byref(io), len(reads), arr, lens64, narr, 16, C.byref(idx)))
+    L.mm355_mapopt_update(C.byref(mo), idx)
+    mo.flag &= ~4
+    ctx = C.c_void_p()
+    _ffi.check(L.mm355_ctx_create(idx, 0, C.byref(ctx)))
+    bases = int(sum(map(len, reads)))
+    print("[ava] %d reads, %.1f Mbases, index built in %.1fs" % (len(reads), bases / 1e6, time.time() - t0), flush=True)
+    res = {"mode": "read-vs-read", "workload": args.workload, "preset": preset, "n_reads": len(reads), "bases": bases, "mid_occ": int(mo.mid_occ)}
+    for leg in ("unnamed", "named"):
+        if leg == "named":
+            _ffi.check(L.mm355_batch_upload_named(ctx, len(reads), arr, rl, narr))
+        else:
+            _ffi.check(L.mm355_batch_upload(ctx, len(reads), arr, rl))
+        hp = C.POINTER(_ffi.Hits)()
+        st = _ffi.Stats()
+        rates = []
+        for rep in range(max(1, args.reps) + 1):                  # the first pass is the warm-up
+            t = time.perf_counter()
+            _ffi.check(L.mm355_map_resident(ctx, C.byref(mo), 0, C.byref(hp)))
+            dt = time.perf_counter() - t
+            n_hits = int(hp.contents.n_hits)
+            L.mm355_free_hits(hp)
+            if rep:
+                rates.append(round(bases / dt / 1e6, 1))
+        L.mm355_get_stats(ctx, C.byref(st))
+        res[leg] = {"mbases_per_s": sorted(rates)[len(rates) // 2], "mbases_per_s_passes": rates, "n_hits": n_hits, "n_a": int(st.n_a),
+                    "n_a_kept": int(st.n_a_kept), "ms_k_seed_select": round(st.ms_kernel[3], 3), "ms_k_seed_expand": round(st.ms_kernel[4], 3),
+                    "ms_other_kernels": round(sum(st.ms_kernel[:3]) + sum(st.ms_kernel[5:]), 3), "ms_total": round(st.ms_total, 1),
+                    "n_regs_dev": int(st.n_regs_dev), "n_regs_host": int(st.n_regs_host)}
+        print("[ava] %s: %s" % (leg, json.dumps(res[leg])), flush=True)
+    res["ratio_named_to_unnamed"] = round(res["named"]["mbases_per_s"] / res["unnamed"]["mbases_per_s"], 2)
+    L.mm355_ctx_destroy(ctx); L.mm355_index_free(idx)
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="ecoli", choices=sorted(READS))
@@ -43,7 +105,10 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--tags", action="store_true")
     ap.add_argument("--reps", type=int, default=1)
+    ap.add_argument("--ava", type=int, default=0, help="read-vs-read mode over the first N reads, with and without query names")
     args = ap.parse_args()
+    if args.ava > 0:
+        return ava_main(args)
     import mappy_rs
     from mappy_rs import _ffi
     from oracle import oracle as O
