@@ -16,6 +16,7 @@
 #include "mm355_glue.h"
 #include "mm355_prof.h"
 #include "mm355_regs.h"
+#include "mm355_rmq.h"
 #include "mm355_selfclamp.h"
 #include <atomic>
 #include <chrono>
@@ -820,7 +821,7 @@ void mm355_glue_regions(const mm355_index *mi, const mm355_mapopt_t *opt, ReadSt
 	const float pen_gap = (float)(opt->chain_gap_scale * 0.01 * mi->k), pen_skip = (float)(opt->chain_skip_scale * 0.01 * mi->k);
 	int n_regs0 = (int)rs.u.size();
 	{ ProfScope pf(PF_PRE_RMQ);
-	if (rmq_state == 2) {   // MM355_RMQ_HOST: the device sorted the chained anchors and left the chaining to the literal code
+	if (rmq_state == MM355_RMQ_HOST) {   // the device sorted the chained anchors and left the chaining to the literal code
 		rechain_rmq(opt->max_gap, opt->rmq_inner_dist, opt->bw_long, opt->max_chain_skip, opt->rmq_size_cap, opt->min_cnt, opt->min_chain_score,
 		            pen_gap, pen_skip, rs.a, rs.u);
 	} else if (rmq_state < 0 && opt->bw_long > opt->bw && (opt->flag & (MMF_SPLICE | MMF_SR | MMF_NO_LJOIN)) == 0 && n_regs0 > 1) {
@@ -1787,12 +1788,7 @@ void mm355_glue_finish(const mm355_index *mi, const mm355_mapopt_t *opt, ReadSta
 	for (int i = 0; i < n; ++i) {
 		const Reg *r = &regs[i];
 		mm355_hit_t h;
-		memset(&h, 0, sizeof(h));
-		h.query_start = r->qs; h.query_end = r->qe; h.strand = r->rev? -1 : 1; h.rid = r->rid;
-		h.target_len = (int32_t)mi->seq_len[r->rid]; h.target_start = r->rs; h.target_end = r->re;
-		h.match_len = r->mlen; h.block_len = r->blen; h.mapq = r->mapq; h.is_primary = r->parent == r->id;
-		h.cs_len = h.md_len = -1;
-		h.score0 = r->score0; h.cnt = r->cnt; h.n_sub = r->n_sub; h.subsc = r->subsc;
+		mm355r_hit(r, r->mapq, mi->seq_len.data(), &h);
 		if (r->p) {
 			h.NM = r->blen - r->mlen + (int32_t)r->p->n_ambi;
 			h.n_cigar = (int32_t)r->p->cigar.size(); h.cigar_off = (int64_t)cigar.size();
@@ -1804,9 +1800,8 @@ void mm355_glue_finish(const mm355_index *mi, const mm355_mapopt_t *opt, ReadSta
 		hits.push_back(h);
 		if (tags) {   // MM355_OUT_TAGS: what U:format.c::mm_write_paf reads of the region besides the columns
 			mm355_tags_t t;
-			memset(&t, 0, sizeof(t));
-			t.score = r->score; t.div = r->div; t.rep_len = rs.rep_len;
-			t.flags = (r->inv? MM355_TAG_INV : 0u) | (r->sam_pri? MM355_TAG_SAM_PRI : 0u) | (r->split & 3u) << MM355_TAG_SPLIT_SHIFT;
+			mm355r_tags(r, rs.rep_len, &t);
+			t.flags |= (r->inv? MM355_TAG_INV : 0u) | (r->split & 3u) << MM355_TAG_SPLIT_SHIFT;
 			if (r->p) { t.n_ambi = (int32_t)r->p->n_ambi; t.n_gap = r->p->n_gap; t.n_gapo = r->p->n_gapo; }
 			tags->push_back(t);
 		}
@@ -1822,17 +1817,12 @@ void mm355_glue_chain_finish(const mm355_index *mi, const mm355_mapopt_t *opt, R
 	set_mapq(n, rs.regs.data(), opt->min_chain_score, opt->a, rs.rep_len);
 	for (int i = 0; i < n; ++i) {
 		const Reg *r = &rs.regs[i];
-		Mm355Reg t;
-		memset(&t, 0, sizeof(t));
-		t.qs = r->qs; t.qe = r->qe; t.rev = r->rev; t.rid = r->rid; t.rs = r->rs; t.re = r->re; t.mlen = r->mlen; t.blen = r->blen;
-		t.parent = r->parent; t.id = r->id; t.score0 = r->score0; t.cnt = r->cnt; t.n_sub = r->n_sub; t.subsc = r->subsc;
 		mm355_hit_t h;
-		mm355r_hit(&t, r->mapq, mi->seq_len.data(), &h);
+		mm355r_hit(r, r->mapq, mi->seq_len.data(), &h);
 		hits.push_back(h);
 		if (tags) {
-			t.score = r->score; t.div = r->div; t.sam_pri = (uint16_t)r->sam_pri;
 			mm355_tags_t g;
-			mm355r_tags(&t, rs.rep_len, &g);
+			mm355r_tags(r, rs.rep_len, &g);
 			tags->push_back(g);
 		}
 	}

@@ -17,19 +17,22 @@
 #include "mm355_pipeline.h"
 #include "mm355_dp.h"
 #include "mm355_glue.h"
+#include "mm355_hits.h"
+#include "mm355_rmq.h"
 #include "mm355_prof.h"
 
-// packs u[], compacted anchors and mini_pos[] of all reads into three dense arrays (one D2H copy each)
-__global__ __launch_bounds__(256) void k_pack_chains(int n_reads, const int64_t *aoff, const int64_t *roff, const int32_t *n_u, const int32_t *n_v, const int32_t *n_mini,
-                                                     const int64_t *uo, const int64_t *vo, const int64_t *mo, const uint64_t *u, const mm128 *a, const uint64_t *mini_pos,
-                                                     uint64_t *pu, mm128 *pa, uint64_t *pm)
+// packs u[], compacted anchors and mini_pos[] of read sel[j] (sel == 0: read j) into three dense arrays (one D2H copy each)
+__global__ __launch_bounds__(256) void k_pack_chains(int n, const int32_t *sel, const int64_t *aoff, const int64_t *roff, const int32_t *n_u, const int32_t *n_v,
+                                                     const int32_t *n_mini, const int64_t *uo, const int64_t *vo, const int64_t *mo, const uint64_t *u, const mm128 *a,
+                                                     const uint64_t *mini_pos, uint64_t *pu, mm128 *pa, uint64_t *pm)
 {
-	const int r = blockIdx.x;
-	if (r >= n_reads) return;
+	const int j = blockIdx.x;
+	if (j >= n) return;
+	const int r = sel? sel[j] : j;
 	const int64_t ao = aoff[r], ro = roff[r];
-	for (int i = threadIdx.x; i < n_u[r]; i += 256) pu[uo[r] + i] = u[ao + i];
-	for (int i = threadIdx.x; i < n_v[r]; i += 256) pa[vo[r] + i] = a[ao + i];
-	for (int i = threadIdx.x; i < n_mini[r]; i += 256) pm[mo[r] + i] = mini_pos[ro + i];
+	for (int i = threadIdx.x; i < n_u[r]; i += 256) pu[uo[j] + i] = u[ao + i];
+	for (int i = threadIdx.x; i < n_v[r]; i += 256) pa[vo[j] + i] = a[ao + i];
+	for (int i = threadIdx.x; i < n_mini[r]; i += 256) pm[mo[j] + i] = mini_pos[ro + i];
 }
 
 // One process-wide pool of host threads shared by every context: while some contexts wait for their kernels the others
@@ -167,7 +170,6 @@ static double now_ms() { return std::chrono::duration<double, std::milli>(std::c
 
 static int host_threads() { return HostPool::get().size(); }
 
-static int host_threads();
 // Deferred destruction of a batch's host state: one background thread frees what the mapping threads are done with (the process never joins
 // it: it only ever frees memory).  At most a few batches are pending; bury() frees synchronously when the queue is long (memory bound).
 struct Reaper {
@@ -186,6 +188,59 @@ struct Reaper {
 		}
 	}
 };
+
+static inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+int mm355_fetch_chains(mm355_ctx *c, const int32_t *sel, int64_t n_sel, PackedChains *out)
+{
+	const HostBatch &hb = c->hb;
+	const int64_t n = sel? n_sel : hb.n_reads;
+	*out = PackedChains();
+	if (n <= 0) return 0;
+	// the tables, pinned: [sel] uo vo mo, every sub-array 16-byte aligned here and on the device (mm128 stores)
+	const size_t b_sel = sel? al16((size_t)n * 4) : 0, b_tab = al16((size_t)(n + 1) * 8), b_head = b_sel + 3 * b_tab;
+	if (c->h_pack.ensure(b_head)) return MM355_ENOMEM;
+	char *hs = (char*)c->h_pack.p;
+	int64_t *uo = (int64_t*)(hs + b_sel), *vo = (int64_t*)(hs + b_sel + b_tab), *mo = (int64_t*)(hs + b_sel + 2 * b_tab);
+	if (sel) memcpy(hs, sel, (size_t)n * 4);
+	int64_t tu = 0, tv = 0, tm = 0;
+	for (int64_t j = 0; j < n; ++j) { const int64_t r = sel? sel[j] : j; uo[j] = tu; vo[j] = tv; mo[j] = tm; tu += hb.n_u[r]; tv += hb.n_v[r]; tm += hb.n_mini[r]; }
+	uo[n] = tu; vo[n] = tv; mo[n] = tm;
+	if (c->h_pu.ensure((size_t)(tu + 1) * 8) || c->h_pm.ensure((size_t)(tm + 1) * 8) || c->h_pa.ensure((size_t)(tv + 1) * 16)) return MM355_ENOMEM;
+	const size_t b_u = al16((size_t)tu * 8), b_a = (size_t)tv * 16;
+	if (c->pack.ensure(b_head + b_u + b_a + (size_t)tm * 8 + 256)) return MM355_ENOMEM;
+	char *d = c->pack.as<char>();
+	uint64_t *d_pu = (uint64_t*)(d + b_head); mm128 *d_pa = (mm128*)(d + b_head + b_u); uint64_t *d_pm = (uint64_t*)(d + b_head + b_u + b_a);
+	HIPCHK(hipMemcpyAsync(d, hs, b_head, hipMemcpyHostToDevice, c->st));
+	mm355_kt(c, KT_PACK, 0, c->st);
+	hipLaunchKernelGGL(k_pack_chains, dim3((unsigned)n), dim3(256), 0, c->st, (int)n, sel? (const int32_t*)d : (const int32_t*)0, c->aoff.as<int64_t>(),
+	                   c->roff.as<int64_t>(), c->n_u.as<int32_t>(), c->n_v.as<int32_t>(), c->n_mini.as<int32_t>(), (const int64_t*)(d + b_sel),
+	                   (const int64_t*)(d + b_sel + b_tab), (const int64_t*)(d + b_sel + 2 * b_tab), c->u.as<uint64_t>(), c->a.as<mm128>(),
+	                   c->mini_pos.as<uint64_t>(), d_pu, d_pa, d_pm);
+	mm355_kt(c, KT_PACK, 1, c->st);
+	HIPCHK(hipGetLastError());
+	if (tu) HIPCHK(hipMemcpyAsync(c->h_pu.p, d_pu, (size_t)tu * 8, hipMemcpyDeviceToHost, c->st));
+	if (tv) HIPCHK(hipMemcpyAsync(c->h_pa.p, d_pa, (size_t)tv * 16, hipMemcpyDeviceToHost, c->st));
+	if (tm) HIPCHK(hipMemcpyAsync(c->h_pm.p, d_pm, (size_t)tm * 8, hipMemcpyDeviceToHost, c->st));
+	HIPCHK(mm355_wait_stream(c->st));
+	*out = PackedChains{n, sel, uo, vo, mo, (const uint64_t*)c->h_pu.p, (const mm128*)c->h_pa.p, (const uint64_t*)c->h_pm.p};
+	return 0;
+}
+
+int mm355_seed_read(const mm355_ctx *c, const mm355_mapopt_t *mo, const PackedChains &pk, int64_t j, int32_t qlen, ReadState &r)
+{
+	const HostBatch &hb = c->hb;
+	const int64_t i = pk.sel? pk.sel[j] : j;
+	r.qlen = qlen; r.rep_len = hb.rep_len[i]; r.name_hash = mm355_read_name_hash(hb, mo->flag, i);
+	{ ProfScope pf(PF_PRE_COPY, pk.sel == 0);   // (the CIGAR path's counter: the chain-only tail, which fetches with a list, has none)
+	r.u.assign(pk.pu + pk.uo[j], pk.pu + pk.uo[j + 1]);
+	r.a.assign(pk.pa + pk.vo[j], pk.pa + pk.vo[j + 1]);
+	r.mini_pos.assign(pk.pm + pk.mo[j], pk.pm + pk.mo[j + 1]); }
+	if (qlen <= 0) return -1;
+	int rst = hb.rmq_state.empty()? MM355_RMQ_HOST_ALL : (int)hb.rmq_state[i];
+	if (rst == MM355_RMQ_HOST_ALL) { if (mo->flag & MMF_RMQ) mm355_glue_chain_rmq(c->mi, mo, r); rst = -1; }   // every mg_lchain_rmq call of this read on the host
+	return rst;
+}
 
 static int run_dp_round(mm355_ctx *c, const mm355_mapopt_t *mo, std::vector<ReadState> &rs, const std::vector<DpReq> &reqs, std::vector<std::vector<uint32_t>> &arenas)
 {
@@ -388,37 +443,10 @@ extern "C" int mm355_map_resident(mm355_ctx_t *c, const mm355_mapopt_t *mo, int 
 		c->stats.host_cpu_ms = (double)(thread_cpu_ns() - cpu_start + tl_helper_cpu_ns) * 1e-6;
 		return 0;
 	}
-	HostBatch &hb = c->hb;
 	tv_front = now_ms() - tv0; trace_add(c, "front", tv0, now_ms()); tv0 = now_ms();
 	// pack chains / anchors / mini_pos and bring them to the host
-	std::vector<int64_t> uo(n_reads + 1), vo(n_reads + 1), mo_(n_reads + 1);
-	int64_t tu = 0, tv = 0, tm = 0;
-	for (int64_t i = 0; i < n_reads; ++i) { uo[i] = tu; vo[i] = tv; mo_[i] = tm; tu += hb.n_u[i]; tv += hb.n_v[i]; tm += hb.n_mini[i]; }
-	uo[n_reads] = tu; vo[n_reads] = tv; mo_[n_reads] = tm;
-	if (c->h_pu.ensure((size_t)(tu + 1) * 8) || c->h_pm.ensure((size_t)(tm + 1) * 8) || c->h_pa.ensure((size_t)(tv + 1) * 16)) return MM355_ENOMEM;
-	uint64_t *pu = (uint64_t*)c->h_pu.p, *pm = (uint64_t*)c->h_pm.p; mm128 *pa = (mm128*)c->h_pa.p;
-	if (n_reads) {
-		DBuf &scr = c->b;   // b[] (compact_a scratch) is free again: reuse it for the packed copies
-		const size_t nr2 = ((size_t)n_reads + 2) & ~(size_t)1, tu2 = ((size_t)tu + 1) & ~(size_t)1;   // keep every sub-array 16-B aligned
-		size_t need = nr2 * 8 * 3 + tu2 * 8 + (size_t)tv * 16 + (size_t)tm * 8 + 256;
-		DBuf &pack = c->pack; if (pack.ensure(need)) return MM355_ENOMEM;
-		(void)scr;
-		int64_t *d_uo = pack.as<int64_t>(), *d_vo = d_uo + nr2, *d_mo = d_vo + nr2;
-		uint64_t *d_pu = (uint64_t*)(d_mo + nr2); mm128 *d_pa = (mm128*)(d_pu + tu2); uint64_t *d_pm = (uint64_t*)(d_pa + tv);
-		HIPCHK(hipMemcpyAsync(d_uo, uo.data(), (n_reads + 1) * 8, hipMemcpyHostToDevice, c->st));
-		HIPCHK(hipMemcpyAsync(d_vo, vo.data(), (n_reads + 1) * 8, hipMemcpyHostToDevice, c->st));
-		HIPCHK(hipMemcpyAsync(d_mo, mo_.data(), (n_reads + 1) * 8, hipMemcpyHostToDevice, c->st));
-		mm355_kt(c, KT_PACK, 0, c->st);
-		hipLaunchKernelGGL(k_pack_chains, dim3((unsigned)n_reads), dim3(256), 0, c->st, (int)n_reads, c->aoff.as<int64_t>(), c->roff.as<int64_t>(),
-		                   c->n_u.as<int32_t>(), c->n_v.as<int32_t>(), c->n_mini.as<int32_t>(), d_uo, d_vo, d_mo, c->u.as<uint64_t>(), c->a.as<mm128>(),
-		                   c->mini_pos.as<uint64_t>(), d_pu, d_pa, d_pm);
-		mm355_kt(c, KT_PACK, 1, c->st);
-		HIPCHK(hipGetLastError());
-		if (tu) HIPCHK(hipMemcpyAsync(pu, d_pu, (size_t)tu * 8, hipMemcpyDeviceToHost, c->st));
-		if (tv) HIPCHK(hipMemcpyAsync(pa, d_pa, (size_t)tv * 16, hipMemcpyDeviceToHost, c->st));
-		if (tm) HIPCHK(hipMemcpyAsync(pm, d_pm, (size_t)tm * 8, hipMemcpyDeviceToHost, c->st));
-		HIPCHK(mm355_wait_stream(c->st));
-	}
+	PackedChains pk;
+	if ((rc = mm355_fetch_chains(c, 0, 0, &pk))) return rc;
 	mm355_timers_resolve(c);   // the stream is idle here: the stage timers of the front turn into milliseconds without waiting
 	tv_pack = now_ms() - tv0; trace_add(c, "pack", tv0, now_ms()); tv0 = now_ms();
 	const double t_host0 = now_ms();
@@ -434,16 +462,10 @@ extern "C" int mm355_map_resident(mm355_ctx_t *c, const mm355_mapopt_t *mo, int 
 	struct RegGuard { std::vector<ReadState> &v; ~RegGuard() { for (ReadState &r : v) mm355_glue_release(r); } } reg_guard{rs};   // every return below frees the regions' Extra records
 	parallel_for(n_reads, nt, [&](int64_t i, int) {
 		ReadState &r = rs[i];
-		r.qlen = dl[i]; r.seq = seqs[i]; r.rep_len = hb.rep_len[i]; r.defer_extra = defer_extra; r.name_hash = mm355_read_name_hash(hb, mo->flag, i);
-		{ ProfScope pf(PF_PRE_COPY);
-		r.u.assign(pu + uo[i], pu + uo[i + 1]);
-		r.a.assign(pa + vo[i], pa + vo[i + 1]);
-		r.mini_pos.assign(pm + mo_[i], pm + mo_[i + 1]); }
-		if (r.qlen > 0) {
-			int rst = hb.rmq_state.empty()? 3 : (int)hb.rmq_state[i];   // 3 = MM355_RMQ_HOST_ALL
-			if (rst == 3) { if (rmq_chain) mm355_glue_chain_rmq(mi, mo, r); rst = -1; }   // every mg_lchain_rmq call of this read on the host
-			mm355_glue_pre_align(mi, mo, r, rst);
-		} else r.aligned = true;
+		r.seq = seqs[i]; r.defer_extra = defer_extra;
+		const int rst = mm355_seed_read(c, mo, pk, i, dl[i], r);
+		if (r.qlen > 0) mm355_glue_pre_align(mi, mo, r, rst);
+		else r.aligned = true;
 	});
 	double ms_host = now_ms() - t_host0;
 	tv_pre = now_ms() - tv0; trace_add(c, "pre", tv0, now_ms());
@@ -510,32 +532,14 @@ extern "C" int mm355_map_resident(mm355_ctx_t *c, const mm355_mapopt_t *mo, int 
 		mm355_glue_release(rs[i]);
 	});
 	tv_fin = now_ms() - th1; trace_add(c, "finish", th1, now_ms()); tv0 = now_ms();
-	mm355_hits_t *H = (mm355_hits_t*)calloc(1, sizeof(mm355_hits_t));
-	H->n_reads = n_reads;
-	H->hit_off = (int64_t*)malloc((n_reads + 1) * 8);
-	H->status = (int32_t*)malloc((n_reads > 0? n_reads : 1) * 4);
-	int64_t nh = 0, nc = 0, ns = 0;
-	for (int64_t i = 0; i < n_reads; ++i) { H->hit_off[i] = nh; H->status[i] = status[i]; nh += (int64_t)rh[i].size(); nc += (int64_t)rc_[i].size(); ns += (int64_t)rstr[i].size(); }
-	H->hit_off[n_reads] = nh; H->n_hits = nh; H->n_cigar = nc; H->n_str = ns;
-	H->hits = (mm355_hit_t*)malloc((nh > 0? nh : 1) * sizeof(mm355_hit_t));
-	H->cigar = (uint32_t*)malloc((nc > 0? nc : 1) * 4);
-	H->str = (char*)malloc(ns > 0? ns : 1);
-	if (want_tags) {
-		H->tags = (mm355_tags_t*)malloc((nh > 0? nh : 1) * sizeof(mm355_tags_t));
-		for (int64_t i = 0; i < n_reads; ++i) if (!rt[i].empty()) memcpy(H->tags + H->hit_off[i], rt[i].data(), rt[i].size() * sizeof(mm355_tags_t));
-	}
-	nh = nc = ns = 0;
+	std::vector<Mm355ReadRows> rows((size_t)n_reads);
 	for (int64_t i = 0; i < n_reads; ++i) {
-		for (mm355_hit_t h : rh[i]) {
-			h.cigar_off += nc;
-			if (h.cs_len >= 0) h.cs_off += ns;
-			if (h.md_len >= 0) h.md_off += ns;
-			H->hits[nh++] = h;
-		}
-		if (!rc_[i].empty()) memcpy(H->cigar + nc, rc_[i].data(), rc_[i].size() * 4);
-		if (!rstr[i].empty()) memcpy(H->str + ns, rstr[i].data(), rstr[i].size());
-		nc += (int64_t)rc_[i].size(); ns += (int64_t)rstr[i].size();
+		Mm355ReadRows &w = rows[i];
+		w.hits = rh[i].data(); w.n = (int64_t)rh[i].size(); if (want_tags) w.tags = rt[i].data();
+		w.cigar = rc_[i].data(); w.n_cigar = (int64_t)rc_[i].size(); w.str = rstr[i].data(); w.n_str = (int64_t)rstr[i].size();
 	}
+	mm355_hits_t *H = 0;
+	if ((rc = mm355_hits_assemble(n_reads, status.data(), rows.data(), want_tags, &H))) return rc;
 	ms_host += now_ms() - th1;
 	tv_asm = now_ms() - tv0; trace_add(c, "asm", tv0, now_ms());
 	if (verbose) fprintf(stderr, "[mm355] map_resident: front %.1f ms | pack+d2h %.1f | pre_align %.1f | align_steps %.1f | dp rounds(%d) %.1f (kernel %.1f) | extra %.1f | finish %.1f | assemble %.1f | total %.1f\n",
@@ -556,10 +560,4 @@ extern "C" int mm355_map_resident(mm355_ctx_t *c, const mm355_mapopt_t *mo, int 
 		trace_add(c, "teardown", td, now_ms());
 	}
 	return 0;
-}
-
-extern "C" void mm355_free_hits(mm355_hits_t *h)
-{
-	if (h == 0) return;
-	free(h->hit_off); free(h->status); free(h->hits); free(h->cigar); free(h->str); free(h->tags); free(h);
 }

@@ -92,7 +92,7 @@ struct mm355_ctx {
 	DBuf mz, mz_tmp, n_mz, sn, sv, sflt, hl, soff, n_a, rep_len, n_mini, mini_pos, counters, err;
 	DBuf aoff, a, f, p, v, z, t8, vi, b, wk, u, u2, n_u, n_v;
 	// dp buffers
-	DBuf dp_jobs, dp_res, dp_q, dp_t, dp_bt, dp_cig, dp_work, dp_H, dp_dense, dp_gather, pack;
+	DBuf dp_jobs, dp_res, dp_q, dp_t, dp_bt, dp_cig, dp_work, dp_H, dp_dense, dp_gather, pack; HBuf h_pack;   // pack / h_pack: mm355_fetch_chains (tables + packed arrays on the device, the tables pinned)
 	DBuf dp_bt2, dp_fail; HBuf h_fail;      // band kernels: direction matrices of the problems that are run again on the full matrix, their list
 	HBuf h_res, h_cig, h_pu, h_pa, h_pm, h_seq;
 	HBuf h_tasks;                          // whole-array tasks of the literal anchor sort (pinned)
@@ -104,7 +104,7 @@ struct mm355_ctx {
 	DBuf rq;       // per-read query codes fwd|rev
 	DBuf rmq_list, rmq_flag; HBuf h_rmq;   // device mg_lchain_rmq: listed reads, per-read state
 	DBuf x_jobs, x_cig, x_cs, x_out, x_dense; HBuf h_xjobs, h_xcig, h_xout, h_xcs;   // k_extra (mm_update_extra's walk + cs on the device)
-	DBuf logt, regs_scr, regs_in, regs_sel; HBuf h_regs_in, h_regs_out, h_regs_sel;  // chain-only region stage (mm355_regs.hip): host-logf table, scratch + rows, read tables
+	DBuf logt, regs_scr, regs_in; HBuf h_regs_in, h_regs_out;  // chain-only region stage (mm355_regs.hip): host-logf table, scratch + rows, read tables
 	bool logt_ok = false;
 	mm355_stats_t stats;
 	hipEvent_t ev0 = 0, ev1 = 0;
@@ -143,6 +143,20 @@ int mm355_run_rmq(mm355_ctx *c, const mm355_mapopt_t *mo, const DevParams &pr); 
 // chain-only tail of a batch (mo->flag without MM_F_CIGAR), after mm355_run_rmq: regions, MAPQ and hit records on the device (k_regs), the
 // reads it does not take on the host; qlen[i] = 0 for reads that are not mapped (empty, longer than max_qlen)
 int mm355_map_chain_only(mm355_ctx *c, const mm355_mapopt_t *mo, const std::vector<int32_t> &qlen, int flags, mm355_hits_t **out);
+
+// The chains of a batch on the host: u[], the chained anchors and mini_pos[] of the fetched reads, packed on the device (k_pack_chains) and
+// copied into h_pu / h_pa / h_pm (valid until the next fetch).  Fetched read j is read sel[j] of the batch (sel == 0: read j); its entries
+// are pu[uo[j] .. uo[j + 1]), pa[vo[j] ..), pm[mo[j] ..).
+struct PackedChains {
+	int64_t n = 0; const int32_t *sel = 0; const int64_t *uo = 0, *vo = 0, *mo = 0;
+	const uint64_t *pu = 0; const mm128 *pa = 0; const uint64_t *pm = 0;
+};
+// sel: n_sel ascending read indices, or null for all reads.  One H2D copy (the tables), one launch, three D2H copies, one wait; nothing for no reads.
+int mm355_fetch_chains(mm355_ctx *c, const int32_t *sel, int64_t n_sel, PackedChains *out);
+// Seeds the ReadState of fetched read j (qlen: 0 for a read that is not mapped); returns the RMQ state for mm355_glue_pre_align /
+// mm355_glue_regions: a read the device stage left alone (MM355_RMQ_HOST_ALL, or no stage) is chained here under MM_F_RMQ and goes on as -1.
+struct ReadState;
+int mm355_seed_read(const mm355_ctx *c, const mm355_mapopt_t *mo, const PackedChains &pk, int64_t j, int32_t qlen, ReadState &r);
 
 // time one launch group on the context's stream with HIP events (the stream the kernels are launched on)
 // Stage timers.  EvTimer records a pair of events around the launches of a stage and does NOT synchronise: the pairs are turned into

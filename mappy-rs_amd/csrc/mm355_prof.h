@@ -9,8 +9,8 @@ struct ProfThread { uint64_t tsc[PF_N], cnt[PF_N]; ProfThread *next; };
 extern bool g_prof_on;
 ProfThread *mm355_prof_thread();   // registers the calling thread on first use
 struct ProfScope {
-	int id; uint64_t t0;
-	explicit ProfScope(int id_) : id(id_), t0(0) { if (g_prof_on) t0 = __rdtsc(); }
-	~ProfScope() { if (g_prof_on) { ProfThread *p = mm355_prof_thread(); p->tsc[id] += __rdtsc() - t0; ++p->cnt[id]; } }
+	int id; uint64_t t0; bool on;   // on_ = false: a scope that counts nothing (code shared with a path that is not profiled)
+	explicit ProfScope(int id_, bool on_ = true) : id(id_), t0(0), on(on_ && g_prof_on) { if (on) t0 = __rdtsc(); }
+	~ProfScope() { if (on) { ProfThread *p = mm355_prof_thread(); p->tsc[id] += __rdtsc() - t0; ++p->cnt[id]; } }
 };
 void mm355_prof_dump(int64_t n_reads);

@@ -329,7 +329,10 @@ MM_HD bool mm355r_set_mapq(int n, Mm355Reg *r, int min_chain_sc, int rep_len, co
 	return true;
 }
 
-MM_HD void mm355r_hit(const Mm355Reg *r, uint32_t mapq, const uint32_t *seq_len, mm355_hit_t *h)
+// The row writers of every path: R is Mm355Reg here and in k_regs, mm355_glue.cpp's Reg on the host (same field names).  The CIGAR path
+// adds its Extra fields and the inv / split bits on top.
+template <typename R>
+MM_HD void mm355r_hit(const R *r, uint32_t mapq, const uint32_t *seq_len, mm355_hit_t *h)
 {
 	memset(h, 0, sizeof(*h));
 	h->query_start = r->qs; h->query_end = r->qe; h->strand = r->rev? -1 : 1; h->rid = r->rid;
@@ -340,7 +343,8 @@ MM_HD void mm355r_hit(const Mm355Reg *r, uint32_t mapq, const uint32_t *seq_len,
 }
 
 // the tags row of a chain-only hit (MM355_OUT_TAGS): no CIGAR, so no n_ambi / gap counts; no inversion or split regions before extension
-MM_HD void mm355r_tags(const Mm355Reg *r, int32_t rep_len, mm355_tags_t *t)
+template <typename R>
+MM_HD void mm355r_tags(const R *r, int32_t rep_len, mm355_tags_t *t)
 {
 	memset(t, 0, sizeof(*t));
 	t->score = r->score; t->div = r->div; t->rep_len = rep_len;

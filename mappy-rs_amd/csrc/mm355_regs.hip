@@ -12,6 +12,7 @@
 #include "mm355_rmq.h"
 #include "mm355_glue.h"
 #include "mm355_regs.h"
+#include "mm355_hits.h"
 
 #define REGS_LOGT_N (1 << 22)     // logf(1 .. 2^22 - 1): chain scores of reads up to a few Mb (a chain scores at most about its query span)
 
@@ -50,20 +51,6 @@ __global__ __launch_bounds__(64) void k_regs_tags(K_REGS_ARGS, mm355_tags_t *tag
 }
 #undef K_REGS_ARGS
 
-// u[], chained anchors and mini_pos[] of the listed reads into three dense arrays (k_pack_chains for a subset)
-__global__ __launch_bounds__(256) void k_pack_sel(int n_sel, const int32_t *sel, const int64_t *aoff, const int64_t *roff, const int32_t *n_u,
-                                                  const int32_t *n_v, const int32_t *n_mini, const int64_t *uo, const int64_t *vo, const int64_t *mo,
-                                                  const uint64_t *u, const mm128 *a, const uint64_t *mini_pos, uint64_t *pu, mm128 *pa, uint64_t *pm)
-{
-	const int j = blockIdx.x;
-	if (j >= n_sel) return;
-	const int r = sel[j];
-	const int64_t ao = aoff[r], ro = roff[r];
-	for (int i = threadIdx.x; i < n_u[r]; i += 256) pu[uo[j] + i] = u[ao + i];
-	for (int i = threadIdx.x; i < n_v[r]; i += 256) pa[vo[j] + i] = a[ao + i];
-	for (int i = threadIdx.x; i < n_mini[r]; i += 256) pm[mo[j] + i] = mini_pos[ro + i];
-}
-
 static const std::vector<float> &host_logt()
 {   // the host's logf of every table index, once per process (the values mm_set_mapq computes on the host)
 	static std::vector<float> t;
@@ -81,7 +68,6 @@ int mm355_map_chain_only(mm355_ctx *c, const mm355_mapopt_t *mo, const std::vect
 	const mm355_index *mi = c->mi;
 	HostBatch &hb = c->hb;
 	const int64_t n_reads = hb.n_reads;
-	const bool rmq_chain = (mo->flag & MMF_RMQ) != 0;
 	const bool all_host = [] { const char *e = getenv("MM355_REGS_HOST"); return e && atoi(e) != 0; }();   // (read per call: the tests switch it)
 	// test hook: only the first n entries of the logf table count, so that reads with larger chain scores take the defer path
 	const int32_t n_logt = [] { const char *e = getenv("MM355_REGS_LOGT_N"); const long v = e? atol(e) : 0; return v > 1 && v < REGS_LOGT_N? (int32_t)v : (int32_t)REGS_LOGT_N; }();
@@ -143,76 +129,28 @@ int mm355_map_chain_only(mm355_ctx *c, const mm355_mapopt_t *mo, const std::vect
 	std::vector<std::vector<mm355_hit_t>> hh((size_t)n_sel);
 	std::vector<std::vector<mm355_tags_t>> ht(want_tags? (size_t)n_sel : 0);
 	if (n_sel > 0) {
-		std::vector<int64_t> offs((size_t)(n_sel + 1) * 3);
-		int64_t *uo = offs.data(), *vo = uo + n_sel + 1, *mo_ = vo + n_sel + 1;
-		int64_t tu = 0, tv = 0, tm = 0;
-		for (int64_t j = 0; j < n_sel; ++j) { const int r = sel[j]; uo[j] = tu; vo[j] = tv; mo_[j] = tm; tu += hb.n_u[r]; tv += hb.n_v[r]; tm += hb.n_mini[r]; }
-		uo[n_sel] = tu; vo[n_sel] = tv; mo_[n_sel] = tm;
-		if (c->h_pu.ensure((size_t)(tu + 1) * 8) || c->h_pm.ensure((size_t)(tm + 1) * 8) || c->h_pa.ensure((size_t)(tv + 1) * 16)) return MM355_ENOMEM;
-		uint64_t *pu = (uint64_t*)c->h_pu.p, *pm = (uint64_t*)c->h_pm.p; mm128 *pa = (mm128*)c->h_pa.p;
-		const size_t b_sel = al256((size_t)n_sel * 4), b_off = al256(offs.size() * 8);
-		const size_t b_u = al256((size_t)tu * 8), b_a = al256((size_t)tv * 16), b_m = al256((size_t)tm * 8);
-		if (c->regs_sel.ensure(b_sel + b_off + b_u + b_a + b_m + 256) || c->h_regs_sel.ensure(b_sel + b_off)) return MM355_ENOMEM;
-		char *d = c->regs_sel.as<char>(), *hs = (char*)c->h_regs_sel.p;
-		memcpy(hs, sel.data(), (size_t)n_sel * 4);
-		memcpy(hs + b_sel, offs.data(), offs.size() * 8);
-		HIPCHK(hipMemcpyAsync(d, hs, b_sel + offs.size() * 8, hipMemcpyHostToDevice, c->st));
-		const int64_t *d_off = (const int64_t*)(d + b_sel);
-		uint64_t *d_pu = (uint64_t*)(d + b_sel + b_off); mm128 *d_pa = (mm128*)(d + b_sel + b_off + b_u); uint64_t *d_pm = (uint64_t*)(d + b_sel + b_off + b_u + b_a);
-		mm355_kt(c, KT_PACK, 0, c->st);
-		hipLaunchKernelGGL(k_pack_sel, dim3((unsigned)n_sel), dim3(256), 0, c->st, (int)n_sel, (const int32_t*)d, c->aoff.as<int64_t>(), c->roff.as<int64_t>(),
-		                   c->n_u.as<int32_t>(), c->n_v.as<int32_t>(), c->n_mini.as<int32_t>(), d_off, d_off + n_sel + 1, d_off + 2 * (n_sel + 1),
-		                   c->u.as<uint64_t>(), c->a.as<mm128>(), c->mini_pos.as<uint64_t>(), d_pu, d_pa, d_pm);
-		mm355_kt(c, KT_PACK, 1, c->st);
-		HIPCHK(hipGetLastError());
-		if (tu) HIPCHK(hipMemcpyAsync(pu, d_pu, (size_t)tu * 8, hipMemcpyDeviceToHost, c->st));
-		if (tv) HIPCHK(hipMemcpyAsync(pa, d_pa, (size_t)tv * 16, hipMemcpyDeviceToHost, c->st));
-		if (tm) HIPCHK(hipMemcpyAsync(pm, d_pm, (size_t)tm * 8, hipMemcpyDeviceToHost, c->st));
-		HIPCHK(mm355_wait_stream(c->st));
+		PackedChains pk;
+		const int rc = mm355_fetch_chains(c, sel.data(), n_sel, &pk);
+		if (rc) return rc;
 		auto one = [&](int64_t j) {
-			const int r = sel[j];
 			ReadState rs;
-			rs.qlen = qlen[r]; rs.rep_len = hb.rep_len[r]; rs.name_hash = mm355_read_name_hash(hb, mo->flag, r);
-			rs.u.assign(pu + uo[j], pu + uo[j + 1]);
-			rs.a.assign(pa + vo[j], pa + vo[j + 1]);
-			rs.mini_pos.assign(pm + mo_[j], pm + mo_[j + 1]);
-			int rst = hb.rmq_state.empty()? MM355_RMQ_HOST_ALL : (int)hb.rmq_state[r];
-			if (rst == MM355_RMQ_HOST_ALL) { if (rmq_chain) mm355_glue_chain_rmq(mi, mo, rs); rst = -1; }   // every mg_lchain_rmq call of this read on the host
+			const int rst = mm355_seed_read(c, mo, pk, j, qlen[sel[j]], rs);
 			mm355_glue_regions(mi, mo, rs, rst);
 			mm355_glue_chain_finish(mi, mo, rs, hh[j], want_tags? &ht[j] : 0);
 		};
 		if (mm355_parallel_hook) mm355_parallel_hook(n_sel, one);
 		else for (int64_t j = 0; j < n_sel; ++j) one(j);
 	}
-	// the batch result, in read order
-	mm355_hits_t *H = (mm355_hits_t*)calloc(1, sizeof(mm355_hits_t));
-	if (H == 0) return MM355_ENOMEM;
-	H->n_reads = n_reads;
-	H->hit_off = (int64_t*)malloc((n_reads + 1) * 8);
-	H->status = (int32_t*)malloc((n_reads > 0? n_reads : 1) * 4);
-	int64_t nh = 0, n_dev = 0;
+	// the batch result, in read order: a read's rows are its host vector, or its span of the device's row buffer
+	std::vector<Mm355ReadRows> rows((size_t)n_reads);
+	int64_t n_dev = 0;
 	for (int64_t i = 0, j = 0; i < n_reads; ++i) {
-		H->hit_off[i] = nh; H->status[i] = hb.status[i];
-		if (j < n_sel && sel[j] == i) nh += (int64_t)hh[j++].size();
-		else if (rr[i].run) { nh += h_cnt[i]; ++n_dev; }
+		Mm355ReadRows &w = rows[i];
+		if (j < n_sel && sel[j] == i) { w.hits = hh[j].data(); w.n = (int64_t)hh[j].size(); if (want_tags) w.tags = ht[j].data(); ++j; }
+		else if (rr[i].run) { w.hits = h_rows + rr[i].hoff; w.n = h_cnt[i]; if (want_tags) w.tags = h_tags + rr[i].hoff; ++n_dev; }
 	}
-	H->hit_off[n_reads] = nh; H->n_hits = nh; H->n_cigar = 0; H->n_str = 0;
-	H->hits = (mm355_hit_t*)malloc((nh > 0? nh : 1) * sizeof(mm355_hit_t));
-	H->cigar = (uint32_t*)malloc(4);
-	H->str = (char*)malloc(1);
-	if (want_tags) H->tags = (mm355_tags_t*)malloc((nh > 0? nh : 1) * sizeof(mm355_tags_t));
-	if (!H->hit_off || !H->status || !H->hits || !H->cigar || !H->str || (want_tags && !H->tags)) { mm355_free_hits(H); return MM355_ENOMEM; }
-	for (int64_t i = 0, j = 0; i < n_reads; ++i) {
-		mm355_hit_t *dst = H->hits + H->hit_off[i];
-		if (j < n_sel && sel[j] == i) { if (!hh[j].empty()) memcpy(dst, hh[j].data(), hh[j].size() * sizeof(mm355_hit_t)); ++j; }
-		else if (rr[i].run && h_cnt[i] > 0) memcpy(dst, h_rows + rr[i].hoff, (size_t)h_cnt[i] * sizeof(mm355_hit_t));
-	}
-	if (want_tags) for (int64_t i = 0, j = 0; i < n_reads; ++i) {   // the same merge for the tags rows
-		mm355_tags_t *dst = H->tags + H->hit_off[i];
-		if (j < n_sel && sel[j] == i) { if (!ht[j].empty()) memcpy(dst, ht[j].data(), ht[j].size() * sizeof(mm355_tags_t)); ++j; }
-		else if (rr[i].run && h_cnt[i] > 0) memcpy(dst, h_tags + rr[i].hoff, (size_t)h_cnt[i] * sizeof(mm355_tags_t));
-	}
+	const int rc = mm355_hits_assemble(n_reads, hb.status.data(), rows.data(), want_tags, out);
+	if (rc) return rc;
 	c->stats.n_regs_dev = n_dev; c->stats.n_regs_host = n_sel;
-	*out = H;
 	return 0;
 }

@@ -42,12 +42,11 @@ RESULT_CHANNEL_CAP = 70000
 
 _HIT_FIELDS = [k for k, _t in _ffi.Hit._fields_]
 _F = {k: i for i, k in enumerate(_HIT_FIELDS)}
-_HIT_DTYPE = np.dtype([(k, np.dtype(t)) for k, t in _ffi.Hit._fields_], align=True)
+_HIT_DTYPE, _TAG_DTYPE = _ffi._HIT_DTYPE, _ffi._TAG_DTYPE
 (_QS, _QE, _ST, _RID, _TL, _TS, _TE, _ML, _BL, _MQ, _PR, _NM, _NC, _CO, _CSO, _CSL, _MDO, _MDL) = (_F[k] for k in (
     "query_start", "query_end", "strand", "rid", "target_len", "target_start", "target_end", "match_len", "block_len", "mapq",
     "is_primary", "NM", "n_cigar", "cigar_off", "cs_off", "cs_len", "md_off", "md_len"))
 # a record mapped with tags=True: the row of the mm355_tags_t array stands behind the hit row in the same tuple
-_TAG_DTYPE = np.dtype([(k, np.dtype(t)) for k, t in _ffi.Tags._fields_], align=True)
 _T0 = len(_HIT_FIELDS)
 _TAG_HIT = tuple(_F[k] for k in ("subsc", "cnt", "dp_max", "dp_score"))
 # what a record keeps of its tags (view: built on access, detached: _own[15]):
@@ -237,27 +236,18 @@ class Mapping:
 
 
 def _batch_to_mappings(hp, n_reads, names, chain_only=False):
-    """all hits of one mm355_hits_t -> list (per read) of list[Mapping] or RuntimeError.  One bulk copy per array (hit rows, CIGAR words,
-    string arena); every Mapping is a view of its row (fields, cs / MD strings and the CIGAR list are produced on access).  chain_only: the batch
-    was mapped without MM_F_CIGAR (no CIGAR words; the records print no cg:Z: field)."""
-    h = hp.contents
-    nh = int(h.n_hits)
-    off = np.ctypeslib.as_array(h.hit_off, shape=(n_reads + 1,)).tolist()
-    status = np.ctypeslib.as_array(h.status, shape=(max(n_reads, 1),))
-    empty = np.flatnonzero(status[:n_reads] == _ffi.MM355_EEMPTY).tolist() if n_reads else []
-    if nh:
-        assert _HIT_DTYPE.itemsize == C.sizeof(_ffi.Hit)
-        rows = np.frombuffer(C.string_at(h.hits, nh * C.sizeof(_ffi.Hit)), dtype=_HIT_DTYPE).tolist()
-        # a chain-only batch has hits but no CIGAR words: the arena may be NULL or empty
-        n_cig = int(h.n_cigar)
-        cig = np.ctypeslib.as_array(h.cigar, shape=(n_cig,)).copy() if n_cig > 0 and h.cigar else np.zeros(0, np.uint32)
-        sbuf = C.string_at(h.str, int(h.n_str)) if h.n_str else b""
-        has_tags = bool(h.tags)
+    """all hits of one mm355_hits_t (a pointer to it, or its _ffi.HitsView) -> list (per read) of list[Mapping] or RuntimeError.  One bulk copy
+    per array (hit rows, CIGAR words, string arena); every Mapping is a view of its row (fields, cs / MD strings and the CIGAR list are produced
+    on access).  chain_only: the batch was mapped without MM_F_CIGAR (no CIGAR words; the records print no cg:Z: field)."""
+    v = hp if isinstance(hp, _ffi.HitsView) else _ffi.read_hits(hp, n_reads)
+    off = v.off.tolist()
+    empty = np.flatnonzero(v.status == _ffi.MM355_EEMPTY).tolist()
+    if len(v.hits):
+        rows = v.hits.tolist()
+        has_tags = v.tags is not None
         if has_tags:    # the tags row of a hit goes behind its hit row
-            assert _TAG_DTYPE.itemsize == C.sizeof(_ffi.Tags)
-            trows = np.frombuffer(C.string_at(h.tags, nh * C.sizeof(_ffi.Tags)), dtype=_TAG_DTYPE).tolist()
-            rows = [r + t for r, t in zip(rows, trows)]
-        B = _HitBatch(cig, sbuf, names, chain_only, has_tags)
+            rows = [r + t for r, t in zip(rows, v.tags.tolist())]
+        B = _HitBatch(v.cigar, v.str, names, chain_only, has_tags)
         view = Mapping._view
         ms = [view(B, r) for r in rows]
         out = [ms[off[i]:off[i + 1]] for i in range(n_reads)]
@@ -575,24 +565,15 @@ class Aligner:
         """one mm355_map_batch call; returns list of list[Mapping].  ctx: a pipeline worker's own context (no lock needed).
         names: query names (str or None per read); None or all None = the unnamed call"""
         L = self._L
-        arr, lens, keep = _ffi.pack_reads(seqs)
-        hp = C.POINTER(_ffi.Hits)()
-        narr = _ffi.pack_names(names)
-        if narr is None:
-            call = lambda c: L.mm355_map_batch(c, C.byref(self._mo), len(seqs), arr, lens, flags, C.byref(hp))
-        else:
-            call = lambda c: L.mm355_map_batch_named(c, C.byref(self._mo), len(seqs), arr, lens, narr, flags, C.byref(hp))
+        packed, narr = _ffi.pack_reads(seqs), _ffi.pack_names(names)
         if ctx is None:
             with self._lock:
-                rc = call(self._context())
+                rc, hp = _ffi.call_map(L, self._context(), self._mo, packed, flags, narr)
         else:
-            rc = call(ctx)
+            rc, hp = _ffi.call_map(L, ctx, self._mo, packed, flags, narr)
         if rc != 0:
             raise RuntimeError(L.mm355_strerror(rc).decode())
-        try:
-            return _batch_to_mappings(hp, len(seqs), self._names(), chain_only=not self._mo.flag & 4)
-        finally:
-            L.mm355_free_hits(hp)
+        return _batch_to_mappings(_ffi.take_hits(L, hp, len(seqs)), len(seqs), self._names(), chain_only=not self._mo.flag & 4)
 
     def _names(self):
         if self._name_cache is None:

@@ -5,6 +5,7 @@ INTEGRATION.md); here the host language above the C-ABI is Python because the im
 Rust toolchain.  The library is built in-tree (mappy-rs_amd/csrc/libmm355.so) and must be
 present: there is no fallback of any kind.
 """
+import collections
 import ctypes as C
 import os
 
@@ -178,8 +179,11 @@ _utf8.restype = C.c_void_p
 _utf8.argtypes = [C.py_object]
 
 
+PackedReads = collections.namedtuple("PackedReads", "arr lens keep")
+
+
 def pack_reads(seqs):
-    """list of str/bytes -> (char** array, int32 lens array, keepalive).  Plain ASCII str -- every read a sequencer or a FASTQ parser hands
+    """list of str/bytes -> PackedReads(char** array, int32 lens array, keepalive).  Plain ASCII str -- every read a sequencer or a FASTQ parser hands
     over -- is passed by the address of its own buffer: `s.encode()` costs 5-6 us per 8 kb read under the GIL (an allocation and a copy),
     more than everything else the interpreter does for a read."""
     n = len(seqs)
@@ -188,12 +192,12 @@ def pack_reads(seqs):
         ptrs = np.fromiter(map(_utf8, seqs), dtype=np.uint64, count=n)
         lens = np.fromiter(map(len, seqs), dtype=np.int32, count=n)
         # (ctypes arrays over the numpy buffers: same types as the copying path below; they hold the buffers, `seqs` holds the bytes)
-        return (C.c_char_p * n).from_buffer(ptrs), (C.c_int32 * n).from_buffer(lens), seqs
+        return PackedReads((C.c_char_p * n).from_buffer(ptrs), (C.c_int32 * n).from_buffer(lens), seqs)
     bs = [s if isinstance(s, (bytes, bytearray)) else s.encode() for s in seqs]
     n = len(bs)
     arr = (C.c_char_p * n)(*bs)
     lens = (C.c_int32 * n)(*[len(b) for b in bs])
-    return arr, lens, bs
+    return PackedReads(arr, lens, bs)
 
 
 def pack_names(names):
@@ -202,6 +206,74 @@ def pack_names(names):
         return None
     bs = [None if nm is None else nm if isinstance(nm, (bytes, bytearray)) else nm.encode("utf-8") for nm in names]
     return (C.c_char_p * len(bs))(*bs)
+
+
+_HIT_DTYPE = np.dtype([(k, np.dtype(t)) for k, t in Hit._fields_], align=True)       # numpy views of the C-ABI rows
+_TAG_DTYPE = np.dtype([(k, np.dtype(t)) for k, t in Tags._fields_], align=True)
+assert _HIT_DTYPE.itemsize == C.sizeof(Hit) and _TAG_DTYPE.itemsize == C.sizeof(Tags)
+# one mm355_hits_t, copied out: off (n_reads + 1) and status (n_reads) arrays, hits a structured array of _HIT_DTYPE, cigar uint32 words
+# (may be empty), str the string arena as bytes, tags a structured array of _TAG_DTYPE or None when the library sent none
+HitsView = collections.namedtuple("HitsView", "off status hits cigar str tags")
+
+
+def read_hits(hp, n_reads):
+    """POINTER(Hits) -> HitsView: one bulk copy per array, nothing per hit, and no array is read whose count is zero (no reads, no hits, the
+    CIGAR arena of a chain-only batch).  Nothing of the view points into the record."""
+    h = hp.contents
+    nh, nc, ns = int(h.n_hits), int(h.n_cigar), int(h.n_str)
+    off = np.ctypeslib.as_array(h.hit_off, shape=(n_reads + 1,)).copy()
+    status = np.ctypeslib.as_array(h.status, shape=(n_reads,)).copy() if n_reads else np.zeros(0, np.int32)
+    hits = np.frombuffer(C.string_at(h.hits, nh * C.sizeof(Hit)) if nh else b"", dtype=_HIT_DTYPE)
+    cigar = np.ctypeslib.as_array(h.cigar, shape=(nc,)).copy() if nc > 0 and h.cigar else np.zeros(0, np.uint32)
+    tags = np.frombuffer(C.string_at(h.tags, nh * C.sizeof(Tags)) if nh else b"", dtype=_TAG_DTYPE) if h.tags else None
+    return HitsView(off, status, hits, cigar, C.string_at(h.str, ns) if ns > 0 else b"", tags)
+
+
+def take_hits(L, hp, n_reads):
+    """read_hits, then mm355_free_hits"""
+    try:
+        return read_hits(hp, n_reads)
+    finally:
+        L.mm355_free_hits(hp)
+
+
+def call_map(L, ctx, mo, reads, flags, names=None, entry="batch"):
+    """one mapping call -> (return code, POINTER(Hits) for take_hits).  reads: a list of str / bytes, or what pack_reads made of one (a caller
+    that times the call, or holds a lock for it, packs first); names: str / bytes / None per read, None, or what pack_names made of them.
+    entry: batch = mm355_map_batch, or mm355_map_batch_named when a read has a name (what Aligner does); named = mm355_map_batch_named always
+    (a null pointer when no read has a name); nullarr = the same with an array of null pointers; resident = mm355_batch_upload_named +
+    mm355_map_resident; current = mm355_map_resident on the batch that is resident already (reads and names are not looked at)"""
+    hp = C.POINTER(Hits)()
+    if entry == "current":
+        return L.mm355_map_resident(ctx, C.byref(mo), flags, C.byref(hp)), hp
+    arr, lens, keep = reads if isinstance(reads, PackedReads) else pack_reads(reads)
+    n, narr = len(keep), names if isinstance(names, C.Array) else pack_names(names)
+    if entry == "batch" and narr is None:
+        rc = L.mm355_map_batch(ctx, C.byref(mo), n, arr, lens, flags, C.byref(hp))
+    elif entry in ("batch", "named", "nullarr"):
+        rc = L.mm355_map_batch_named(ctx, C.byref(mo), n, arr, lens, (C.c_char_p * n)() if entry == "nullarr" else narr, flags, C.byref(hp))
+    else:
+        assert entry == "resident", entry
+        rc = L.mm355_batch_upload_named(ctx, n, arr, lens, narr)
+        if rc == 0:
+            rc = L.mm355_map_resident(ctx, C.byref(mo), flags, C.byref(hp))
+    return rc, hp
+
+
+def map_raw(L, ctx, mo, reads, flags, names=None, entry="batch", raise_on_error=True):
+    """call_map + take_hits: the HitsView of one call.  A failed call raises Mm355Error; with raise_on_error=False the result is
+    (return code, view) instead, the view None after a failure."""
+    rc, hp = call_map(L, ctx, mo, reads, flags, names, entry)
+    if rc != 0 and raise_on_error:
+        raise Mm355Error(rc)
+    v = take_hits(L, hp, int(hp.contents.n_reads)) if rc == 0 else None
+    return v if raise_on_error else (rc, v)
+
+
+def get_stats(L, ctx):
+    st = Stats()
+    check(L.mm355_get_stats(ctx, C.byref(st)))
+    return st
 
 
 class StageRunner:
@@ -225,9 +297,7 @@ class StageRunner:
             pass
 
     def stats(self):
-        st = Stats()
-        check(self.L.mm355_get_stats(self.ctx, C.byref(st)))
-        return st
+        return get_stats(self.L, self.ctx)
 
     def sketch(self, seqs):
         arr, lens, keep = pack_reads(seqs)

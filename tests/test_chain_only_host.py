@@ -6,16 +6,14 @@ oracle's sorted anchors and final chains of each read, must give the oracle's re
 for field, over the long-read presets and the flags that change the region logic.  GPU side: tests/test_gpu_chain_only.py."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import oracle as O
+import _capi
 import synthdata as S
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(HERE, "..", "mappy-rs_amd", "csrc")
 
 ALL_CHAINS, HARD_MLEVEL, FOR_ONLY, REV_ONLY = 0x800000, 0x20000000, 0x100000, 0x200000
 FIELDS = ("query_start", "query_end", "strand", "rid", "target_len", "target_start", "target_end", "match_len", "block_len", "mapq",
@@ -24,12 +22,7 @@ FIELDS = ("query_start", "query_end", "strand", "rid", "target_len", "target_sta
 
 @pytest.fixture(scope="module")
 def regs_lib(built):
-    src = os.path.join(HERE, "host_harness", "regs_host.cpp")
-    so = os.path.join(HERE, "host_harness", "libregshost.so")
-    deps = [src, os.path.join(CSRC, "mm355_regs.h"), os.path.join(CSRC, "mm355_core.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-w", "-ffp-contract=off", "-o", so, src])
-    L = C.CDLL(so)
+    L = _capi.build_harness("regs_host", ["-w", "-ffp-contract=off"], ["mm355_regs.h", "mm355_core.h"])
     L.regs_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_int32,
                             C.c_void_p, C.c_void_p]
     L.regs_host.restype = C.c_int

@@ -3,25 +3,18 @@ sufficiency it PROVES while running, plain and homopolymer-compressed) compiled 
 and held against the oracle's sequential U:sketch.c::mm_sketch on the inputs that stress the proof -- the CPU counterpart of
 tests/test_gpu_stages.py::test_chunked_sketch_adversarial and tests/test_gpu_hpc.py::test_hpc_chunked_sketch_parity (same header, no GPU)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import oracle as O
+import _capi
 import synthdata as S
-
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @pytest.fixture(scope="module")
 def chunk_lib(built):
-    src = os.path.join(HERE, "host_harness", "chunk_sketch_host.cpp")
-    so = os.path.join(HERE, "host_harness", "libchunkhost.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(src), os.path.getmtime(os.path.join(HERE, "..", "mappy-rs_amd", "csrc", "mm355_sketch.h"))):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-w", "-o", so, src])
-    L = C.CDLL(so)
+    L = _capi.build_harness("chunk_sketch_host", ["-w"], ["mm355_sketch.h"])
     L.chunk_sketch_host.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.chunk_sketch_host.restype = C.c_int
     return L

@@ -2,7 +2,6 @@
 (mappy-rs_amd/csrc/mm355_regs.hip) and its host path give the oracle's records of the same reads mapped without MM_F_CIGAR, every field of
 the C-ABI row; the host switch gives the same rows; a read's hits do not depend on its batch; map_batch / devices work; an index without
 sequence maps.  CPU side: tests/test_chain_only_host.py."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -12,6 +11,8 @@ pytestmark = pytest.mark.gpu
 
 from oracle import oracle as O
 import synthdata as S
+import _capi
+from _capi import stats
 from test_chain_only_host import ALL_CHAINS, HARD_MLEVEL, FOR_ONLY, REV_ONLY, _inverted_genome
 
 ROW = ("query_start", "query_end", "strand", "rid", "target_len", "target_start", "target_end", "match_len", "block_len", "mapq",
@@ -20,19 +21,9 @@ ROW = ("query_start", "query_end", "strand", "rid", "target_len", "target_start"
 
 def map_rows(al, reads):
     """reads through mm355_map_batch on the Aligner's context: per read, a list of row tuples (ROW fields) or the status code"""
-    from mappy_rs import _ffi
-    import mappy_rs
-    L = al._L
-    arr, lens, keep = _ffi.pack_reads(reads)
-    hp = C.POINTER(_ffi.Hits)()
-    rc = L.mm355_map_batch(al._context(), C.byref(al._mo), len(reads), arr, lens, 0, C.byref(hp))
-    assert rc == 0, L.mm355_strerror(rc)
-    h = hp.contents
-    assert h.n_cigar == 0 and h.n_str == 0
-    off = np.ctypeslib.as_array(h.hit_off, shape=(len(reads) + 1,)).copy()
-    st = np.ctypeslib.as_array(h.status, shape=(max(len(reads), 1),)).copy()
-    rows = np.frombuffer(C.string_at(h.hits, int(h.n_hits) * C.sizeof(_ffi.Hit)), dtype=mappy_rs._HIT_DTYPE).copy()
-    L.mm355_free_hits(hp)
+    v = _capi.map_raw(al, reads, 0)
+    assert len(v.cigar) == 0 and len(v.str) == 0              # n_cigar == 0 and n_str == 0
+    off, st, rows = v.off, v.status, v.hits
     out = []
     for i in range(len(reads)):
         if st[i] != 0:
@@ -51,13 +42,6 @@ def oracle_rows(orc, rd):
 def _ffi_code(name):
     from mappy_rs import _ffi
     return getattr(_ffi, name)
-
-
-def stats(al):
-    from mappy_rs import _ffi
-    st = _ffi.Stats()
-    assert al._L.mm355_get_stats(al._context(), C.byref(st)) == 0
-    return st
 
 
 def check(al, orc, reads):
@@ -85,11 +69,7 @@ def world(built, tmp_path_factory):
 
 
 def pair(fa, preset, **kw):
-    import mappy_rs
-    al = mappy_rs.Aligner(fa, preset=preset, cigar=False, **kw)
-    orc = O.OracleAligner(fa, preset=preset, **kw)
-    orc.mo.flag &= ~4
-    return al, orc
+    return _capi.pair(fa, preset, False, **kw)
 
 
 CASES = [("map-ont", {}), ("map-hifi", {}), ("map-pb", {}), ("asm5", {}), ("asm20", {}), ("ava-ont", {}),
@@ -124,10 +104,8 @@ def test_chain_only_mapping_records(world):
     with pytest.raises(ValueError):
         al.map(rd, cs=True)
     from mappy_rs import _ffi
-    arr, lens, keep = _ffi.pack_reads([rd])
-    hp = C.POINTER(_ffi.Hits)()
     for fl in (_ffi.OUT_CS, _ffi.OUT_MD):
-        assert al._L.mm355_map_batch(al._context(), C.byref(al._mo), 1, arr, lens, fl, C.byref(hp)) == _ffi.MM355_EINVAL
+        assert _capi.map_raw(al, [rd], fl, raise_on_error=False) == (_ffi.MM355_EINVAL, None)
 
 
 def test_chain_only_edge_reads(world):

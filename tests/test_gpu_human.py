@@ -59,7 +59,7 @@ def test_full_size_human_properties(human_full, preset, seed, kw, n):
         assert mo.mid_occ > 100, mo.mid_occ                      # a GRCh38-scale occurrence threshold (383 for map-ont on this genome)
         n_hits, n_right = check_properties(L, ctx, mo, reads, truth, [0, 500, 503, n // 2, n])
         assert n_hits >= 0.95 * n and n_right >= 0.93 * n, (n_hits, n_right)
-        st = _ffi.Stats(); L.mm355_get_stats(ctx, C.byref(st))
+        st = _ffi.get_stats(L, ctx)
         if preset == "map-ont":
             assert st.n_a / st.n_reads > 2048                    # anchor-rich: the segmented-sort path
     finally:
@@ -111,12 +111,8 @@ def test_mid_scale_human_parity(human_mid, preset, seed, kw, extra):
     ctx = C.c_void_p()
     _ffi.check(L.mm355_ctx_create(idx, 0, C.byref(ctx)))
     try:
-        rarr, rlens, keep = _ffi.pack_reads(reads)
-        hp = C.POINTER(_ffi.Hits)()
-        _ffi.check(L.mm355_map_batch(ctx, C.byref(mo), len(reads), rarr, rlens, 1, C.byref(hp)))
-        got = mappy_rs._batch_to_mappings(hp, len(reads), names)
-        L.mm355_free_hits(hp)
-        st = _ffi.Stats(); L.mm355_get_stats(ctx, C.byref(st))
+        got = mappy_rs._batch_to_mappings(_ffi.map_raw(L, ctx, mo, reads, 1), len(reads), names)
+        st = _ffi.get_stats(L, ctx)
         n_hits = 0
         for i, rd in enumerate(reads):
             exp = orc.map(rd, cs=True)

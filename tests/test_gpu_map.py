@@ -12,6 +12,7 @@ pytestmark = pytest.mark.gpu
 from oracle import oracle as O
 import synthdata as S
 import _dp_problems as D
+import _capi
 
 FIELDS = ("target_name", "target_start", "target_end", "query_start", "query_end", "strand", "target_len", "match_len",
           "block_len", "mapq", "is_primary", "NM", "cs", "MD")
@@ -381,8 +382,7 @@ def test_stats_counters(ont):
     al = ont["al"]
     al._map_many(reads, 1)
     from mappy_rs import _ffi
-    st = _ffi.Stats()
-    _ffi.check(al._L.mm355_get_stats(al._ctx, C.byref(st)))
+    st = _ffi.get_stats(al._L, al._ctx)
     tot = dict(n_mz=0, n_hit=0, n_a=0, n_a_multi=0)
     for rd in reads:
         ont["orc"].map(rd)
@@ -400,11 +400,11 @@ def test_round_cut_by_hbm_budget_is_counted_and_exact(ont, monkeypatch):
     reads, _ = S.make_reads(84, ont["g"], 40, n50=3000, lo=500)
     al = ont["al"]
     ref = [[rec(m) for m in ms] for ms in al._map_many(reads, 1)]
-    st = _ffi.Stats(); _ffi.check(al._L.mm355_get_stats(al._ctx, C.byref(st)))
+    st = _ffi.get_stats(al._L, al._ctx)
     assert st.n_rounds_split == 0 and st.n_ext_rounds >= 1
     monkeypatch.setenv("MM355_DP_BUDGET_MB", "1")
     cut = [[rec(m) for m in ms] for ms in al._map_many(reads, 1)]
-    _ffi.check(al._L.mm355_get_stats(al._ctx, C.byref(st)))
+    st = _ffi.get_stats(al._L, al._ctx)
     assert st.n_rounds_split >= 1, st.n_rounds_split
     assert cut == ref
 
@@ -442,28 +442,18 @@ def test_resident_batch_slots(ont):
             _ffi.check(L.mm355_batch_select(ctx, slot))
             _ffi.check(L.mm355_batch_upload(ctx, len(keep), rarr, rlens))
 
-        def hits_of(hp, n):
-            h = hp.contents
-            off = np.ctypeslib.as_array(h.hit_off, shape=(n + 1,)).copy()
-            rec = [(h.hits[k].rid, h.hits[k].target_start, h.hits[k].target_end, h.hits[k].query_start, h.hits[k].query_end, h.hits[k].strand,
-                    h.hits[k].mapq, h.hits[k].n_cigar, h.hits[k].NM) for k in range(int(h.n_hits))]
-            L.mm355_free_hits(hp)
-            return list(off), rec
+        def hits_of(v):
+            return v.off.tolist(), [tuple(int(h[k]) for k in ("rid", "target_start", "target_end", "query_start", "query_end", "strand", "mapq",
+                                                               "n_cigar", "NM")) for h in v.hits]
 
-        expect = []
         ctx2 = C.c_void_p()
         _ffi.check(L.mm355_ctx_create(al._idx, 0, C.byref(ctx2)))
-        for rarr, rlens, keep in packs:   # reference: a fresh context, one-shot upload + map
-            hp = C.POINTER(_ffi.Hits)()
-            _ffi.check(L.mm355_map_batch(ctx2, C.byref(al._mo), len(keep), rarr, rlens, 1, C.byref(hp)))
-            expect.append(hits_of(hp, len(keep)))
+        expect = [hits_of(_ffi.map_raw(L, ctx2, al._mo, rd, 1)) for rd in (ra, rb)]   # reference: a fresh context, one-shot upload + map
         L.mm355_ctx_destroy(ctx2)
         for order in ((0, 1), (1, 0, 1)):
             for slot in order:
                 _ffi.check(L.mm355_batch_select(ctx, slot))
-                hp = C.POINTER(_ffi.Hits)()
-                _ffi.check(L.mm355_map_resident(ctx, C.byref(al._mo), 1, C.byref(hp)))
-                assert hits_of(hp, len(packs[slot][2])) == expect[slot], slot
+                assert hits_of(_ffi.map_raw(L, ctx, al._mo, None, 1, entry="current")) == expect[slot], slot
         assert sum(len(e[1]) for e in expect) > 20
     finally:
         L.mm355_ctx_destroy(ctx)
@@ -564,40 +554,19 @@ def test_full_size_properties(built, tmp_path):
     _ffi.check(L.mm355_ctx_create(al._idx, 0, C.byref(ctx)))
 
     def run(sub):
-        rarr, rlens, keep = _ffi.pack_reads(sub)
-        hp = C.POINTER(_ffi.Hits)()
-        _ffi.check(L.mm355_map_batch(ctx, C.byref(al._mo), len(sub), rarr, rlens, 1, C.byref(hp)))
-        h = hp.contents
-        off = np.ctypeslib.as_array(h.hit_off, shape=(len(sub) + 1,)).copy()
-        hits = np.frombuffer(C.string_at(h.hits, int(h.n_hits) * C.sizeof(_ffi.Hit)), dtype=mappy_rs._HIT_DTYPE).copy()
-        cig = np.ctypeslib.as_array(h.cigar, shape=(max(int(h.n_cigar), 1),)).copy()
-        sbuf = C.string_at(h.str, int(h.n_str)) if h.n_str else b""
-        L.mm355_free_hits(hp)
-        return off, hits, cig, sbuf
-
-    def per_read(off, hits, cig, sbuf):
-        out = []
-        for i in range(len(off) - 1):
-            rs = []
-            for k in range(off[i], off[i + 1]):
-                x = hits[k]
-                rs.append((int(x["rid"]), int(x["target_start"]), int(x["target_end"]), int(x["query_start"]), int(x["query_end"]), int(x["strand"]),
-                           int(x["mapq"]), int(x["NM"]), cig[x["cigar_off"]:x["cigar_off"] + x["n_cigar"]].tobytes(),
-                           sbuf[x["cs_off"]:x["cs_off"] + x["cs_len"]]))
-            out.append(rs)
-        return out
+        return _capi.per_read(_ffi.map_raw(L, ctx, al._mo, sub, 1))
 
     try:
-        whole = per_read(*run(reads))
-        assert per_read(*run(reads)) == whole                                  # (2)
+        whole = run(reads)
+        assert run(reads) == whole                                  # (2)
         cuts = [0, 1000, 1003, 5000, len(reads)]
         parts = []
         for a, b in zip(cuts[:-1], cuts[1:]):
-            parts += per_read(*run(reads[a:b]))
+            parts += run(reads[a:b])
         assert parts == whole                                                  # (1)
         n_hits = n_right = 0
         for i, rs in enumerate(whole):
-            for (rid, ts, te, qs, qe, strand, mapq, nm, cg, cs) in rs:
+            for (rid, ts, te, qs, qe, strand, mapq, nm, cg, cs, _pri) in rs:
                 ops = np.frombuffer(cg, dtype=np.uint32)
                 ln, op = ops >> 4, ops & 0xf
                 assert int(ln[(op == 0) | (op == 1)].sum()) == qe - qs and int(ln[(op == 0) | (op == 2)].sum()) == te - ts   # (3)
@@ -640,12 +609,8 @@ def test_repeat_rich_genome_device_index_parity(built, tmp_path):
     ctx = C.c_void_p()
     _ffi.check(L.mm355_ctx_create(idx, 0, C.byref(ctx)))
     try:
-        rarr, rlens, keep = _ffi.pack_reads(reads)
-        hp = C.POINTER(_ffi.Hits)()
-        _ffi.check(L.mm355_map_batch(ctx, C.byref(mo), len(reads), rarr, rlens, 1, C.byref(hp)))
-        got = mappy_rs._batch_to_mappings(hp, len(reads), names)
-        L.mm355_free_hits(hp)
-        st = _ffi.Stats(); L.mm355_get_stats(ctx, C.byref(st))
+        got = mappy_rs._batch_to_mappings(_ffi.map_raw(L, ctx, mo, reads, 1), len(reads), names)
+        st = _ffi.get_stats(L, ctx)
         assert st.n_a / len(reads) > 800, "the miniature must be repeat-rich (anchors per read: %.0f)" % (st.n_a / len(reads))
         n_hits = 0
         for i in range(0, len(reads), 2):
@@ -683,12 +648,8 @@ def test_many_zdrop_splits_need_more_than_64_rounds(built, tmp_path):
     ctx = C.c_void_p()
     _ffi.check(al._L.mm355_ctx_create(al._idx, 0, C.byref(ctx)))
     try:
-        rarr, rlens, keep = _ffi.pack_reads([rd])
-        hp = C.POINTER(_ffi.Hits)()
-        _ffi.check(al._L.mm355_map_batch(ctx, C.byref(al._mo), 1, rarr, rlens, 3, C.byref(hp)))
-        got = mappy_rs._batch_to_mappings(hp, 1, al._names())[0]
-        al._L.mm355_free_hits(hp)
-        st = _ffi.Stats(); al._L.mm355_get_stats(ctx, C.byref(st))
+        got = al._map_many([rd], 3, ctx)[0]
+        st = _ffi.get_stats(al._L, ctx)
         exp = orc.map(rd, cs=True, MD=True)
         assert len(got) == len(exp) and len(exp) > 40, (len(got), len(exp))
         for m, e in zip(got, exp):
@@ -887,18 +848,10 @@ def test_more_contexts_than_the_stream_pool_holds(ont):
     al = ont["al"]
     L = al._L
     reads, _ = S.make_reads(97, ont["g"], 40, n50=4000, lo=300)
-    rarr, rlens, keep = _ffi.pack_reads(reads)
-
     def run(ctx, out, k):
-        hp = C.POINTER(_ffi.Hits)()
-        _ffi.check(L.mm355_map_batch(ctx, C.byref(al._mo), len(keep), rarr, rlens, 1, C.byref(hp)))
-        h = hp.contents
-        off = list(np.ctypeslib.as_array(h.hit_off, shape=(len(keep) + 1,)))
-        rec = [(h.hits[i].rid, h.hits[i].target_start, h.hits[i].target_end, h.hits[i].query_start, h.hits[i].query_end, h.hits[i].strand, h.hits[i].mapq,
-                h.hits[i].n_cigar, h.hits[i].NM) for i in range(int(h.n_hits))]
-        cig = list(np.ctypeslib.as_array(h.cigar, shape=(max(1, int(h.n_cigar)),))[:int(h.n_cigar)])
-        L.mm355_free_hits(hp)
-        out[k] = (off, rec, cig)
+        v = _ffi.map_raw(L, ctx, al._mo, reads, 1)
+        rec = [tuple(int(h[f]) for f in ("rid", "target_start", "target_end", "query_start", "query_end", "strand", "mapq", "n_cigar", "NM")) for h in v.hits]
+        out[k] = (v.off.tolist(), rec, v.cigar.tolist())
 
     ctxs = []
     try:

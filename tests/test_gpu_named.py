@@ -12,53 +12,23 @@ pytestmark = pytest.mark.gpu
 
 from oracle import oracle as O
 import _named_truth as T
+import _capi
+from _capi import pair, stats
 
 OUT_CS, OUT_TAGS = 1, 4
 
 
-def _call(al, reads, names, flags, entry):
-    """one mapping call -> the mm355_hits_t pointer.  entry: named (mm355_map_batch_named), old (mm355_map_batch; names must be None),
-    resident (mm355_batch_upload_named + mm355_map_resident), nullarr (named entry, an array of NULL pointers)"""
-    from mappy_rs import _ffi
-    L = al._L
-    arr, lens, keep = _ffi.pack_reads(reads)
-    n = len(reads)
-    hp = C.POINTER(_ffi.Hits)()
-    narr = _ffi.pack_names(names)
-    if entry == "old":
-        assert narr is None
-        rc = L.mm355_map_batch(al._context(), C.byref(al._mo), n, arr, lens, flags, C.byref(hp))
-    elif entry == "nullarr":
-        assert narr is None
-        rc = L.mm355_map_batch_named(al._context(), C.byref(al._mo), n, arr, lens, (C.c_char_p * n)(), flags, C.byref(hp))
-    elif entry == "resident":
-        rc = L.mm355_batch_upload_named(al._context(), n, arr, lens, narr)
-        assert rc == 0
-        rc = L.mm355_map_resident(al._context(), C.byref(al._mo), flags, C.byref(hp))
-    else:
-        rc = L.mm355_map_batch_named(al._context(), C.byref(al._mo), n, arr, lens, narr, flags, C.byref(hp))
-    assert rc == 0, L.mm355_strerror(rc)
-    return hp
-
-
 def map_named(al, reads, names, flags=OUT_TAGS, entry="named"):
-    """(per read: list of (row tuple, cigar bytes, cs bytes or None, tags tuple or None)), (raw hit rows, CIGAR words, string arena)"""
-    from mappy_rs import _ffi
-    import mappy_rs
-    hp = _call(al, reads, names, flags, entry)
-    h = hp.contents
-    nh = int(h.n_hits)
-    off = np.ctypeslib.as_array(h.hit_off, shape=(len(reads) + 1,)).copy()
-    hb = C.string_at(h.hits, nh * C.sizeof(_ffi.Hit))
-    cb = C.string_at(h.cigar, int(h.n_cigar) * 4) if h.n_cigar else b""
-    sb = C.string_at(h.str, int(h.n_str)) if h.n_str else b""
-    rows = np.frombuffer(hb, dtype=mappy_rs._HIT_DTYPE)
-    tg = np.frombuffer(C.string_at(h.tags, nh * C.sizeof(_ffi.Tags)), dtype=mappy_rs._TAG_DTYPE) if h.tags else None
-    al._L.mm355_free_hits(hp)
+    """(per read: list of (row tuple, cigar bytes, cs bytes or None, tags tuple or None)), (raw hit rows, CIGAR words, string arena).
+    entry: named (mm355_map_batch_named), batch (mm355_map_batch when names is None), resident (mm355_batch_upload_named +
+    mm355_map_resident), nullarr (named entry, an array of NULL pointers)"""
+    assert names is None or entry in ("named", "resident")
+    v = _capi.map_raw(al, reads, flags, names, entry)
+    rows, tg, cb, sb = v.hits, v.tags, v.cigar.tobytes(), v.str
     out = []
     for i in range(len(reads)):
         one = []
-        for j in range(off[i], off[i + 1]):
+        for j in range(v.off[i], v.off[i + 1]):
             r = rows[j]
             tt = None
             if tg is not None:
@@ -69,27 +39,11 @@ def map_named(al, reads, names, flags=OUT_TAGS, entry="named"):
             cs = sb[int(r["cs_off"]):int(r["cs_off"]) + int(r["cs_len"])] if int(r["cs_len"]) >= 0 else None
             one.append((tuple(int(r[k]) for k in T.ROW_FIELDS), cb[co * 4:(co + nc) * 4], cs, tt))
         out.append(one)
-    return out, (hb, cb, sb)
+    return out, (_capi.raw(v.hits), cb, sb)
 
 
 def want_rows(dicts, tags=True):
     return [(T.row_tuple(d), d["cigar"], d["cs"], T.tag_tuple(d) if tags else None) for d in dicts]
-
-
-def stats(al):
-    from mappy_rs import _ffi
-    st = _ffi.Stats()
-    assert al._L.mm355_get_stats(al._context(), C.byref(st)) == 0
-    return st
-
-
-def pair(fa, preset, cigar, **kw):
-    import mappy_rs
-    al = mappy_rs.Aligner(fa, preset=preset, cigar=cigar, **kw)
-    orc = O.OracleAligner(fa, preset=preset, **kw)
-    if not cigar:
-        orc.mo.flag &= ~4
-    return al, orc
 
 
 @pytest.fixture(scope="module")
@@ -166,7 +120,7 @@ def test_overlap_chain_only(W, preset, xf):
     names = [nm for nm, _ in W["queries"]]; seqs = [s for _, s in W["queries"]]
     tn = [nm for nm, _ in W["targets"]]
     got, _ = map_named(al, seqs, names)
-    unnamed, _ = map_named(al, seqs, None, entry="old")
+    unnamed, _ = map_named(al, seqs, None, entry="batch")
     n_rows = 0
     seen = {}
     for i, (nm, s) in enumerate(W["queries"]):
@@ -245,7 +199,7 @@ def test_unnamed_is_byte_identical(W, preset, cigar):
     al, _ = pair(W["fa"], preset, cigar)
     seqs = [s for _, s in W["queries"]]
     flags = OUT_TAGS | (OUT_CS if cigar else 0)
-    base, raw = map_named(al, seqs, None, flags, entry="old")
+    base, raw = map_named(al, seqs, None, flags, entry="batch")
     assert sum(map(len, base)) > 20
     for entry in ("named", "nullarr", "resident"):
         g, r = map_named(al, seqs, None, flags, entry=entry)
@@ -341,11 +295,7 @@ def test_device_built_index(W):
             assert np.array_equal(got[i], a) and int(rep[i]) == rep_len and int(nmp[i]) == len(mini_pos), (i, q)
             n_self += ns
         assert n_self > 100
-        arr, rl, keep = _ffi.pack_reads(seqs)
-        hp = C.POINTER(_ffi.Hits)()
-        _ffi.check(L.mm355_map_batch_named(sr.ctx, C.byref(mo), len(seqs), arr, rl, _ffi.pack_names(names), 0, C.byref(hp)))
-        off = np.ctypeslib.as_array(hp.contents.hit_off, shape=(len(seqs) + 1,)).copy()
-        L.mm355_free_hits(hp)
+        off = _ffi.map_raw(L, sr.ctx, mo, seqs, 0, names, "named").off
         assert [int(off[i + 1] - off[i]) for i in range(len(seqs))] == [len(T.compose_named(orc, s, q)[0]) for q, s in W["queries"]]
         sr.close()
     finally:

@@ -14,33 +14,20 @@ from oracle import oracle as O
 import synthdata as S
 from test_chain_only_host import ALL_CHAINS, _inverted_genome
 import _tags_truth as T
+import _capi
+from _capi import pair, stats
 
 OUT_CS, OUT_TAGS = 1, 4
 
 
 def map_raw(al, reads, flags):
     """one mm355_map_batch call: (per-read list of (hit dict, tags tuple or None), raw bytes of hits / cigar / str, whether tags came back)"""
-    from mappy_rs import _ffi
-    import mappy_rs
-    L = al._L
-    arr, lens, keep = _ffi.pack_reads(reads)
-    hp = C.POINTER(_ffi.Hits)()
-    rc = L.mm355_map_batch(al._context(), C.byref(al._mo), len(reads), arr, lens, flags, C.byref(hp))
-    assert rc == 0, L.mm355_strerror(rc)
-    h = hp.contents
-    nh = int(h.n_hits)
-    off = np.ctypeslib.as_array(h.hit_off, shape=(len(reads) + 1,)).copy()
-    hb = C.string_at(h.hits, nh * C.sizeof(_ffi.Hit))
-    cb = C.string_at(h.cigar, int(h.n_cigar) * 4) if h.n_cigar else b""
-    sb = C.string_at(h.str, int(h.n_str)) if h.n_str else b""
-    rows = np.frombuffer(hb, dtype=mappy_rs._HIT_DTYPE)
-    has_tags = bool(h.tags)
-    tg = np.frombuffer(C.string_at(h.tags, nh * C.sizeof(_ffi.Tags)), dtype=mappy_rs._TAG_DTYPE) if has_tags else None
-    L.mm355_free_hits(hp)
+    v = _capi.map_raw(al, reads, flags)
+    rows, tg, has_tags = v.hits, v.tags, v.tags is not None
     out = []
     for i in range(len(reads)):
         one = []
-        for j in range(off[i], off[i + 1]):
+        for j in range(v.off[i], v.off[i + 1]):
             hd = {k: int(rows[j][k]) for k in T.HIT_FIELDS}
             tt = None
             if has_tags:
@@ -51,18 +38,11 @@ def map_raw(al, reads, flags):
                       fl & 1, fl >> 1 & 1, fl >> 2 & 3)
             one.append((hd, tt))
         out.append(one)
-    return out, (hb, cb, sb), has_tags
+    return out, (_capi.raw(v.hits), v.cigar.tobytes(), v.str), has_tags
 
 
 def expected(orc, rd):
     return [({k: e[k] for k in T.HIT_FIELDS}, T.tags_tuple(e)) for e in T.oracle_tags(orc, rd)]
-
-
-def stats(al):
-    from mappy_rs import _ffi
-    st = _ffi.Stats()
-    assert al._L.mm355_get_stats(al._context(), C.byref(st)) == 0
-    return st
 
 
 def _rc(c):
@@ -96,15 +76,6 @@ def world(built, tmp_path_factory):
         c[[1000, 2500, 2501, 4800]] = 4
         ambi.append(S.codes_to_str(c))
     return dict(fa=fa, g=g, reads=reads, cigar_reads={True: inv_ont + plain + ambi, False: [S.codes_to_str(c) for c in inv] + plain + ambi})
-
-
-def pair(fa, preset, cigar, **kw):
-    import mappy_rs
-    al = mappy_rs.Aligner(fa, preset=preset, cigar=cigar, **kw)
-    orc = O.OracleAligner(fa, preset=preset, **kw)
-    if not cigar:
-        orc.mo.flag &= ~4
-    return al, orc
 
 
 CASES = [("map-ont", {}), ("map-hifi", {}), ("asm20", {}), ("ava-ont", {}), ("map-ont", {"extra_flags": ALL_CHAINS})]

@@ -10,19 +10,16 @@ rejected and disagrees on nearly every problem ((1,19,1,39,3,85,1) vs (1,19,1,40
 (a + q + 2e = 128) is accepted and agrees, 121 is rejected and disagrees.  The rejected scorings of the random sweep mostly disagree too
 (asserted below for a share of them), so the domain is not much wider than the predicate."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import oracle as O
+import _capi
 import synthdata as S
 from test_row_sweep_model import consts, row_sweep, backtrack, REGULAR
 from test_band_model import band_sweep, plan
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(HERE, "..", "mappy-rs_amd", "csrc")
 
 # (a, b, sc_ambi, q, e, q2, e2) of the long-read presets (oracle/mmo_options.c)
 PRESETS = {"map-ont": (2, 4, 1, 4, 2, 24, 1), "map-hifi": (1, 4, 1, 6, 2, 26, 1), "asm5": (1, 19, 1, 39, 3, 81, 1), "asm10": (1, 9, 1, 16, 2, 41, 1),
@@ -35,12 +32,7 @@ EDGES = [(1, 19, 1, 39, 3, 85, 1), (120, 4, 1, 4, 2, 24, 1)]          # the last
 
 @pytest.fixture(scope="module")
 def domain():
-    src = os.path.join(HERE, "host_harness", "dp_domain_host.cpp")
-    so = os.path.join(HERE, "host_harness", "libdpdomainhost.so")
-    deps = [src, os.path.join(CSRC, "mm355_dpdomain.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-o", so, src])
-    L = C.CDLL(so)
+    L = _capi.build_harness("dp_domain_host", ["-Wall"], ["mm355_dpdomain.h"])
     L.dp_domain_host.argtypes = [C.c_int] * 7
     L.dp_domain_host.restype = C.c_int
     return lambda cfg: bool(L.dp_domain_host(*cfg))

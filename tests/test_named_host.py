@@ -5,28 +5,18 @@ with the filter on its regions to other targets are mmo_map(qname)'s regions wit
 g++ alone (tests/host_harness/named_host.cpp): mm355_regs.h with a name hash against mmo_map(qname), the MM_SEED_SELF clamp against a table
 worked by hand, the name ranking against Python's bytes comparison.  GPU side: tests/test_gpu_named.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import oracle as O
+import _capi
 import _named_truth as T
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(HERE, "..", "mappy-rs_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
 def named_lib(built):
-    src = os.path.join(HERE, "host_harness", "named_host.cpp")
-    so = os.path.join(HERE, "host_harness", "libnamedhost.so")
-    deps = [src] + [os.path.join(CSRC, h) for h in ("mm355_regs.h", "mm355_core.h", "mm355_names.h", "mm355_selfclamp.h")] + \
-           [os.path.join(HERE, "..", "include", "mm355.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-w", "-ffp-contract=off", "-o", so, src])
-    L = C.CDLL(so)
+    L = _capi.build_harness("named_host", ["-w", "-ffp-contract=off"], ["mm355_regs.h", "mm355_core.h", "mm355_names.h", "mm355_selfclamp.h"])
     L.named_regs_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_int32,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32]
     L.named_read_hash.restype = L.named_read_hash0.restype = L.named_x31.restype = C.c_uint32

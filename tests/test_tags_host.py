@@ -6,29 +6,22 @@ it.  The pow rule: with tags a read is deferred when any surviving region's dive
 comparison reads it.  The Python surface: properties, detach(), paf_line against hand-written lines.  GPU side: tests/test_gpu_tags.py."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import oracle as O
+import _capi
 import synthdata as S
 from test_chain_only_host import ALL_CHAINS, _inverted_genome
 import _tags_truth as T
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(HERE, "..", "mappy-rs_amd", "csrc")
 DEFER_POW = 2
 
 
 @pytest.fixture(scope="module")
 def tags_lib(built):
-    src = os.path.join(HERE, "host_harness", "regs_tags_host.cpp")
-    so = os.path.join(HERE, "host_harness", "libregstagshost.so")
-    deps = [src, os.path.join(CSRC, "mm355_regs.h"), os.path.join(CSRC, "mm355_core.h"), os.path.join(HERE, "..", "include", "mm355.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-w", "-ffp-contract=off", "-o", so, src])
-    L = C.CDLL(so)
+    L = _capi.build_harness("regs_tags_host", ["-w", "-ffp-contract=off"], ["mm355_regs.h", "mm355_core.h"])
     L.regs_tags_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_int32,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.regs_tags_host.restype = C.c_int

@@ -37,6 +37,16 @@ import synthdata as S  # noqa: E402
 READS = {"ecoli": (2, dict(n50=8000, sigma=0.75, lo=500, hi=100000)), "human": (4, dict(n50=10000, sigma=0.75, lo=500, hi=100000))}
 
 
+def timed_resident(L, ctx, mo, packed, flags):
+    """mm355_map_resident on the context's current batch: (seconds of the call alone, the HitsView of its record)"""
+    from mappy_rs import _ffi
+    t = time.perf_counter()
+    rc, hp = _ffi.call_map(L, ctx, mo, packed, flags, entry="current")
+    dt = time.perf_counter() - t
+    _ffi.check(rc)
+    return dt, _ffi.take_hits(L, hp, len(packed.keep))
+
+
 def ava_main(args):
     from mappy_rs import _ffi
     L = _ffi.lib()
@@ -49,7 +59,7 @@ def ava_main(args):
     io, mo = _ffi.IdxOpt(), _ffi.MapOpt()
     L.mm355_set_opt(None, C.byref(io), C.byref(mo))
     _ffi.check(L.mm355_set_opt(preset.encode(), C.byref(io), C.byref(mo)))
-    arr, rl, keep = _ffi.pack_reads(reads)
+    packed = arr, rl, keep = _ffi.pack_reads(reads)
     narr = _ffi.pack_names(names)
     lens64 = (C.c_int64 * len(reads))(*[len(r) for r in reads])
     idx = C.c_void_p()
@@ -66,18 +76,13 @@ def ava_main(args):
             _ffi.check(L.mm355_batch_upload_named(ctx, len(reads), arr, rl, narr))
         else:
             _ffi.check(L.mm355_batch_upload(ctx, len(reads), arr, rl))
-        hp = C.POINTER(_ffi.Hits)()
-        st = _ffi.Stats()
         rates = []
         for rep in range(max(1, args.reps) + 1):                  # the first pass is the warm-up
-            t = time.perf_counter()
-            _ffi.check(L.mm355_map_resident(ctx, C.byref(mo), 0, C.byref(hp)))
-            dt = time.perf_counter() - t
-            n_hits = int(hp.contents.n_hits)
-            L.mm355_free_hits(hp)
+            dt, v = timed_resident(L, ctx, mo, packed, 0)
+            n_hits = len(v.hits)
             if rep:
                 rates.append(round(bases / dt / 1e6, 1))
-        L.mm355_get_stats(ctx, C.byref(st))
+        st = _ffi.get_stats(L, ctx)
         res[leg] = {"mbases_per_s": sorted(rates)[len(rates) // 2], "mbases_per_s_passes": rates, "n_hits": n_hits, "n_a": int(st.n_a),
                     "n_a_kept": int(st.n_a_kept), "ms_k_seed_select": round(st.ms_kernel[3], 3), "ms_k_seed_expand": round(st.ms_kernel[4], 3),
                     "ms_other_kernels": round(sum(st.ms_kernel[:3]) + sum(st.ms_kernel[5:]), 3), "ms_total": round(st.ms_total, 1),
@@ -138,39 +143,31 @@ def main():
     res = {"workload": args.workload, "preset": args.preset, "scale": args.scale, "read_model": kw, "n_reads": len(reads),
            "sub_batch": args.sub, "bases": int(sum(map(len, reads)))}
     subs = [reads[i:i + args.sub] for i in range(0, len(reads), args.sub)]
-    keep = []
-    for j, sb in enumerate(subs):
-        arr, rl, k = _ffi.pack_reads(sb)
-        keep.append(k)
-        _ffi.check(L.mm355_batch_select(ctx, j)); _ffi.check(L.mm355_batch_upload(ctx, len(sb), arr, rl))
+    packed = [_ffi.pack_reads(sb) for sb in subs]
+    for j, pk in enumerate(packed):
+        _ffi.check(L.mm355_batch_select(ctx, j)); _ffi.check(L.mm355_batch_upload(ctx, len(pk.keep), pk.arr, pk.lens))
     names_l = list(names)
     for mode in ("cigar", "chain_only") + (("chain_only_tags",) if args.tags else ()):
         mo = _ffi.MapOpt.from_buffer_copy(mo0)
         if mode == "cigar":
             mo.flag |= 4
         flags = _ffi.OUT_CS if mode == "cigar" else _ffi.OUT_TAGS if mode == "chain_only_tags" else 0
-        hp = C.POINTER(_ffi.Hits)()
-        _ffi.check(L.mm355_batch_select(ctx, 0)); _ffi.check(L.mm355_map_resident(ctx, C.byref(mo), flags, C.byref(hp)))   # warm-up
-        L.mm355_free_hits(hp)
-        st = _ffi.Stats()
+        _ffi.check(L.mm355_batch_select(ctx, 0)); timed_resident(L, ctx, mo, packed[0], flags)   # warm-up
         rates = []
-        for _rep in range(max(1, args.reps) - 1):      # the earlier passes: rate only
+        for _rep in range(max(1, args.reps) - 1):      # the earlier passes: rate only, wall clock over the whole pass (select and release included)
             t = time.perf_counter()
             for j in range(len(subs)):
-                _ffi.check(L.mm355_batch_select(ctx, j)); _ffi.check(L.mm355_map_resident(ctx, C.byref(mo), flags, C.byref(hp)))
-                L.mm355_free_hits(hp)
+                _ffi.check(L.mm355_batch_select(ctx, j)); timed_resident(L, ctx, mo, packed[j], flags)
             rates.append(round(res["bases"] / (time.perf_counter() - t) / 1e6, 1))
         ms, n_dev, n_host, k_regs, k_other, n_hits = [], 0, 0, 0.0, 0.0, 0
         for j, sb in enumerate(subs):
             _ffi.check(L.mm355_batch_select(ctx, j))
-            t = time.perf_counter()
-            _ffi.check(L.mm355_map_resident(ctx, C.byref(mo), flags, C.byref(hp)))
-            ms.append((time.perf_counter() - t) * 1e3)
-            n_hits += int(hp.contents.n_hits)
+            dt, v = timed_resident(L, ctx, mo, packed[j], flags)
+            ms.append(dt * 1e3)
+            n_hits += len(v.hits)
             if mode == "chain_only" and j == 0 and args.check:
-                first = mappy_rs._batch_to_mappings(hp, len(sb), names_l, chain_only=True)
-            L.mm355_free_hits(hp)
-            L.mm355_get_stats(ctx, C.byref(st))
+                first = mappy_rs._batch_to_mappings(v, len(sb), names_l, chain_only=True)
+            st = _ffi.get_stats(L, ctx)
             n_dev += st.n_regs_dev; n_host += st.n_regs_host; k_regs += st.ms_kernel[23]; k_other += sum(st.ms_kernel[:23])
         tot_s = sum(ms) / 1e3
         rates.append(round(res["bases"] / tot_s / 1e6, 1))

@@ -52,8 +52,7 @@ def run_parts(parts, label, n_thr=6, dynamic=True):
                 si = nxt[0]; nxt[0] += 1
             if si >= len(packed):
                 return
-            arr, ln, keep = packed[si]
-            hp = C.POINTER(_ffi.Hits)(); _ffi.check(L.mm355_map_batch(ctxs[ti], C.byref(mo), len(keep), arr, ln, 1, C.byref(hp))); L.mm355_free_hits(hp)
+            _ffi.map_raw(L, ctxs[ti], mo, packed[si], 1)
     pool = ThreadPoolExecutor(n_thr)
 
     def step():

@@ -81,15 +81,12 @@ def run(seed, n_configs, preset):
             a0, b0 = int(rng.integers(0, len(c0) - 8000)), int(rng.integers(0, len(c1) - 8000))
             c = np.concatenate([c0[a0:a0 + 3000], comp(c1[b0:b0 + 2500]), c0[a0 + 5000:a0 + 7500]])
             reads.append(S.mutate(c, rng, 0.03, 0.01, 0.01).tobytes())
-        rarr, rlens, keep = _ffi.pack_reads(reads)
-        hp = C.POINTER(_ffi.Hits)()
-        rc = L.mm355_map_batch(ctx, C.byref(mo), len(reads), rarr, rlens, 1, C.byref(hp))
+        rc, v = _ffi.map_raw(L, ctx, mo, reads, 1, raise_on_error=False)
         if rc != 0:
             print("cfg %2d refused (rc %d) %s" % (ci, rc, f), flush=True)
             continue
-        got = mappy_rs._batch_to_mappings(hp, len(reads), names)
-        L.mm355_free_hits(hp)
-        st = _ffi.Stats(); L.mm355_get_stats(ctx, C.byref(st))
+        got = mappy_rs._batch_to_mappings(v, len(reads), names)
+        st = _ffi.get_stats(L, ctx)
         bad = nh = 0
         for i, rd in enumerate(reads):
             exp = orc.map(rd, cs=True)
