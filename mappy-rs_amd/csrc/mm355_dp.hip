@@ -683,11 +683,11 @@ int mm355_dp_run(mm355_ctx *c, const mm355_mapopt_t *mo, DpJobDev *jobs, size_t 
 		void lock(int cap) { std::unique_lock<std::mutex> lk(m); cv.wait(lk, [&] { return busy < cap; }); ++busy; }
 		void unlock() { { std::lock_guard<std::mutex> lk(m); --busy; } cv.notify_one(); }
 	};
-	static Turn dp_turn[16];
+	static std::vector<Turn> dp_turn((size_t)mm355_device_count());   // one per device, indexed by the device id
 	static const int turn_cap = [] { const char *e = getenv("MM355_DP_TURNS"); return e? atoi(e) : 1; }();
 	const bool take_turns = turn_cap > 0;
 	struct TurnGuard { Turn *t = 0; void lock(Turn *x, int cap) { x->lock(cap); t = x; } void unlock() { if (t) { t->unlock(); t = 0; } } ~TurnGuard() { unlock(); } } turn;
-	Turn *my_turn = &dp_turn[c->dev & 15];
+	Turn *my_turn = &dp_turn[c->dev];
 	HIPCHK(hipMemcpyAsync(c->dp_jobs.p, jobs, n * sizeof(DpJobDev), hipMemcpyHostToDevice, c->st));
 	int32_t *d_off = c->dp_work.as<int32_t>();
 	int32_t *d_ids = d_off + off_tot + 16;
@@ -718,7 +718,7 @@ int mm355_dp_run(mm355_ctx *c, const mm355_mapopt_t *mo, DpJobDev *jobs, size_t 
 	static const bool legacy_groups = [] { const char *e = getenv("MM355_DP_SPLIT_LONG"); return e && atoi(e) != 0; }();
 	const DpJobDev *dj = c->dp_jobs.as<DpJobDev>();
 	mm355_dpres_t *dres = c->dp_res.as<mm355_dpres_t>();
-	auto group_stream = [&](int sidx, hipStream_t *out) -> int { return mm355_dp_stream(c, sidx, out); };
+	auto group_stream = [&](int sidx, hipStream_t *out) -> int { return c->dp_stream(sidx, out); };
 	auto group_begin = [&](int g, hipStream_t gst) -> int {
 		if (c->dp_ev[g] == 0) HIPCHK(hipEventCreateWithFlags(&c->dp_ev[g], hipEventDisableTiming));
 		HIPCHK(hipStreamWaitEvent(gst, c->dp_up_ev, 0));
@@ -1209,7 +1209,7 @@ extern "C" int mm355_stage_dp(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t 
 {
 	if (c == 0 || mo == 0) return MM355_EINVAL;
 	HIPCHK(hipSetDevice(c->dev));
-	c->n_tpend = 0; memset(&c->stats, 0, sizeof(c->stats));
+	mm355_stats_reset(c);
 	HIPCHK(hipMemsetAsync(c->counters.p, 0, CTR_BYTES, c->st));
 	if (c->dp_q.ensure((size_t)n_q + 64) || c->dp_t.ensure((size_t)n_t + 64)) return MM355_ENOMEM;
 	if (n_q) HIPCHK(hipMemcpyAsync(c->dp_q.p, qcodes, n_q, hipMemcpyHostToDevice, c->st));

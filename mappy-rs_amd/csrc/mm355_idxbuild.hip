@@ -258,8 +258,7 @@ extern "C" int mm355_index_build_device(const mm355_idxopt_t *io, int n_seq, con
 		if (hipMemcpyAsync(mi->top_counts.data(), d_len2.p, keep * 4, hipMemcpyDeviceToHost, st) != hipSuccess) FAIL(MM355_EHIP);
 		if (hipStreamSynchronize(st) != hipSuccess) FAIL(MM355_EHIP);
 		if (hipGetLastError() != hipSuccess) FAIL(MM355_EHIP);
-		d_flag.release(); d_rid.release(); d_starts.release(); d_len.release(); d_multi.release(); d_moff.release(); d_len2.release();
-	}
+	}   // (the run tables leave HBM here, before the replica's pieces are allocated)
 	IB_LOG("count tail");
 	mi->S.resize(Sw);
 	if (hipMemcpy(mi->S.data(), dS, Sw * 4, hipMemcpyDeviceToHost) != hipSuccess) FAIL(MM355_EHIP);
@@ -288,8 +287,7 @@ extern "C" int mm355_index_build_device(const mm355_idxopt_t *io, int n_seq, con
 		}
 		mi->replicas.push_back(rp);
 	}
-done:
-	d_seq.release(); d_slots16.release(); d_cn.release(); d_co.release(); d_keys.release(); d_vals.release(); d_keys2.release(); d_vals2.release(); d_tmp.release(); d_err.release();
+done:   // (FAIL leaves every scope it jumps out of, so every DBuf is freed on the way here or at the return)
 	if (dS) (void)hipFree(dS);
 	(void)hipStreamDestroy(st);
 	if (rc) { mi->dev_id = device; free_build_buffers(mi); delete mi; return rc; }

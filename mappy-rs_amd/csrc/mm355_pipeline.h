@@ -6,9 +6,15 @@
 #include <functional>
 #include "mm355_host.h"
 #include "mm355_dev.h"
+#include "mm355_timers.h"
 
+// Device and pinned buffers own their memory: move-only, freed by the destructor (release() frees early, e.g. before a larger allocation)
 struct DBuf {
 	void *p = 0; size_t cap = 0;
+	DBuf() = default;
+	DBuf(DBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = 0; o.cap = 0; }
+	DBuf &operator=(DBuf &&o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = 0; o.cap = 0; } return *this; }
+	~DBuf() { release(); }                 // (the moves above delete the copies)
 	int ensure(size_t bytes, int slack_div = 2) {
 		if (bytes <= cap) return 0;
 		if (p) (void)hipFree(p);
@@ -28,6 +34,10 @@ struct DBuf {
 
 struct HBuf {                 // pinned host staging buffer (grow-only)
 	void *p = 0; size_t cap = 0;
+	HBuf() = default;
+	HBuf(HBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = 0; o.cap = 0; }
+	HBuf &operator=(HBuf &&o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = 0; o.cap = 0; } return *this; }
+	~HBuf() { release(); }
 	int ensure(size_t bytes) {
 		if (bytes <= cap) return 0;
 		if (p) (void)hipHostFree(p);
@@ -75,20 +85,39 @@ struct ResidentBatch { HostBatch hb; DBuf seq, roff, rlen, order, ck_read, ck_st
 #define CTR_BYTES        (CTR_WORDS * 8)
 static_assert(CTR_GCELLS_OFF >= 8 && CTR_PAIRS_OFF == CTR_GCELLS_OFF + CTR_GCELLS_WORDS && CTR_RMQ_OFF == CTR_PAIRS_OFF + CTR_PAIRS_WORDS, "counter regions must be disjoint");
 
-struct mm355_ctx {
+// The streams and events of a context.  acquire() is the one place they are made and release() the one place they go: a context whose
+// acquire() failed half way is released like any other.  The main and the sort stream of the first eight contexts of a device belong to that
+// device's pool (pool_slot >= 0), and so do the extension streams under MM355_DP_SHARED_STREAMS=1 (dp_shared); release() returns the slot
+// and leaves those streams with the pool.
+struct mm355_streams {
+	int dev = -1;                          // set by acquire()
+	hipStream_t st = 0, aux_st = 0;        // main stream; block-level sort of anchor-rich reads (mm355_cullsort.hip)
+	hipStream_t dp_st[16] = {};            // extension classes (dp_stream): 0..5 made by acquire(), 6 and 7 on first use
+	int pool_slot = -1; bool dp_shared = false;
+	int prio_low = 0, prio_high = 0; bool use_prio = false; int ord = 0;   // ord: creation ordinal of the context
+	hipEvent_t aux_ev = 0, aux_ev2 = 0, ev0 = 0, ev1 = 0, dp_up_ev = 0;
+	hipEvent_t dp_ev[24] = {}, dp_ev0[24] = {}, dp_ev1[24] = {};
+	mm355_streams() = default;
+	mm355_streams(const mm355_streams&) = delete; mm355_streams &operator=(const mm355_streams&) = delete;
+	~mm355_streams() { release(); }
+	int acquire(int device);               // makes `device` current; 0 or an MM355_E* code
+	void release();                        // (on the current device: mm355_ctx's destructor sets it)
+	int dp_prio(int sidx) const;
+	int dp_stream(int sidx, hipStream_t *out);   // stream of an extension kernel class
+};
+
+struct mm355_ctx : mm355_streams {
+	~mm355_ctx() { if (dev >= 0) (void)hipSetDevice(dev); release(); }   // streams and events first; the members free their memory after that
 	const mm355_index *mi = 0;
 	std::vector<ResidentBatch> slots; int cur_slot = 0;
-	int dev = 0;
-	hipStream_t st = 0;
 	DevIndex dix;
 	const uint32_t *d_name_rank = 0;       // the replica's name_rank[] (named seed kernels)
 	// per-batch device buffers
 	DBuf heavy, seq, roff, rlen, order, ck_read, ck_start, ck_n, ck_r0;
 	DBuf name_key;                         // HostBatch::name_key of the current call (uploaded only when the named seed kernels run)
 	int64_t n_chunks = 0;
-	int prio_low = 0, prio_high = 0; bool use_prio = false; int ord = 0;   // ord: creation ordinal of the context
 	DBuf sort_flag, tie_list, n_keep, aoff2, cs_list, tie_a, tie_b, tie_f, tie_p, tie_t8, tie_tcnt; HBuf h_cs;   // cull + sort of anchor-rich batches (mm355_cullsort.hip)
-	int n_heavy = 0; hipStream_t aux_st = 0; hipEvent_t aux_ev = 0, aux_ev2 = 0; DBuf sort_tasks;
+	int n_heavy = 0; DBuf sort_tasks;
 	DBuf mz, mz_tmp, n_mz, sn, sv, sflt, hl, soff, n_a, rep_len, n_mini, mini_pos, counters, err;
 	DBuf aoff, a, f, p, v, z, t8, vi, b, wk, u, u2, n_u, n_v;
 	// dp buffers
@@ -98,8 +127,7 @@ struct mm355_ctx {
 	HBuf h_tasks;                          // whole-array tasks of the literal anchor sort (pinned)
 	HBuf h_chunks; DBuf d_chunks;          // chunk table of k_chain_segments
 	HBuf h_jobs, h_gather, h_ids;          // pinned staging of the extension round (descriptors, launch orders)
-	HBuf h_arena[8]; int n_arena = 0;
-	hipEvent_t dp_up_ev = 0;      // dense CIGAR arenas of the launches of the current batch (results point into them)
+	HBuf h_arena[8]; int n_arena = 0;      // dense CIGAR arenas of the launches of the current batch (results point into them)
 	DBuf kprof;    // MM355_KPROF phase counters (64 x u64)
 	DBuf rq;       // per-read query codes fwd|rev
 	DBuf rmq_list, rmq_flag; HBuf h_rmq;   // device mg_lchain_rmq: listed reads, per-read state
@@ -107,19 +135,14 @@ struct mm355_ctx {
 	DBuf logt, regs_scr, regs_in; HBuf h_regs_in, h_regs_out;  // chain-only region stage (mm355_regs.hip): host-logf table, scratch + rows, read tables
 	bool logt_ok = false;
 	mm355_stats_t stats;
-	hipEvent_t ev0 = 0, ev1 = 0;
-	std::vector<hipEvent_t> tev; std::vector<double*> tacc; int n_tpend = 0;   // lazy stage timers (EvTimer, mm355_kt)
+	mm355_timer_book timers;           // lazy stage timers (EvTimer, mm355_kt)
 	unsigned long long pairs_land[64] = {};   // landing zone of the chain stage's pair counters (mm355_run_backtrack)
-	int pool_slot = -1;                // >= 0: st / aux_st are the device pool's (mm355_ctx_create), not this context's
 	bool timers_on = true;             // off for calls of fewer than 16 reads (two event records per kernel are a fifth of a single-read call); MM355_TIMERS=1 / 0 forces
-	int kt_open[KT_N] = {};   // open mm355_kt pair of a slot: its event-pair index + 1
-	hipStream_t dp_st[16] = {}; hipEvent_t dp_ev[24] = {}, dp_ev0[24] = {}, dp_ev1[24] = {};
 	HostBatch hb;
 };
+inline void mm355_stats_reset(mm355_ctx *c) { c->timers.reset(); memset(&c->stats, 0, sizeof(c->stats)); }   // a call starts: pending pairs dropped, stats zeroed
 
 DevParams mm355_make_params(const mm355_mapopt_t *mo, const mm355_index *mi);
-bool mm355_dp_shared_streams();
-int mm355_dp_stream(mm355_ctx *c, int sidx, hipStream_t *out);   // stream of an extension kernel class (shared by the contexts of a device)
 int mm355_check_opts(const mm355_mapopt_t *mo, const mm355_index *mi);
 
 // stage drivers (each leaves its outputs resident on the device and the per-read counts in ctx->hb)
@@ -169,20 +192,12 @@ struct EvTimer2 {
 	~EvTimer2() { float ms = 0; (void)hipEventRecord(c->ev1, c->st); (void)mm355_wait_stream(c->st); (void)hipEventElapsedTime(&ms, c->ev0, c->ev1); *acc += ms; }
 };
 void mm355_timers_resolve(mm355_ctx *c);
+void mm355_kt(void *kt, int slot, int end, hipStream_t st);   // per-kernel timer (mm355_dev.h: KtScope)
 void mm355_kprof_dump(mm355_ctx *c);
 struct EvTimer {
-	mm355_ctx *c; int slot;
-	EvTimer(mm355_ctx *c_, double *a) : c(c_), slot(-1)
-	{
-		if (!c->timers_on) return;
-		if (c->n_tpend >= 120) mm355_timers_resolve(c);
-		slot = c->n_tpend++;
-		while ((int)c->tev.size() < 2 * (slot + 1)) { hipEvent_t e = 0; (void)hipEventCreate(&e); c->tev.push_back(e); }
-		if ((int)c->tacc.size() <= slot) c->tacc.resize(slot + 1);
-		c->tacc[slot] = a;
-		(void)hipEventRecord(c->tev[2 * slot], c->st);
-	}
-	~EvTimer() { if (slot >= 0) (void)hipEventRecord(c->tev[2 * slot + 1], c->st); }
+	mm355_ctx *c; int pair;
+	EvTimer(mm355_ctx *c_, double *a) : c(c_), pair(c_->timers_on? c_->timers.begin(a, c_->st) : -1) {}
+	~EvTimer() { c->timers.end(pair, c->st); }
 };
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[mm355] HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); return MM355_EHIP; } } while (0)

@@ -1,4 +1,4 @@
-// mm355_pipeline.hip -- per-GPU context and the stage drivers of the seeding + chaining half of the path.
+// mm355_pipeline.hip -- index replicas and the stage drivers of the seeding + chaining half of the path.
 // Replaces the reference's per-thread mm_tbuf_t + the worker loop body at /root/reference/src/lib.rs:587-593:
 // instead of N OS threads each calling mm_map on one read, one context owns one GPU, the index is uploaded
 // once into its HBM, and a whole batch of reads moves through the kernels of mm355_kernels.hip.
@@ -7,7 +7,6 @@
 #include <algorithm>
 #include <numeric>
 #include <mutex>
-#include <atomic>
 #include <functional>
 #include "mm355_pipeline.h"
 #include "mm355_rmq.h"
@@ -46,7 +45,7 @@ DevParams mm355_make_params(const mm355_mapopt_t *mo, const mm355_index *mi)
 	return p;
 }
 
-// ------------------------------------------------------------------ context
+// ------------------------------------------------------------------ devices
 extern "C" int mm355_device_count(void)
 {
 	int n = 0;
@@ -54,169 +53,10 @@ extern "C" int mm355_device_count(void)
 	return n;
 }
 
-void mm355_timers_resolve(mm355_ctx *c)
-{
-	for (int i = 0; i < c->n_tpend; ++i) {
-		float ms = 0;
-		if (hipEventSynchronize(c->tev[2 * i + 1]) == hipSuccess && hipEventElapsedTime(&ms, c->tev[2 * i], c->tev[2 * i + 1]) == hipSuccess) *c->tacc[i] += ms;
-	}
-	c->n_tpend = 0;
-}
-
-// per-kernel timer (mm355_dev.h): the pair shares the lazy event slots of EvTimer
-void mm355_kt(void *kt, int slot, int end, hipStream_t st)
-{
-	mm355_ctx *c = (mm355_ctx*)kt;
-	if (c == 0 || slot < 0 || slot >= KT_N || !c->timers_on) return;
-	if (!end) {
-		if (c->n_tpend >= 120) mm355_timers_resolve(c);
-		const int k = c->n_tpend++;
-		while ((int)c->tev.size() < 2 * (k + 1)) { hipEvent_t e = 0; (void)hipEventCreate(&e); c->tev.push_back(e); }
-		if ((int)c->tacc.size() <= k) c->tacc.resize(k + 1);
-		c->tacc[k] = &c->stats.ms_kernel[slot];
-		c->kt_open[slot] = k + 1;
-		(void)hipEventRecord(c->tev[2 * k], st);
-	} else if (c->kt_open[slot] > 0) {
-		(void)hipEventRecord(c->tev[2 * (c->kt_open[slot] - 1) + 1], st);
-		c->kt_open[slot] = 0;
-	}
-}
-
 extern "C" int mm355_device_synchronize(int device_id)
 {
 	HIPCHK(hipSetDevice(device_id));
 	HIPCHK(hipDeviceSynchronize());
-	return 0;
-}
-
-// Streams of the extension rounds.  The runtime multiplexes the HIP streams of a priority level over GPU_MAX_HW_QUEUES (8) hardware queues,
-// handed out round-robin at stream creation; a kernel waits for everything in front of it on its QUEUE, whatever stream that came from.
-// With eight extension streams per context (round 2) the long latency chains of one context (k_ksw_regw8 / k_ksw_rowl: a few dozen
-// alignments for 10-20 ms) sat on the queue of another context's k_ksw_row<2> -- a kernel of the TURN, which every other context's round is
-// waiting for (rocprofv3 trace of round 3: a turn kernel started 17 ms late behind such a chain; the turn kernels covered 56 % of the time).
-// The rounds take turns anyway, so the classes need no stream per context: one pool of eight per device, each class on a queue of its own
-//   0 row<2> + approximate targets <= 256    2 row<8> + approximate 1024    3 row<4> + approximate 512        (the turn)
-//   1 exact register classes   4 eight-wave LDS kernel (all long targets)   6 k_ksw_rowl   5 / 7 k_ksw_regw8 (contexts alternate)
-// Measured (round 3, default bench, alternating runs on one box): shared pool 853 / 795 Mbases/s against 876 / 865 with eight streams per
-// context -- the exact classes and the long chains of different contexts then wait for one another on their one stream, which costs more
-// than the occasional held turn.  Kept as an experiment switch (MM355_DP_SHARED_STREAMS=1); the default is a set of streams per context.
-// Priority of an extension stream (experiment, off by default).  The runtime keeps a pool of hardware queues PER PRIORITY LEVEL: with the wide
-// grids of the turn (classes 0, 2, 3) and the latency chains (1 exact register classes, 4 / 5 long targets, 6 k_ksw_rowl, 7 k_ksw_regw8) on
-// one level, a turn kernel of one context sometimes sits on the hardware queue of another context's k_ksw_rowl / k_ksw_regw8 and starts when
-// that chain ends, 6-19 ms late, with every other context's round waiting for the turn (rocprofv3 trace of the round-4 default bench: 12 such
-// starts in 96 turns).  A level of their own for the chains (MM355_DP_PRIO3=1: chains normal, turn least; =2: turn normal, chains least)
-// removes that -- and costs more than it saves: 1276 1279 1336 (=1) and 1320 1319 (=2) against 1380 1435 1428 / 1406 1422 Mbases/s with one
-// level for every extension stream (alternating runs on one box): a third level is eight more hardware queues, and more than sixteen in
-// use were slower in every sweep of GPU_MAX_HW_QUEUES as well (profiles/r04_knob_sweeps.txt).
-static int dp_stream_prio(const mm355_ctx *c, int sidx)
-{
-	static const int three = [] { const char *e = getenv("MM355_DP_PRIO3"); return e? atoi(e) : 0; }();   // 1: chains normal, turn least; 2: turn normal, chains least
-	const bool chain = sidx == 1 || sidx >= 4;
-	return three && (three == 1? chain : !chain) && c->prio_low - c->prio_high >= 2? (c->prio_low + c->prio_high) / 2 : c->prio_low;
-}
-struct StreamPool { hipStream_t main[8], aux[8]; bool ready; uint8_t used; };   // main + sort stream of up to eight contexts per device (mm355_ctx_create)
-static StreamPool g_pool[16];
-static std::mutex g_pool_mu;
-bool mm355_dp_shared_streams() { static const bool on = [] { const char *e = getenv("MM355_DP_SHARED_STREAMS"); return e && atoi(e) != 0; }(); return on; }
-int mm355_dp_stream(mm355_ctx *c, int sidx, hipStream_t *out)
-{
-	static std::mutex mu;
-	static hipStream_t pool[16][8];
-	static bool ready[16];
-	if (!mm355_dp_shared_streams()) {
-		hipStream_t *slot = &c->dp_st[sidx];
-		if (*slot == 0) { if (c->use_prio) HIPCHK(hipStreamCreateWithPriority(slot, hipStreamNonBlocking, dp_stream_prio(c, sidx))); else HIPCHK(hipStreamCreateWithFlags(slot, hipStreamNonBlocking)); }
-		*out = *slot;
-		return 0;
-	}
-	const int d = c->dev & 15;
-	{
-		std::lock_guard<std::mutex> lk(mu);
-		if (!ready[d]) {
-			for (int i = 0; i < 8; ++i) {
-				if (c->use_prio) HIPCHK(hipStreamCreateWithPriority(&pool[d][i], hipStreamNonBlocking, dp_stream_prio(c, i)));
-				else HIPCHK(hipStreamCreateWithFlags(&pool[d][i], hipStreamNonBlocking));
-			}
-			ready[d] = true;
-		}
-	}
-	if (sidx == 5) sidx = 4;                            // one stream for every long-target launch
-	if (sidx == 7 && (c->ord & 1)) sidx = 5;            // k_ksw_regw8: two streams, the contexts alternate
-	*out = pool[d][sidx];
-	return 0;
-}
-
-extern "C" int mm355_ctx_create(const mm355_index_t *mi, int device_id, mm355_ctx_t **out)
-{
-	*out = 0;
-	if (mi == 0) return MM355_ENOIDX;
-	int n = 0;
-	if (hipGetDeviceCount(&n) != hipSuccess || n == 0 || device_id >= n) return MM355_ENODEV;
-	HIPCHK(hipSetDevice(device_id));
-	mm355_ctx *c = new mm355_ctx();
-	c->mi = mi; c->dev = device_id;
-	{   // the per-read front kernels are latency chains of single waves: their stream outranks the extension streams, whose wide
-		// grids would otherwise occupy every CU slot and stretch the front of the other contexts (MM355_STREAM_PRIO=0 disables)
-		int lo = 0, hi = 0;
-		static const bool use_prio = [] { const char *e = getenv("MM355_STREAM_PRIO"); return !(e && atoi(e) == 0); }();
-		(void)hipDeviceGetStreamPriorityRange(&lo, &hi);   // lo = least, hi = greatest (numerically lower)
-		// The main and the sort stream of the first eight contexts of a device come from a pool that is created in one go -- eight main streams, then
-		// eight sort streams: the runtime multiplexes the streams of a priority level over eight hardware queues, handed out in turn at stream
-		// creation, and a kernel waits for everything in front of it on its QUEUE.  Created context by context (main, sort, main, sort ...) the main
-		// streams of contexts i and i + 4 shared a queue, and so did their sort streams: the front of one context waited for the other's kernels.
-		// From the pool, the two streams of a context share a queue with each other and with no other context (1401 against 1350 Mbases/s, six and
-		// four alternating runs; MM355_STREAM_POOL=0: streams of its own for every context, as before).
-		static const bool pool_on = [] { const char *e = getenv("MM355_STREAM_POOL"); return !(e && atoi(e) == 0); }();
-		if (pool_on && use_prio && hi < lo) {
-			std::lock_guard<std::mutex> lk(g_pool_mu);
-			StreamPool &P = g_pool[device_id & 15];
-			if (!P.ready) {
-				for (int i = 0; i < 8; ++i) HIPCHK(hipStreamCreateWithPriority(&P.main[i], hipStreamDefault, hi));
-				for (int i = 0; i < 8; ++i) HIPCHK(hipStreamCreateWithPriority(&P.aux[i], hipStreamNonBlocking, hi));
-				P.ready = true;
-			}
-			for (int k = 0; k < 8; ++k) if (!(P.used >> k & 1)) { P.used |= (uint8_t)(1u << k); c->pool_slot = k; c->st = P.main[k]; c->aux_st = P.aux[k]; break; }
-		}
-		if (c->st) {}
-		else if (use_prio && hi < lo) HIPCHK(hipStreamCreateWithPriority(&c->st, hipStreamDefault, hi));
-		else HIPCHK(hipStreamCreate(&c->st));
-		c->prio_low = use_prio && hi < lo? lo : 0; c->prio_high = use_prio && hi < lo? hi : 0; c->use_prio = use_prio && hi < lo;
-		// The streams of the extension classes are created here, back to back under a lock: the runtime hands out hardware queues round-robin at
-		// stream creation, and the classes of one context must not share a queue (MM355_DP_SHARED_STREAMS=1: one pool per device, mm355_dp_stream).
-		static std::mutex mk;
-		std::lock_guard<std::mutex> lk(mk);
-		static std::atomic<int> n_ctx(0);
-		c->ord = n_ctx.fetch_add(1);
-		if (!mm355_dp_shared_streams()) {
-			// MM355_DP_QALIGN=1 (experiment): all eight extension streams at once, the four of the turn first (0, 2, 3 and the exact classes 1), then the
-			// four chains (4 / 5 long targets, 6 k_ksw_rowl, 7 k_ksw_regw8) rotated by the context's ordinal: with eight queues handed out in turn, every
-			// context's turn streams sit on queues 0-3 -- shared only with other contexts' turn streams, and turns exclude one another -- and a chain
-			// of context j on queue 4 + (class + j) mod 4.
-			static const bool qalign = [] { const char *e = getenv("MM355_DP_QALIGN"); return e && atoi(e) != 0; }();
-			static const int turn_first[4] = { 0, 2, 3, 1 };
-			for (int t = 0; t < (qalign? 8 : 6); ++t) {   // 0..3 the register classes, 4 and 5 the eight-wave kernel (mm355_dp_run): with the main and the sort stream, 8 per context
-				const int i = !qalign? t : t < 4? turn_first[t] : 4 + ((t - c->ord) & 3);
-				if (c->use_prio) HIPCHK(hipStreamCreateWithPriority(&c->dp_st[i], hipStreamNonBlocking, dp_stream_prio(c, i)));
-				else HIPCHK(hipStreamCreateWithFlags(&c->dp_st[i], hipStreamNonBlocking));
-			}
-		} else { hipStream_t t; int rc = mm355_dp_stream(c, 0, &t); if (rc) { mm355_ctx_destroy(c); return rc; } }
-		// the stream of the block-level sort of anchor-rich reads: same consideration (7 streams per context, 8 hardware queues)
-		if (c->aux_st) {} else if (c->use_prio) HIPCHK(hipStreamCreateWithPriority(&c->aux_st, hipStreamNonBlocking, c->prio_high)); else HIPCHK(hipStreamCreateWithFlags(&c->aux_st, hipStreamNonBlocking));
-		HIPCHK(hipEventCreateWithFlags(&c->aux_ev, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->aux_ev2, hipEventDisableTiming));
-	}
-	HIPCHK(hipEventCreate(&c->ev0)); HIPCHK(hipEventCreate(&c->ev1));
-	// the index replica of this device (shared by all its contexts; created on first use: H2D from the host image or a peer copy)
-	mm355_replica rp;
-	{ int rc = mm355_index_replica(mi, device_id, &rp); if (rc) { mm355_ctx_destroy(c); return rc; } }
-	c->dix.slots = (const mm355_slot*)rp.slots; c->dix.line_mask = mi->n_lines - 1;
-	c->dix.pos = (const uint64_t*)rp.pos; c->dix.S2 = (const uint32_t*)rp.S2; c->dix.nr = (const uint64_t*)rp.nr; c->dix.n_nr = rp.n_nr;
-	c->dix.seq_off = (const uint64_t*)rp.seq_off; c->dix.seq_len = (const uint32_t*)rp.seq_len;
-	c->dix.k = mi->k; c->dix.w = mi->w; c->dix.b = mi->b; c->dix.flag = mi->flag; c->dix.n_seq = mi->n_seq;
-	c->d_name_rank = (const uint32_t*)rp.name_rank;
-	if (c->counters.ensure(CTR_BYTES) || c->err.ensure(16)) { mm355_ctx_destroy(c); return MM355_ENOMEM; }
-	if (getenv("MM355_KPROF")) { if (c->kprof.ensure(512)) { mm355_ctx_destroy(c); return MM355_ENOMEM; } HIPCHK(hipMemset(c->kprof.p, 0, 512)); }
-	c->n_tpend = 0; memset(&c->stats, 0, sizeof(c->stats));
-	*out = c;
 	return 0;
 }
 
@@ -352,33 +192,6 @@ extern "C" int mm355_upload(mm355_index_t *mi, const int *device_ids, int n)
 		if (rc) return rc;
 	}
 	return 0;
-}
-
-extern "C" void mm355_ctx_destroy(mm355_ctx_t *c)
-{
-	if (c == 0) return;
-	(void)hipSetDevice(c->dev);
-	DBuf *bufs[] = { &c->sort_tasks, &c->sort_flag, &c->tie_list, &c->n_keep, &c->aoff2, &c->cs_list, &c->tie_a, &c->tie_b, &c->tie_f, &c->tie_p, &c->tie_t8, &c->tie_tcnt, &c->heavy, &c->name_key, &c->seq, &c->roff, &c->rlen, &c->order, &c->ck_read, &c->ck_start, &c->ck_n, &c->ck_r0,
-		&c->mz, &c->mz_tmp, &c->n_mz, &c->sn, &c->sv, &c->sflt, &c->hl, &c->soff, &c->n_a, &c->rep_len, &c->n_mini, &c->mini_pos, &c->counters, &c->err,
-		&c->aoff, &c->a, &c->f, &c->p, &c->v, &c->z, &c->t8, &c->vi, &c->b, &c->wk, &c->u, &c->u2, &c->n_u, &c->n_v,
-		&c->kprof, &c->d_chunks, &c->dp_jobs, &c->dp_res, &c->dp_q, &c->dp_t, &c->dp_bt, &c->dp_bt2, &c->dp_fail, &c->dp_cig, &c->dp_work, &c->dp_H, &c->rq, &c->dp_dense, &c->dp_gather, &c->pack, &c->rmq_list, &c->rmq_flag, &c->x_jobs, &c->x_cig, &c->x_cs, &c->x_out, &c->x_dense,
-		&c->logt, &c->regs_scr, &c->regs_in };
-	for (DBuf *b : bufs) b->release();
-	for (ResidentBatch &r : c->slots) { r.seq.release(); r.roff.release(); r.rlen.release(); r.order.release(); r.ck_read.release(); r.ck_start.release(); r.ck_r0.release(); }
-	c->h_fail.release(); c->h_cs.release(); c->h_rmq.release(); c->h_xjobs.release(); c->h_xcig.release(); c->h_xout.release(); c->h_xcs.release(); c->h_tasks.release(); c->h_chunks.release(); c->h_res.release(); c->h_jobs.release(); c->h_gather.release(); c->h_ids.release(); for (int i = 0; i < 8; ++i) c->h_arena[i].release(); c->h_cig.release(); c->h_pu.release(); c->h_pa.release(); c->h_pm.release(); c->h_seq.release();
-	c->h_regs_in.release(); c->h_regs_out.release(); c->h_pack.release();
-	for (int i = 0; i < 16; ++i) if (c->dp_st[i]) (void)hipStreamDestroy(c->dp_st[i]);
-	for (int i = 0; i < 24; ++i) { if (c->dp_ev[i]) (void)hipEventDestroy(c->dp_ev[i]); if (c->dp_ev0[i]) (void)hipEventDestroy(c->dp_ev0[i]); if (c->dp_ev1[i]) (void)hipEventDestroy(c->dp_ev1[i]); }
-	if (c->dp_up_ev) (void)hipEventDestroy(c->dp_up_ev);
-	if (c->aux_st && c->pool_slot < 0) (void)hipStreamDestroy(c->aux_st);
-	if (c->aux_ev) (void)hipEventDestroy(c->aux_ev);
-	if (c->aux_ev2) (void)hipEventDestroy(c->aux_ev2);
-	for (hipEvent_t e : c->tev) (void)hipEventDestroy(e);
-	if (c->ev0) (void)hipEventDestroy(c->ev0);
-	if (c->ev1) (void)hipEventDestroy(c->ev1);
-	if (c->st && c->pool_slot < 0) (void)hipStreamDestroy(c->st);
-	if (c->pool_slot >= 0) { std::lock_guard<std::mutex> lk(g_pool_mu); g_pool[c->dev & 15].used &= (uint8_t)~(1u << c->pool_slot); }   // (the streams stay with the device's pool)
-	delete c;
 }
 
 extern "C" int mm355_get_stats(mm355_ctx_t *c, mm355_stats_t *st) { if (c == 0) return MM355_EINVAL; mm355_timers_resolve(c); *st = c->stats; return 0; }
@@ -796,7 +609,7 @@ static int stage_prologue(mm355_ctx *c, const mm355_mapopt_t *mo, int64_t n_read
 {
 	if (c == 0) return MM355_EINVAL;
 	if (mo) { int rc = mm355_check_opts(mo, c->mi); if (rc) return rc; *pr = mm355_make_params(mo, c->mi); }
-	c->n_tpend = 0; memset(&c->stats, 0, sizeof(c->stats));
+	mm355_stats_reset(c);
 	const int rc = mm355_run_pack(c, n_reads, seqs, lens);
 	if (rc == 0) mm355_set_names(c, n_reads, names);
 	return rc;
