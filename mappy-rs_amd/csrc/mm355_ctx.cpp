@@ -6,7 +6,8 @@
 #include "mm355_pipeline.h"
 
 // ------------------------------------------------------------------ streams
-// Streams of the extension rounds.  The runtime multiplexes the HIP streams of a priority level over GPU_MAX_HW_QUEUES (8) hardware queues,
+// Streams of the extension rounds.  The runtime multiplexes the HIP streams of a priority level over GPU_MAX_HW_QUEUES hardware queues (8: set by
+// mm355_runtime_init below, whatever the process inherited),
 // handed out round-robin at stream creation; a kernel waits for everything in front of it on its QUEUE, whatever stream that came from.
 // With eight extension streams per context (round 2) the long latency chains of one context (k_ksw_regw8 / k_ksw_rowl: a few dozen
 // alignments for 10-20 ms) sat on the queue of another context's k_ksw_row<2> -- a kernel of the TURN, which every other context's round is
@@ -24,7 +25,7 @@
 // starts in 96 turns).  A level of their own for the chains (MM355_DP_PRIO3=1: chains normal, turn least; =2: turn normal, chains least)
 // removes that -- and costs more than it saves: 1276 1279 1336 (=1) and 1320 1319 (=2) against 1380 1435 1428 / 1406 1422 Mbases/s with one
 // level for every extension stream (alternating runs on one box): a third level is eight more hardware queues, and more than sixteen in
-// use were slower in every sweep of GPU_MAX_HW_QUEUES as well (profiles/r04_knob_sweeps.txt).
+// use were slower in every sweep of the queue count as well (profiles/r04_knob_sweeps.txt; MM355_HW_QUEUES is the knob now).
 int mm355_streams::dp_prio(int sidx) const
 {
 	static const int three = [] { const char *e = getenv("MM355_DP_PRIO3"); return e? atoi(e) : 0; }();   // 1: chains normal, turn least; 2: turn normal, chains least
@@ -128,9 +129,35 @@ int mm355_streams::dp_stream(int sidx, hipStream_t *out)
 	return 0;
 }
 
+// ------------------------------------------------------------------ hardware queues
+// The stream layout above is tuned for eight hardware queues per priority level (profiles/r04_knob_sweeps.txt: 1244 Mbases/s with 8, 1047 with
+// 4, 921 with 16), and the runtime reads GPU_MAX_HW_QUEUES once, when it starts.  So the library sets it itself, before its first HIP call:
+// MM355_HW_QUEUES (a number, clamped to 1..32) if given, else 8 -- over whatever the process inherited; a value that is no number counts as
+// not given (atoi's 0 would mean ONE queue).  Every entry point that can be the first to reach the runtime calls this.  Where something else
+// in the process started HIP earlier the call comes too late and changes nothing.  setenv() must not run beside another thread's getenv():
+// the library's own threads (host pool, context threads) start after this call, and an embedder makes its first call into the library
+// before it starts threads that read the environment.
+void mm355_runtime_init(void)
+{
+	static std::once_flag once;
+	std::call_once(once, [] {
+		const char *seen = getenv("GPU_MAX_HW_QUEUES"), *want = getenv("MM355_HW_QUEUES");
+		int q = 8;
+		char *end = 0;
+		const long w = want? strtol(want, &end, 10) : 0;
+		const bool given = want && end != want && *end == 0;
+		if (given) q = w < 1? 1 : w > 32? 32 : (int)w;
+		char buf[16];
+		snprintf(buf, sizeof(buf), "%d", q);
+		if (getenv("MM355_VERBOSE")) fprintf(stderr, "[mm355] hardware queues: GPU_MAX_HW_QUEUES was %s, now %s (%s)\n", seen? seen : "not set", buf, given? "MM355_HW_QUEUES" : "the tuned default");
+		setenv("GPU_MAX_HW_QUEUES", buf, 1);
+	});
+}
+
 // ------------------------------------------------------------------ context
 extern "C" int mm355_ctx_create(const mm355_index_t *mi, int device_id, mm355_ctx_t **out)
 {
+	mm355_runtime_init();
 	*out = 0;
 	if (mi == 0) return MM355_ENOIDX;
 	mm355_ctx *c = new mm355_ctx();   // from here on every failure leaves through fail(): the destructor gives back whatever was acquired

@@ -130,6 +130,7 @@ extern "C" int mm355_index_build_device(const mm355_idxopt_t *io, int n_seq, con
 	*out = 0;
 	if (n_seq <= 0) return MM355_EINVAL;
 	if (io->k <= 0 || io->k > 28 || io->w <= 0 || io->w >= 256) return MM355_EINVAL;   // U:sketch.c::mm_sketch asserts the same ranges (e.g. options never initialised with mm355_set_opt(NULL, ..))
+	mm355_runtime_init();
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) return MM355_ENODEV;
 	HIPCHK(hipSetDevice(device));

@@ -746,13 +746,18 @@ __device__ inline uint32_t block_ordered_prefix(bool flag, uint32_t &base, MwLds
 	return off;
 }
 
+// MM355_KPROF slots KP_LEVEL + 0..4 ("lvl:*" in mm355_kprof_dump): histogram, compaction, walk, scatter, copy-back of a task of the big class
+#define KP_LEVEL 26
 // One block per task (a bucket of one read at byte shift s).  NT threads, LABCAP label bytes in LDS: <1024, 120 KB> for buckets of more
 // than MW_BIG elements, <256, MW_BIG + 64 B> for the medium ones (six blocks per CU instead of one).  Children go to the list of their
 // own size class; ctr = { next-level big, next-level medium, wave tasks (running total) }.
 template <typename T, typename Key, int NT, int LABCAP>
 __device__ inline void mw_level_task(MwLds<NT> &L, uint8_t *lds_lab, const DevAnchors &an, const SortTask tk, SortTask *out_big, SortTask *out_med, SortTask *out_small,
-                                     unsigned int *ctr, unsigned int *ctr_small, uint32_t big_min, uint32_t med_min, SortTask *stk = 0, unsigned int *stk_n = 0, uint32_t stk_cap = 0)
+                                     unsigned int *ctr, unsigned int *ctr_small, uint32_t big_min, uint32_t med_min, unsigned long long *prof, SortTask *stk = 0, unsigned int *stk_n = 0, uint32_t stk_cap = 0)
 {
+	// (stamped by thread 0 of a big-class block alone: KPROF stamps where its pointer is set, and one wave's clock is the block's between barriers)
+	const struct { unsigned long long *prof; } kp_src = { NT == MW_NT && threadIdx.x == 0? prof : 0 };
+	KPROF_BEGIN(kp_src);
 	const int64_t o = an.aoff[tk.read];
 	T *a = SortArr<T>::arr(an, o);
 	const WalkScratch ws = SortArr<T>::ws(an, o);
@@ -775,6 +780,7 @@ __device__ inline void mw_level_task(MwLds<NT> &L, uint8_t *lds_lab, const DevAn
 	}
 	if (tid == 0) { uint32_t acc = 0; for (int k = 0; k < 256; ++k) { L.bb[k] = acc; acc += L.cnt[k]; L.be[k] = acc; } }
 	__syncthreads();
+	KPROF(KP_LEVEL + 0);
 	T *out = (T*)ws.out + beg;
 	uint32_t *fpos = ws.fpos + beg, *rank = ws.rank + beg;
 	uint8_t *flab = ws.flab + beg;
@@ -802,6 +808,7 @@ __device__ inline void mw_level_task(MwLds<NT> &L, uint8_t *lds_lab, const DevAn
 	__syncthreads();
 	const bool two = L.wtot[0] + L.wtot[1] + L.wtot[2] + L.wtot[3] == 2;
 	__syncthreads();
+	KPROF(KP_LEVEL + 1);
 	if (two) {
 		const uint32_t m = nfor >> 1;   // foreign elements per region
 		for (uint32_t e = tid; e < nfor; e += NT) rank[e] = e < m? e : e - m;
@@ -825,6 +832,7 @@ __device__ inline void mw_level_task(MwLds<NT> &L, uint8_t *lds_lab, const DevAn
 		}
 	}
 	__syncthreads();
+	KPROF(KP_LEVEL + 2);
 	uint32_t nfb = 0;
 	for (uint32_t base = 0; base < tot; base += NT) {
 		const uint32_t rel = base + tid;
@@ -840,8 +848,10 @@ __device__ inline void mw_level_task(MwLds<NT> &L, uint8_t *lds_lab, const DevAn
 		}
 	}
 	__syncthreads();
+	KPROF(KP_LEVEL + 3);
 	for (uint32_t i = tid; i < tot; i += NT) a[beg + i] = out[i];
 	__syncthreads();
+	KPROF(KP_LEVEL + 4);
 	if (s > 0 && tid < 256) {   // children: big / medium -> another block level, small -> one wave each, <= 64 -> insertion sort right here
 		const uint32_t b0 = L.bb[tid], sz = L.cnt[tid];
 		if (sz > 1 && !ws_has_tie(ws.tcnt, beg + b0, beg + b0 + sz)) { /* unique content, restored by the caller */ }
@@ -862,8 +872,9 @@ __device__ inline void mw_level_task(MwLds<NT> &L, uint8_t *lds_lab, const DevAn
 // blocks that each wait for a whole free CU beside the other contexts' kernels.
 template <typename T, typename Key, int NT, int LABCAP>
 __global__ __launch_bounds__(NT) void k_sort_level_mw(DevAnchors an, const SortTask *tasks, const unsigned int *n_tasks_p, SortTask *out_big, SortTask *out_med, SortTask *out_small,
-                                                      unsigned int *ctr, unsigned int *ctr_small, uint32_t big_min, uint32_t med_min, int *err, SortTask *stacks)
+                                                      unsigned int *ctr, unsigned int *ctr_small, uint32_t big_min, uint32_t med_min, int *err, SortTask *stacks, unsigned long long *prof)
 {
+	MM355_LATENCY_KERNEL();   // one lane walks while the block waits: the walking wave issues ahead of the wide grids on its SIMD
 	__shared__ MwLds<NT> L;
 	__shared__ unsigned int s_stk_n;
 	extern __shared__ uint8_t lds_lab[];   // LABCAP labels
@@ -875,7 +886,7 @@ __global__ __launch_bounds__(NT) void k_sort_level_mw(DevAnchors an, const SortT
 	for (unsigned int t = blockIdx.x; t < n_tasks; t += gridDim.x) {
 		if (threadIdx.x == 0) s_stk_n = 0;
 		__syncthreads();
-		mw_level_task<T, Key, NT, LABCAP>(L, lds_lab, an, tasks[t], out_big, out_med, out_small, ctr, ctr_small, big_min, med_min, stk, &s_stk_n, stk? MW_STK : 0);
+		mw_level_task<T, Key, NT, LABCAP>(L, lds_lab, an, tasks[t], out_big, out_med, out_small, ctr, ctr_small, big_min, med_min, prof, stk, &s_stk_n, stk? MW_STK : 0);
 		for (;;) {
 			__threadfence_block();
 			__syncthreads();
@@ -885,7 +896,7 @@ __global__ __launch_bounds__(NT) void k_sort_level_mw(DevAnchors an, const SortT
 			__syncthreads();
 			if (threadIdx.x == 0) s_stk_n = n - 1;
 			__syncthreads();
-			mw_level_task<T, Key, NT, LABCAP>(L, lds_lab, an, tk, out_big, out_med, out_small, ctr, ctr_small, big_min, med_min, stk, &s_stk_n, MW_STK);
+			mw_level_task<T, Key, NT, LABCAP>(L, lds_lab, an, tk, out_big, out_med, out_small, ctr, ctr_small, big_min, med_min, prof, stk, &s_stk_n, MW_STK);
 		}
 	}
 	(void)err;
@@ -895,6 +906,7 @@ __global__ __launch_bounds__(NT) void k_sort_level_mw(DevAnchors an, const SortT
 template <typename T, typename Key>
 __global__ __launch_bounds__(WAVE) void k_sort_tasks(DevAnchors an, const SortTask *tasks, const unsigned int *n_tasks_p, int *err)
 {
+	MM355_LATENCY_KERNEL();
 	__shared__ SortLds L;
 	__shared__ mm128 stage[2048];
 	const unsigned int n_tasks = *n_tasks_p;
@@ -926,7 +938,7 @@ __global__ __launch_bounds__(WAVE) void k_sort_tasks(DevAnchors an, const SortTa
 size_t mm355_sort_buf_bytes(size_t task_cap);
 #define MW_STK 128                   // entries of a big-class block's own stack of big buckets
 template <typename T, typename Key>
-static int sort_tasks_run(DevAnchors &an, SortTask *d_big[2], SortTask *d_med[2], SortTask *d_small, unsigned int *d_ctr, int n_big, int n_med, int n_small, size_t n_elems, size_t task_cap, int n_levels, int *err, hipStream_t st, void *kt, SortTask *stacks)
+static int sort_tasks_run(DevAnchors &an, SortTask *d_big[2], SortTask *d_med[2], SortTask *d_small, unsigned int *d_ctr, int n_big, int n_med, int n_small, size_t n_elems, size_t task_cap, int n_levels, int *err, hipStream_t st, void *kt, SortTask *stacks, unsigned long long *prof)
 {
 	(void)hipFuncSetAttribute((const void*)k_sort_level_mw<T, Key, MW_NT, MW_LAB_CAP>, hipFuncAttributeMaxDynamicSharedMemorySize, MW_LAB_CAP);
 	const uint32_t big_min = (uint32_t)mm355_sort_heavy_threshold(), med_min = (uint32_t)mm355_sort_medium_threshold();
@@ -949,8 +961,8 @@ static int sort_tasks_run(DevAnchors &an, SortTask *d_big[2], SortTask *d_med[2]
 		const size_t gb = level == 0? (size_t)n_big : level == 1? cap_big : std::min(cap_big, deep_big), gm = level == 0? (size_t)n_med : cap_med;
 		if (level == 0 && n_big + n_med == 0) break;
 		unsigned int *c_in = d_ctr + 2 * level, *c_out = d_ctr + 2 * (level + 1);
-		if (gb) { KtScope ks(kt, KT_LITERAL, st); hipLaunchKernelGGL((k_sort_level_mw<T, Key, MW_NT, MW_LAB_CAP>), dim3((unsigned)std::min<size_t>(gb, MW_STACK_BLOCKS)), dim3(MW_NT), MW_LAB_CAP, st, an, d_big[cur], c_in, d_big[cur ^ 1], d_med[cur ^ 1], d_small, c_out, d_small_ctr, big_min, med_min, err, stacks); }
-		if (gm) { KtScope ks(kt, KT_LIT_MED, st); hipLaunchKernelGGL((k_sort_level_mw<T, Key, 256, MW_MED_LAB>), dim3((unsigned)gm), dim3(256), MW_MED_LAB, st, an, d_med[cur], c_in + 1, d_big[cur ^ 1], d_med[cur ^ 1], d_small, c_out, d_small_ctr, big_min, med_min, err, (SortTask*)0); }
+		if (gb) { KtScope ks(kt, KT_LITERAL, st); hipLaunchKernelGGL((k_sort_level_mw<T, Key, MW_NT, MW_LAB_CAP>), dim3((unsigned)std::min<size_t>(gb, MW_STACK_BLOCKS)), dim3(MW_NT), MW_LAB_CAP, st, an, d_big[cur], c_in, d_big[cur ^ 1], d_med[cur ^ 1], d_small, c_out, d_small_ctr, big_min, med_min, err, stacks, prof); }
+		if (gm) { KtScope ks(kt, KT_LIT_MED, st); hipLaunchKernelGGL((k_sort_level_mw<T, Key, 256, MW_MED_LAB>), dim3((unsigned)gm), dim3(256), MW_MED_LAB, st, an, d_med[cur], c_in + 1, d_big[cur ^ 1], d_med[cur ^ 1], d_small, c_out, d_small_ctr, big_min, med_min, err, (SortTask*)0, prof); }
 		cur ^= 1;
 	}
 	const size_t gs = n_big + n_med == 0? (size_t)n_small : std::min<size_t>(task_cap, 16384);
@@ -1382,7 +1394,6 @@ void mm355_launch_seed_expand(const DevIndex &ix, const DevParams &pr, const Dev
 // same for every element the index can produce (a level whose byte is constant is skipped inside the kernel and opens no new list).
 int mm355_launch_sort(const DevBatch &bt, DevAnchors &an, int *err, const void *h_tasks, int n_big, int n_med, int n_small, size_t n_elems, void *task_buf, size_t task_cap, hipStream_t st, void *kt, int n_levels)
 {
-	(void)bt;
 	const int n = n_big + n_med + n_small;
 	if (n == 0) return 0;
 	SortTask *base = (SortTask*)task_buf;
@@ -1398,7 +1409,7 @@ int mm355_launch_sort(const DevBatch &bt, DevAnchors &an, int *err, const void *
 	if (n_big && hipMemcpyAsync(big[0], ht, (size_t)n_big * sizeof(SortTask), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
 	if (n_med && hipMemcpyAsync(med[0], ht + n_big, (size_t)n_med * sizeof(SortTask), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
 	if (n_small && hipMemcpyAsync(small, ht + n_big + n_med, (size_t)n_small * sizeof(SortTask), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
-	return sort_tasks_run<mm128, mm_key_x>(an, big, med, small, ctr, n_big, n_med, n_small, n_elems, task_cap, n_levels > 0? n_levels : MW_LEVELS, err, st, kt, stacks);
+	return sort_tasks_run<mm128, mm_key_x>(an, big, med, small, ctr, n_big, n_med, n_small, n_elems, task_cap, n_levels > 0? n_levels : MW_LEVELS, err, st, kt, stacks, bt.prof);
 }
 int mm355_sort_task_bytes(void) { return (int)sizeof(SortTask); }
 // device scratch of mm355_launch_sort for `task_cap`: five task lists, 64 counters, the stacks of the big-class blocks

@@ -203,6 +203,7 @@ struct EvTimer {
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[mm355] HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); return MM355_EHIP; } } while (0)
 
 int mm355_sort_levels(const mm355_index *mi);
+void mm355_runtime_init(void);   // before the library's first HIP call: the hardware queue count (mm355_ctx.cpp)
 bool mm355_cull_sort_fits(const mm355_ctx *c);   // the 8-byte words of mm355_cullsort.hip can hold this batch (position bits + index bits <= 64)
 int mm355_cull_sort(mm355_ctx *c, const DevParams &pr, int cull);   // mm355_cullsort.hip: anchors that cannot chain dropped, the rest sorted per read in LDS
 hipError_t mm355_wait_stream(hipStream_t st);   // polls hipStreamQuery with short naps (MM355_BLOCKING_WAIT=0: hipStreamSynchronize, =1: blocking-sync event)

@@ -48,6 +48,7 @@ DevParams mm355_make_params(const mm355_mapopt_t *mo, const mm355_index *mi)
 // ------------------------------------------------------------------ devices
 extern "C" int mm355_device_count(void)
 {
+	mm355_runtime_init();
 	int n = 0;
 	if (hipGetDeviceCount(&n) != hipSuccess) return 0;
 	return n;
@@ -55,6 +56,7 @@ extern "C" int mm355_device_count(void)
 
 extern "C" int mm355_device_synchronize(int device_id)
 {
+	mm355_runtime_init();
 	HIPCHK(hipSetDevice(device_id));
 	HIPCHK(hipDeviceSynchronize());
 	return 0;
@@ -68,7 +70,7 @@ void mm355_kprof_dump(mm355_ctx *c)
 	if (hipMemcpy(h, c->kprof.p, 512, hipMemcpyDeviceToHost) != hipSuccess) return;
 	(void)hipMemset(c->kprof.p, 0, 512);
 	static const char *nm[32] = { "bt:zlist", "bt:zsort", "bt:walk", "bt:compact", "sel:hits", "sel:streaks", "sel:tail", "-",
-	                              "srt:total", "-", "-", "-", "chb:total", "chs:total", "-", "-", "mzf:total", "rmq:windows", "rmq:dp", "-", "rbt:zlist", "rbt:zsort", "rbt:walk", "rbt:compact", "sk:piece", "sk:pack", "-", "-", "-", "-", "-", "-" };
+	                              "srt:total", "-", "-", "-", "chb:total", "chs:total", "-", "-", "mzf:total", "rmq:windows", "rmq:dp", "-", "rbt:zlist", "rbt:zsort", "rbt:walk", "rbt:compact", "sk:piece", "sk:pack", /* 26 = KP_LEVEL (mm355_kernels.hip): */ "lvl:hist", "lvl:compact", "lvl:walk", "lvl:scatter", "lvl:copy", "-" };
 	fprintf(stderr, "[mm355] kprof (Mcycles: sum over reads / slowest read):");
 	for (int i = 0; i < 32; ++i) if (h[i]) fprintf(stderr, " %s %.1f/%.2f", nm[i], h[i] / 1e6, h[32 + i] / 1e6);
 	fprintf(stderr, "\n");
@@ -183,6 +185,7 @@ extern "C" int mm355_upload(mm355_index_t *mi, const int *device_ids, int n)
 {
 	if (mi == 0) return MM355_ENOIDX;
 	if (n < 0 || (n > 0 && device_ids == 0)) return MM355_EINVAL;
+	mm355_runtime_init();
 	int nd = 0;
 	if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) return MM355_ENODEV;
 	for (int i = 0; i < n; ++i) {

@@ -14,10 +14,10 @@ PY
 if [ -n "$2" ]; then
   while IFS='|' read -r name envs args; do [ -n "$name" ] && run "$name" "${envs:-A=1}" "$args"; done < "$2"
 else
-  # (every knob below exists in the library: MM355_DP_TURNS, MM355_DP_REGW8, MM355_DP_SHARED_STREAMS, MM355_RMQ_ON_HOST, MM355_BUF_SLACK_DIV, GPU_MAX_HW_QUEUES)
+  # (every knob below exists in the library: MM355_DP_TURNS, MM355_DP_REGW8, MM355_DP_SHARED_STREAMS, MM355_RMQ_ON_HOST, MM355_BUF_SLACK_DIV, MM355_HW_QUEUES -- the library sets GPU_MAX_HW_QUEUES from it, over an inherited value)
   run base "A=1" ""
-  run q16 "GPU_MAX_HW_QUEUES=16" ""
-  run q4 "GPU_MAX_HW_QUEUES=4" ""
+  run q16 "MM355_HW_QUEUES=16" ""
+  run q4 "MM355_HW_QUEUES=4" ""
   run turns2 "MM355_DP_TURNS=2" ""
   run regw1 "MM355_DP_REGW8=0" ""
   run shared "MM355_DP_SHARED_STREAMS=1" ""
