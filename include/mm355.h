@@ -119,6 +119,25 @@ int mm355_index_build(const mm355_idxopt_t *io, int n_seq, const char *const *se
  * mm_idx_reader_read for large references).  The table stays resident on that device; other devices get peer copies (mm355_upload). */
 int mm355_index_build_device(const mm355_idxopt_t *io, int n_seq, const uint8_t *const *seqs, const int64_t *lens,
                              const char *const *names, int device, mm355_index_t **out);
+/* a FASTA / FASTQ path (plain or gzip: the reader of mm355_index_load) indexed on GPU `device` through mm355_index_build_device; a path
+ * whose magic is MMI\2 is loaded as mm355_index_load loads it (a host image: there is nothing to build).  Same error codes as
+ * mm355_index_load, plus MM355_ENODEV. */
+int mm355_index_load_device(const char *path, const mm355_idxopt_t *io, int device, mm355_index_t **out);
+/* writes the index as a minimap2 MMI\2 file: replaces mm_idx_dump, the reference's fn_idx_out (lib.rs:391-394).  Any index: loaded from
+ * .mmi, built on the host, or built on a device (its table is converted in HBM and copied out in fixed-size pieces).  The file is the one
+ * U:index.c::mm_idx_load reads:
+ *   magic; w k b n_seq flag (5 x u32); per contig u8 name length, name, u32 length; for each of the 1<<b buckets i32 n, n position words,
+ *   u32 size, size (key, value) pairs; unless flag & 2 (MM_I_NO_SEQ) the 4-bit sequence image, (sum_len+7)/8 words.
+ *   bucket = minimizer & ((1<<b)-1); key = minimizer>>b<<1, | 1 for a singleton; value = the position word of a singleton, else
+ *   start<<32 | count with start relative to the bucket's own p[].
+ * minimap2 lists a bucket's pairs in khash slot order, which no loader depends on (they re-insert).  This writer's order is CANONICAL, so
+ * that the file is a pure function of the index: within a bucket the pairs have ascending keys, and p[] holds the runs of the
+ * multi-occurrence keys in that same order, each run ascending -- the p[] layout of U:index.c::worker_post, so the p[] sections and every
+ * value equal minimap2's own dump.
+ * MM355_ENOIDX for NULL; MM355_EINVAL when a contig name is longer than 255 bytes (the length field is one byte; checked before the file
+ * is opened); MM355_EIO when the file cannot be created or written (a partly written file is removed); MM355_ENOMEM / MM355_EHIP from
+ * the device conversion.  The index is unchanged. */
+int mm355_index_dump(const mm355_index_t *idx, const char *path);
 void mm355_index_free(mm355_index_t *idx);
 /* header fields read at lib.rs:655-670 (k, w, n_seq) */
 int mm355_index_info(const mm355_index_t *idx, int32_t *k, int32_t *w, int32_t *b, int32_t *flag, uint32_t *n_seq);

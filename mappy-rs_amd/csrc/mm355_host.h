@@ -1,6 +1,7 @@
 // mm355_host.h -- host-side structures of libmm355 (index, options, batch context)
 #pragma once
 #include <stdint.h>
+#include <stdio.h>
 #include <string>
 #include <vector>
 #include <unordered_map>
@@ -59,6 +60,9 @@ inline uint32_t mm355_host_get(const mm355_index *mi, uint64_t minier, uint64_t 
 		line = (line + 1) & (mi->n_lines - 1);
 	}
 }
+
+// mm355_idxdump.hip: the bucket sections of the .mmi of a device-resident index, converted to the canonical order in HBM and streamed to fp
+int mm355_index_dump_buckets_device(const mm355_index *mi, FILE *fp);
 
 int mm355_index_from_pairs(mm355_index *mi, std::vector<mm128> &pairs);   // pairs: x = minimizer (56 bit), y = position word
 int32_t mm355_index_cal_max_occ(const mm355_index *mi, float f);

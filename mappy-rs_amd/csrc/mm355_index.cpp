@@ -1,9 +1,9 @@
-// mm355_index.cpp -- host side of the index: MMI\2 reader, FASTA/FASTQ builder, the flat
+// mm355_index.cpp -- host side of the index: MMI\2 reader and writer, FASTA/FASTQ builder, the flat
 // 128-B-line hash table that is uploaded to HBM, sequence accessors and option presets.
 // Replaces, behind the C-ABI of include/mm355.h, the reference's FFI calls
 //   mm_set_opt (lib.rs:333,336), mm_idx_reader_open/read/close (lib.rs:397-412),
 //   mm_mapopt_update (lib.rs:414), mm_idx_index_name (lib.rs:416),
-//   mm_idx_name2id (lib.rs:716), mm_idx_getseq (lib.rs:747).
+//   mm_idx_name2id (lib.rs:716), mm_idx_getseq (lib.rs:747), mm_idx_dump (fn_idx_out, lib.rs:391-394).
 // minimap2 2.26 units whose observable behaviour is kept: U:index.c (file format, key/value
 // encoding, positions ascending inside a run, mm_idx_cal_max_occ), U:options.c (presets).
 #include <stdio.h>
@@ -282,12 +282,11 @@ static mm355_index *build_from_seqs(const mm355_idxopt_t *io, int n_seq, const c
 }
 
 // FASTA/FASTQ, plain or gzip-compressed (U:bseq.c reads through zlib's gzFile, which passes plain files through unchanged)
-static mm355_index *build_from_fastx(const char *path, const mm355_idxopt_t *io, int n_threads)
+static bool parse_fastx(const char *path, std::vector<std::string> &names, std::vector<std::string> &seqs)
 {
 	gzFile gz = gzopen(path, "rb");
-	if (gz == 0) return 0;
+	if (gz == 0) return false;
 	(void)gzbuffer(gz, 1 << 20);
-	std::vector<std::string> names, seqs;
 	std::string line;
 	std::vector<char> buf(1 << 16);
 	bool in_qual = false, is_fq = false, eof = false; size_t l_qual = 0;
@@ -313,11 +312,24 @@ static mm355_index *build_from_fastx(const char *path, const mm355_idxopt_t *io,
 	}
 	int zerr = 0; (void)gzerror(gz, &zerr);
 	gzclose(gz);
-	if (zerr != Z_OK && zerr != Z_STREAM_END) return 0;   // truncated / corrupt gzip stream: no garbage index
-	if (names.empty()) return 0;
+	if (zerr != Z_OK && zerr != Z_STREAM_END) return false;   // truncated / corrupt gzip stream: no garbage index
+	return !names.empty();
+}
+
+// the parsed records as the pointer arrays the builders take (they point into names / seqs)
+struct FastxView {
 	std::vector<const char*> sp, np; std::vector<int64_t> ln;
-	for (size_t i = 0; i < names.size(); ++i) { sp.push_back(seqs[i].data()); np.push_back(names[i].c_str()); ln.push_back((int64_t)seqs[i].size()); }
-	return build_from_seqs(io, (int)names.size(), sp.data(), ln.data(), np.data(), n_threads);
+	FastxView(const std::vector<std::string> &names, const std::vector<std::string> &seqs) {
+		for (size_t i = 0; i < names.size(); ++i) { sp.push_back(seqs[i].data()); np.push_back(names[i].c_str()); ln.push_back((int64_t)seqs[i].size()); }
+	}
+};
+
+static mm355_index *build_from_fastx(const char *path, const mm355_idxopt_t *io, int n_threads)
+{
+	std::vector<std::string> names, seqs;
+	if (!parse_fastx(path, names, seqs)) return 0;
+	FastxView v(names, seqs);
+	return build_from_seqs(io, (int)names.size(), v.sp.data(), v.ln.data(), v.np.data(), n_threads);
 }
 
 static void finish_index(mm355_index *mi)
@@ -345,6 +357,85 @@ extern "C" int mm355_index_load(const char *path, const mm355_idxopt_t *io, int 
 	finish_index(mi);
 	*out = mi;
 	return 0;
+}
+
+void mm355_runtime_init(void);   // mm355_ctx.cpp
+
+// the FASTA / FASTQ branch of mm355_index_load with the build on GPU `device` (mm355_idxbuild.hip); an .mmi has nothing to build
+extern "C" int mm355_index_load_device(const char *path, const mm355_idxopt_t *io, int device, mm355_index_t **out)
+{
+	*out = 0;
+	mm355_runtime_init();   // (this entry can be the first HIP user of the process)
+	FILE *fp = fopen(path, "rb");
+	if (fp == 0) return MM355_EIO;
+	char magic[4]; size_t n = fread(magic, 1, 4, fp);
+	fclose(fp);
+	if (n == 4 && strncmp(magic, "MMI\2", 4) == 0) return mm355_index_load(path, io, 1, out);
+	if (n == 0) return MM355_EIO;
+	if (io->k <= 0 || io->k > 28 || io->w <= 0 || io->w >= 256) return MM355_EINVAL;
+	if (device < 0) return MM355_ENODEV;
+	std::vector<std::string> names, seqs;
+	if (!parse_fastx(path, names, seqs)) return MM355_EIO;
+	FastxView v(names, seqs);
+	return mm355_index_build_device(io, (int)names.size(), (const uint8_t *const *)v.sp.data(), v.ln.data(), v.np.data(), device, out);
+}
+
+// ------------------------------------------------------------------ MMI\2 writer (U:index.c::mm_idx_dump; the layout and the canonical
+// order are stated in include/mm355.h)
+// The bucket sections of an index with a host image: the occupied slots ordered by (bucket, key), p[] re-laid in that order.
+static int dump_buckets_host(const mm355_index *mi, FILE *fp)
+{
+	struct Ent { uint64_t bucket, key, val; };   // key as in the file: minimizer>>b<<1 | singleton
+	const uint64_t mask = (1ULL << mi->b) - 1;
+	std::vector<Ent> ents; ents.reserve((size_t)mi->n_distinct);
+	for (const mm355_slot &s : mi->slots)
+		if (s.key != UINT64_MAX) { const uint64_t minier = s.key >> 1; ents.push_back(Ent{ minier & mask, minier >> mi->b << 1 | (s.key & 1), s.val }); }
+	std::sort(ents.begin(), ents.end(), [](const Ent &p, const Ent &q) { return p.bucket < q.bucket || (p.bucket == q.bucket && p.key < q.key); });
+	std::vector<uint64_t> p, kv;
+	size_t i = 0;
+	for (uint64_t bkt = 0; bkt <= mask; ++bkt) {
+		p.clear(); kv.clear();
+		for (; i < ents.size() && ents[i].bucket == bkt; ++i) {
+			const Ent &e = ents[i];
+			kv.push_back(e.key);
+			if (e.key & 1) { kv.push_back(e.val); continue; }
+			const uint64_t start = e.val >> 32, cnt = (uint32_t)e.val;
+			kv.push_back((uint64_t)p.size() << 32 | cnt);
+			p.insert(p.end(), mi->pos.begin() + start, mi->pos.begin() + start + cnt);
+		}
+		if (p.size() > (size_t)INT32_MAX) return MM355_EUNSUP;   // the file's n is an int32, as minimap2's
+		const int32_t n = (int32_t)p.size(); const uint32_t size = (uint32_t)(kv.size() / 2);
+		fwrite(&n, 4, 1, fp); fwrite(p.data(), 8, p.size(), fp);
+		fwrite(&size, 4, 1, fp); fwrite(kv.data(), 8, kv.size(), fp);
+	}
+	return 0;
+}
+
+extern "C" int mm355_index_dump(const mm355_index_t *mi, const char *path)
+{
+	if (mi == 0) return MM355_ENOIDX;
+	if (path == 0) return MM355_EINVAL;
+	for (const std::string &nm : mi->names) if (nm.size() > 255) return MM355_EINVAL;   // minimap2 would truncate the name silently
+	FILE *fp = fopen(path, "wb");
+	if (fp == 0) return MM355_EIO;
+	(void)setvbuf(fp, 0, _IOFBF, 1 << 20);
+	const uint32_t x[5] = { (uint32_t)mi->w, (uint32_t)mi->k, (uint32_t)mi->b, mi->n_seq, (uint32_t)mi->flag };
+	fwrite("MMI\2", 1, 4, fp); fwrite(x, 4, 5, fp);
+	uint64_t sum_len = 0;
+	for (uint32_t i = 0; i < mi->n_seq; ++i) {
+		const uint8_t l = (uint8_t)mi->names[i].size();
+		fwrite(&l, 1, 1, fp); fwrite(mi->names[i].data(), 1, l, fp); fwrite(&mi->seq_len[i], 4, 1, fp);
+		sum_len += mi->seq_len[i];
+	}
+	int rc = mi->dev_resident? mm355_index_dump_buckets_device(mi, fp) : dump_buckets_host(mi, fp);
+	if (rc == 0 && !(mi->flag & 2)) {
+		const size_t n = (sum_len + 7) / 8;
+		if (mi->S.size() < n) rc = MM355_EINVAL; else fwrite(mi->S.data(), 4, n, fp);
+	}
+	if (rc == 0 && (fflush(fp) != 0 || ferror(fp))) rc = MM355_EIO;   // (a failed fwrite leaves the stream's error flag set)
+	if (fclose(fp) != 0 && rc == 0) rc = MM355_EIO;
+	if (rc) remove(path);
+	return rc;
 }
 
 extern "C" int mm355_index_build(const mm355_idxopt_t *io, int n_seq, const char *const *seqs, const int64_t *lens, const char *const *names, int n_threads, mm355_index_t **out)

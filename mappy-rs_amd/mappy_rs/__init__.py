@@ -441,11 +441,15 @@ class Aligner:
     `device` / `devices` are the only additions to the reference's constructor: the GPU (or list of GPUs of one node) that map
     this Aligner's reads.  With several devices the index is replicated into each one's HBM (mm355_upload) and `map_batch` deals
     its sub-batches to the contexts of all of them -- the GPU analogue of the reference's N worker threads over one shared index
-    (lib.rs:541-636).  Reads are independent: no collective."""
+    (lib.rs:541-636).  Reads are independent: no collective.
+
+    `build_on_gpu=True` (keyword-only) builds the index of a FASTA / FASTQ on devices[0] instead of on the host (mm355_index_load_device);
+    `save_index(path)` writes any index as an .mmi, so that a reference is indexed once and loaded from then on."""
 
     def __init__(self, fn_idx_in=None, preset=None, k=None, w=None, min_cnt=None, min_chain_score=None,
                  min_dp_score=None, bw=None, best_n=None, n_threads=3, fn_idx_out=None, max_frag_len=None,
-                 extra_flags=None, seq=None, scoring=None, device=0, devices=None, *, cigar=True, tags=False, name_key=None):
+                 extra_flags=None, seq=None, scoring=None, device=0, devices=None, *, cigar=True, tags=False, name_key=None,
+                 build_on_gpu=False):
         L = _ffi.lib()
         self._L = L
         self._idx = C.c_void_p()
@@ -498,7 +502,10 @@ class Aligner:
             raise NotImplementedError("Not Implemented")
         if fn_idx_in is None:
             raise RuntimeError("Did not create or open an index")
-        rc = L.mm355_index_load(str(fn_idx_in).encode(), C.byref(io), int(n_threads), C.byref(self._idx))
+        if build_on_gpu:                   # a FASTA / FASTQ is sketched, sorted and tabled on devices[0]; an .mmi loads as below
+            rc = L.mm355_index_load_device(str(fn_idx_in).encode(), C.byref(io), self._device, C.byref(self._idx))
+        else:
+            rc = L.mm355_index_load(str(fn_idx_in).encode(), C.byref(io), int(n_threads), C.byref(self._idx))
         if rc != 0 or not self._idx:
             raise RuntimeError("Did not create or open an index")
         L.mm355_mapopt_update(C.byref(mo), self._idx)
@@ -552,6 +559,13 @@ class Aligner:
         if n < 0:
             return None
         return bytes(buf[:n]).translate(bytes.maketrans(b"\x00\x01\x02\x03\x04", b"ACGTN")).decode()
+
+    def save_index(self, path):
+        """writes the index as a minimap2 .mmi (mm355_index_dump; the reference's `fn_idx_out`, lib.rs:391-394, as a method): any index, also
+        one built with build_on_gpu=True.  Aligner(path), minimap2 and mappy load the file."""
+        rc = self._L.mm355_index_dump(self._idx, os.fsencode(path))
+        if rc != 0:
+            raise RuntimeError("mm355: " + self._L.mm355_strerror(rc).decode())
 
     # ---- device context
     def _context(self):
