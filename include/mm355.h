@@ -123,6 +123,13 @@ int mm355_index_build_device(const mm355_idxopt_t *io, int n_seq, const uint8_t 
  * whose magic is MMI\2 is loaded as mm355_index_load loads it (a host image: there is nothing to build).  Same error codes as
  * mm355_index_load, plus MM355_ENODEV. */
 int mm355_index_load_device(const char *path, const mm355_idxopt_t *io, int device, mm355_index_t **out);
+/* an MMI\2 file loaded into the HBM of `device`: the result is device-resident exactly like an index from mm355_index_build_device
+ * (table and pos[] only in HBM; the host keeps header, names and the 4-bit sequence image).  The host reads the bucket headers, the bucket
+ * sections cross in pieces of 32 MB (MM355_IDXLOAD_PIECE=<bytes>) and are scattered into the table and pos[] on the device; no host table
+ * is ever made.  Not an MMI\2 file: MM355_EINVAL (nothing is built: use mm355_index_load_device).  Unreadable, truncated or inconsistent
+ * file: MM355_EIO.  MM355_ENODEV / ENOMEM / EHIP / EUNSUP (2^32 or more positions) as mm355_index_build_device.  Only the first part of a
+ * multi-part file is read, as by mm355_index_load. */
+int mm355_index_load_mmi_device(const char *path, int device, mm355_index_t **out);
 /* writes the index as a minimap2 MMI\2 file: replaces mm_idx_dump, the reference's fn_idx_out (lib.rs:391-394).  Any index: loaded from
  * .mmi, built on the host, or built on a device (its table is converted in HBM and copied out in fixed-size pieces).  The file is the one
  * U:index.c::mm_idx_load reads:

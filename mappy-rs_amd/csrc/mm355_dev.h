@@ -34,6 +34,21 @@ __device__ __forceinline__ uint32_t ref_code(const DevIndex &ix, uint32_t first,
 	for (uint32_t k = 0; k < cnt; ++k) if (o >= ix.nr[2 * (first + k)] && o < ix.nr[2 * (first + k) + 1]) c = 4;
 	return c;
 }
+// one key into the flat table while it is being filled (index build, .mmi load): the probe of the host's table_insert and of k_seed_lookup --
+// the 128-B line of the minimizer's hash, then the following lines -- claiming the first empty slot with a CAS on its key.  The table holds
+// more slots than keys are ever inserted (n / 0.55), so the probe ends.
+__device__ __forceinline__ void table_insert_dev(mm355_slot *slots, uint64_t line_mask, uint64_t minier, uint64_t key, uint64_t val)
+{
+	uint64_t line = mm_table_hash(minier) & line_mask;
+	for (;;) {
+		mm355_slot *ln = slots + line * MM355_SLOTS_PER_LINE;
+		for (int q = 0; q < MM355_SLOTS_PER_LINE; ++q) {
+			unsigned long long old = atomicCAS((unsigned long long*)&ln[q].key, ~0ULL, (unsigned long long)key);
+			if (old == ~0ULL) { ln[q].val = val; return; }
+		}
+		line = (line + 1) & line_mask;
+	}
+}
 #endif
 
 struct DevParams {           // subset of mm_mapopt_t the kernels read

@@ -61,6 +61,16 @@ inline uint32_t mm355_host_get(const mm355_index *mi, uint64_t minier, uint64_t 
 	}
 }
 
+// mm355_index.cpp: header and contig table of an .mmi into the index (mm355_mmiwalk.h; takes the header's vectors), name -> id and name ranks
+struct MmiHeader;
+void mm355_index_set_header(mm355_index *mi, MmiHeader &hd);
+void mm355_index_finish_names(mm355_index *mi);
+// mm355_idxbuild.hip, shared with mm355_idxload.hip: the end of making a device-resident index.  d_slots and d_pos are filled on `device`, dS is
+// the 4-bit sequence image there (mi->S holds the host's copy, or nothing with MM_I_NO_SEQ).  Registers the first replica on `device`, packs the
+// sequence to 2 bits and frees dS.  On failure dS is freed and the table buffers are still the caller's (mm355_index_free_build_buffers).
+int mm355_index_finish_device(mm355_index *mi, int device, void *dS);
+void mm355_index_free_build_buffers(mm355_index *mi);
+
 // mm355_idxdump.hip: the bucket sections of the .mmi of a device-resident index, converted to the canonical order in HBM and streamed to fp
 int mm355_index_dump_buckets_device(const mm355_index *mi, FILE *fp);
 

@@ -92,15 +92,7 @@ __global__ void k_table_insert(const uint64_t *keys, const uint64_t *vals, const
 	const uint64_t s = starts[r], minier = keys[s];
 	const uint32_t n = len[r];
 	const uint64_t key = minier << 1 | (n == 1? 1 : 0), val = n == 1? vals[s] : (moff[r] << 32 | n);
-	uint64_t line = mm_table_hash(minier) & line_mask;
-	for (;;) {
-		mm355_slot *ln = slots + line * MM355_SLOTS_PER_LINE;
-		for (int q = 0; q < MM355_SLOTS_PER_LINE; ++q) {
-			unsigned long long old = atomicCAS((unsigned long long*)&ln[q].key, ~0ULL, (unsigned long long)key);
-			if (old == ~0ULL) { ln[q].val = val; return; }
-		}
-		line = (line + 1) & line_mask;
-	}
+	table_insert_dev(slots, line_mask, minier, key, val);
 }
 __global__ void k_fill_pos(const uint64_t *vals, const uint32_t *run_id, const uint64_t *starts, const uint32_t *len, const uint64_t *moff, uint64_t n, uint64_t *pos)
 {
@@ -110,13 +102,41 @@ __global__ void k_fill_pos(const uint64_t *vals, const uint32_t *run_id, const u
 	if (len[r] > 1) pos[moff[r] + (i - starts[r])] = vals[i];
 }
 
-static void free_build_buffers(mm355_index *mi)   // a failed build: nothing was registered as a replica yet
+void mm355_index_free_build_buffers(mm355_index *mi)   // a failed build or load: nothing was registered as a replica yet
 {
 	(void)hipSetDevice(mi->dev_id);
 	if (mi->d_slots) (void)hipFree(mi->d_slots);
 	if (mi->d_pos) (void)hipFree(mi->d_pos);
 	if (mi->d_S) (void)hipFree(mi->d_S);
 	mi->d_slots = mi->d_pos = mi->d_S = 0;
+}
+
+int mm355_index_finish_device(mm355_index *mi, int device, void *dS)
+{
+	const size_t n_seq = mi->n_seq;
+	mi->d_S = dS;
+	mi->dev_resident = true; mi->dev_id = device;
+	// the build device holds the first replica; other devices get peer copies (mm355_upload / mm355_ctx_create)
+	mm355_replica rp; rp.dev = device; rp.slots = mi->d_slots; rp.pos = mi->d_pos; rp.S = mi->d_S;
+	// (the table buffers stay the caller's on failure, the replica frees only its own pieces)
+	auto fail = [&](int code) {
+		if (rp.seq_off) (void)hipFree(rp.seq_off); if (rp.seq_len) (void)hipFree(rp.seq_len); if (rp.name_rank) (void)hipFree(rp.name_rank);
+		if (rp.S2) (void)hipFree(rp.S2); if (rp.nr) (void)hipFree(rp.nr); if (rp.S) (void)hipFree(rp.S);
+		mi->d_S = 0; mi->dev_resident = false; return code; };
+	if (hipMalloc(&rp.seq_off, n_seq * 8 + 8) != hipSuccess || hipMalloc(&rp.seq_len, n_seq * 4 + 8) != hipSuccess ||
+	    hipMalloc(&rp.name_rank, n_seq * 4 + 8) != hipSuccess) return fail(MM355_ENOMEM);
+	if (mi->name_rank.size() != n_seq) return fail(MM355_EHIP);
+	if (hipMemcpy(rp.seq_off, mi->seq_off.data(), n_seq * 8, hipMemcpyHostToDevice) != hipSuccess ||
+	    hipMemcpy(rp.seq_len, mi->seq_len.data(), n_seq * 4, hipMemcpyHostToDevice) != hipSuccess ||
+	    hipMemcpy(rp.name_rank, mi->name_rank.data(), n_seq * 4, hipMemcpyHostToDevice) != hipSuccess) return fail(MM355_EHIP);
+	{   // 2-bit image + N-run table for the kernels; the 4-bit image leaves HBM (the host keeps it for mm_idx_getseq and the .mmi)
+		std::lock_guard<std::mutex> lk(mi->rep_mu);
+		const int rc = mm355_replica_pack2(mi, &rp);
+		if (rc) return fail(rc);
+		mi->d_S = rp.S;
+		mi->replicas.push_back(rp);
+	}
+	return 0;
 }
 
 #define GRID(n, b) dim3((unsigned)(((n) + (b) - 1) / (b)))
@@ -264,34 +284,11 @@ extern "C" int mm355_index_build_device(const mm355_idxopt_t *io, int n_seq, con
 	mi->S.resize(Sw);
 	if (hipMemcpy(mi->S.data(), dS, Sw * 4, hipMemcpyDeviceToHost) != hipSuccess) FAIL(MM355_EHIP);
 	IB_LOG("S to host");
-	mi->d_S = dS; dS = 0;
-	mi->dev_resident = true; mi->dev_id = device;
-	{   // the build device holds the first replica; other devices get peer copies (mm355_upload / mm355_ctx_create)
-		mm355_replica rp; rp.dev = device; rp.slots = mi->d_slots; rp.pos = mi->d_pos; rp.S = mi->d_S;
-		if (hipMalloc(&rp.seq_off, (size_t)n_seq * 8) != hipSuccess || hipMalloc(&rp.seq_len, (size_t)n_seq * 4) != hipSuccess ||
-		    hipMalloc(&rp.name_rank, (size_t)n_seq * 4) != hipSuccess) {
-			if (rp.seq_off) (void)hipFree(rp.seq_off); if (rp.seq_len) (void)hipFree(rp.seq_len); mi->dev_resident = false; FAIL(MM355_ENOMEM);
-		}
-		(void)hipMemcpy(rp.seq_off, mi->seq_off.data(), (size_t)n_seq * 8, hipMemcpyHostToDevice);
-		(void)hipMemcpy(rp.seq_len, mi->seq_len.data(), (size_t)n_seq * 4, hipMemcpyHostToDevice);
-		if (mi->name_rank.size() != (size_t)n_seq || hipMemcpy(rp.name_rank, mi->name_rank.data(), (size_t)n_seq * 4, hipMemcpyHostToDevice) != hipSuccess) {
-			(void)hipFree(rp.seq_off); (void)hipFree(rp.seq_len); (void)hipFree(rp.name_rank); mi->dev_resident = false; FAIL(MM355_EHIP);
-		}
-		{   // 2-bit image + N-run table for the kernels; the 4-bit image leaves HBM (the host keeps it for mm_idx_getseq and the .mmi)
-			std::lock_guard<std::mutex> lk(mi->rep_mu);
-			rc = mm355_replica_pack2(mi, &rp);
-			mi->d_S = rp.S;
-		}
-		if (rc) {   // (the table buffers still belong to the build: free_build_buffers releases them, the replica only its own pieces)
-			(void)hipFree(rp.seq_off); (void)hipFree(rp.seq_len); (void)hipFree(rp.name_rank); if (rp.S2) (void)hipFree(rp.S2); if (rp.nr) (void)hipFree(rp.nr);
-			mi->dev_resident = false; goto done;
-		}
-		mi->replicas.push_back(rp);
-	}
+	rc = mm355_index_finish_device(mi, device, dS); dS = 0;
 done:   // (FAIL leaves every scope it jumps out of, so every DBuf is freed on the way here or at the return)
 	if (dS) (void)hipFree(dS);
 	(void)hipStreamDestroy(st);
-	if (rc) { mi->dev_id = device; free_build_buffers(mi); delete mi; return rc; }
+	if (rc) { mi->dev_id = device; mm355_index_free_build_buffers(mi); delete mi; return rc; }
 	*out = mi;
 	return 0;
 }

@@ -15,6 +15,7 @@
 #include <atomic>
 #include <zlib.h>
 #include "mm355_host.h"
+#include "mm355_mmiwalk.h"
 
 #define mm_seq4_set(s, i, c) ((s)[(i)>>3] |= (uint32_t)(c) << (((i)&7)<<2))
 #define mm_seq4_get(s, i)    ((s)[(i)>>3] >> (((i)&7)<<2) & 0xf)
@@ -182,24 +183,19 @@ int mm355_index_from_pairs(mm355_index *mi, std::vector<mm128> &a)
 }
 
 // ------------------------------------------------------------------ MMI\2 reader (U:index.c::mm_idx_load)
+void mm355_index_set_header(mm355_index *mi, MmiHeader &hd)
+{
+	mi->w = hd.w, mi->k = hd.k, mi->b = hd.b, mi->n_seq = hd.n_seq, mi->flag = hd.flag;
+	mi->names.swap(hd.names); mi->seq_off.swap(hd.seq_off); mi->seq_len.swap(hd.seq_len);
+}
+
 static mm355_index *load_mmi(FILE *fp)
 {
-	char magic[4]; uint32_t x[5];
-	if (fread(magic, 1, 4, fp) != 4 || strncmp(magic, "MMI\2", 4) != 0) return 0;
-	if (fread(x, 4, 5, fp) != 5) return 0;
+	MmiHeader hd;
+	if (mmi_read_header(fp, &hd) != 0) return 0;   // (magic, the ranges of w, k and b, the contig table: mm355_mmiwalk.h)
 	mm355_index *mi = new mm355_index();
-	mi->w = x[0], mi->k = x[1], mi->b = x[2], mi->n_seq = x[3], mi->flag = x[4];
-	// a corrupt header must not drive the 1<<b bucket loop or the sketch kernels: U:sketch.c asserts 0 < w < 256, 0 < k <= 28; b <= 2k
-	if (x[0] < 1 || x[0] > 255 || x[1] < 1 || x[1] > 28 || x[2] > 28 || x[2] > 2 * x[1]) { delete mi; return 0; }
-	uint64_t sum_len = 0;
-	for (uint32_t i = 0; i < mi->n_seq; ++i) {
-		uint8_t l; uint32_t len; char nm[256];
-		if (fread(&l, 1, 1, fp) != 1) { delete mi; return 0; }
-		if (l && fread(nm, 1, l, fp) != l) { delete mi; return 0; }
-		if (fread(&len, 4, 1, fp) != 1) { delete mi; return 0; }
-		mi->names.emplace_back(nm, l); mi->seq_off.push_back(sum_len); mi->seq_len.push_back(len);
-		sum_len += len;
-	}
+	mm355_index_set_header(mi, hd);
+	const uint64_t sum_len = hd.sum_len;
 	// buckets -> (minimizer, positions); collected first to size the flat table
 	struct Ent { uint64_t minier, val; uint32_t n; };
 	std::vector<Ent> ents;
@@ -332,7 +328,7 @@ static mm355_index *build_from_fastx(const char *path, const mm355_idxopt_t *io,
 	return build_from_seqs(io, (int)names.size(), v.sp.data(), v.ln.data(), v.np.data(), n_threads);
 }
 
-static void finish_index(mm355_index *mi)
+void mm355_index_finish_names(mm355_index *mi)
 {
 	for (uint32_t i = 0; i < mi->n_seq; ++i) mi->name2id.emplace(mi->names[i], (int)i);   // first wins, as a hash put would report a duplicate
 	mm355_name_ranks(mi->names, mi->names_sorted, mi->name_rank);
@@ -354,7 +350,7 @@ extern "C" int mm355_index_load(const char *path, const mm355_idxopt_t *io, int 
 	}
 	if (fp) fclose(fp);
 	if (mi == 0 || mi->n_seq == 0) { delete mi; return MM355_EIO; }
-	finish_index(mi);
+	mm355_index_finish_names(mi);
 	*out = mi;
 	return 0;
 }
@@ -445,7 +441,7 @@ extern "C" int mm355_index_build(const mm355_idxopt_t *io, int n_seq, const char
 	if (io->k <= 0 || io->k > 28 || io->w <= 0 || io->w >= 256) return MM355_EINVAL;   // U:sketch.c::mm_sketch asserts the same ranges
 	mm355_index *mi = build_from_seqs(io, n_seq, seqs, lens, names, n_threads);
 	if (mi == 0) return MM355_EINVAL;
-	finish_index(mi);
+	mm355_index_finish_names(mi);
 	*out = mi;
 	return 0;
 }

@@ -38,10 +38,10 @@ struct HBuf {                 // pinned host staging buffer (grow-only)
 	HBuf(HBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = 0; o.cap = 0; }
 	HBuf &operator=(HBuf &&o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = 0; o.cap = 0; } return *this; }
 	~HBuf() { release(); }
-	int ensure(size_t bytes) {
+	int ensure(size_t bytes, int slack_div = 2) {   // (pinning costs time in proportion to the size: a buffer that never grows passes a large divisor)
 		if (bytes <= cap) return 0;
 		if (p) (void)hipHostFree(p);
-		size_t want = bytes + bytes / 2 + 4096;
+		size_t want = bytes + bytes / (size_t)slack_div + 4096;
 		if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { p = 0; cap = 0; return -1; }
 		cap = want; return 0;
 	}

@@ -444,12 +444,14 @@ class Aligner:
     (lib.rs:541-636).  Reads are independent: no collective.
 
     `build_on_gpu=True` (keyword-only) builds the index of a FASTA / FASTQ on devices[0] instead of on the host (mm355_index_load_device);
-    `save_index(path)` writes any index as an .mmi, so that a reference is indexed once and loaded from then on."""
+    `save_index(path)` writes any index as an .mmi, so that a reference is indexed once and loaded from then on.
+    `load_on_gpu=True` (keyword-only) loads an .mmi straight into the HBM of devices[0] (mm355_index_load_mmi_device): no host table is made.
+    A file that is not an .mmi takes the usual route, so `build_on_gpu=True, load_on_gpu=True` keeps the index on the GPU whatever the file is."""
 
     def __init__(self, fn_idx_in=None, preset=None, k=None, w=None, min_cnt=None, min_chain_score=None,
                  min_dp_score=None, bw=None, best_n=None, n_threads=3, fn_idx_out=None, max_frag_len=None,
                  extra_flags=None, seq=None, scoring=None, device=0, devices=None, *, cigar=True, tags=False, name_key=None,
-                 build_on_gpu=False):
+                 build_on_gpu=False, load_on_gpu=False):
         L = _ffi.lib()
         self._L = L
         self._idx = C.c_void_p()
@@ -502,10 +504,14 @@ class Aligner:
             raise NotImplementedError("Not Implemented")
         if fn_idx_in is None:
             raise RuntimeError("Did not create or open an index")
-        if build_on_gpu:                   # a FASTA / FASTQ is sketched, sorted and tabled on devices[0]; an .mmi loads as below
-            rc = L.mm355_index_load_device(str(fn_idx_in).encode(), C.byref(io), self._device, C.byref(self._idx))
-        else:
-            rc = L.mm355_index_load(str(fn_idx_in).encode(), C.byref(io), int(n_threads), C.byref(self._idx))
+        path = str(fn_idx_in).encode()
+        rc = _ffi.MM355_EINVAL
+        if load_on_gpu:                    # an .mmi goes into the HBM of devices[0] in pieces; MM355_EINVAL = not an .mmi: the routes below
+            rc = L.mm355_index_load_mmi_device(path, self._device, C.byref(self._idx))
+        if rc == _ffi.MM355_EINVAL and build_on_gpu:   # a FASTA / FASTQ is sketched, sorted and tabled on devices[0]; an .mmi loads as below
+            rc = L.mm355_index_load_device(path, C.byref(io), self._device, C.byref(self._idx))
+        elif rc == _ffi.MM355_EINVAL:
+            rc = L.mm355_index_load(path, C.byref(io), int(n_threads), C.byref(self._idx))
         if rc != 0 or not self._idx:
             raise RuntimeError("Did not create or open an index")
         L.mm355_mapopt_update(C.byref(mo), self._idx)

@@ -106,7 +106,7 @@ EXPORTS = [
     "mm355_free_hits", "mm355_batch_upload", "mm355_batch_select", "mm355_map_resident", "mm355_stage_sketch", "mm355_stage_anchors", "mm355_stage_chain", "mm355_stage_chains", "mm355_stage_rmq",
     "mm355_stage_dp", "mm355_stage_extra", "mm355_get_stats", "mm355_device_count", "mm355_device_synchronize", "mm355_strerror", "mm355_version",
     "mm355_map_batch_named", "mm355_batch_upload_named", "mm355_stage_anchors_named",
-    "mm355_index_load_device", "mm355_index_dump",
+    "mm355_index_load_device", "mm355_index_dump", "mm355_index_load_mmi_device",
 ]
 
 _LIB = None
@@ -129,6 +129,7 @@ def lib():
     L.mm355_index_build.argtypes = [C.POINTER(IdxOpt), C.c_int, C.POINTER(C.c_char_p), i64p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(vp)]
     L.mm355_index_build_device.argtypes = [C.POINTER(IdxOpt), C.c_int, C.POINTER(C.c_char_p), i64p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(vp)]
     L.mm355_index_load_device.argtypes = [C.c_char_p, C.POINTER(IdxOpt), C.c_int, C.POINTER(vp)]
+    L.mm355_index_load_mmi_device.argtypes = [C.c_char_p, C.c_int, C.POINTER(vp)]
     L.mm355_index_dump.argtypes = [vp, C.c_char_p]
     L.mm355_index_free.argtypes = [vp]
     L.mm355_index_info.argtypes = [vp, i32p, i32p, i32p, i32p, C.POINTER(C.c_uint32)]
