@@ -195,6 +195,48 @@ int mm355_map_batch_named(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_
 int mm355_batch_upload_named(mm355_ctx_t *ctx, int64_t n_reads, const char *const *seqs, const int32_t *lens, const char *const *names);
 void mm355_free_hits(mm355_hits_t *hits);
 
+/* --- PAF text: replaces the caller's own formatting loop over the hit records (one mappy_rs.paf_line per hit: minimap2's
+ * format.c::mm_write_paf + write_tags).  One line per row of hits[], in row order, each ending in '\n': the twelve columns; with a CIGAR
+ * NM ms AS nn; tp cm s1, and s2 on primaries; de with a CIGAR, otherwise dv when 0 <= div <= 1 ("0" when exactly zero, else C's %.4f of
+ * the double); zd when the split bits are set; rl; with a CIGAR cg:Z:, then cs:Z: / MD:Z: when cs_len / md_len >= 0.  The query name is
+ * the read's name up to its first space or tab; a read without a name prints "*" (minimap2 has no unnamed reads in a file).  A read
+ * without hits, or with status MM355_EEMPTY, writes nothing.  The text is produced on the device (mm355_paf.hip: a length kernel, a scan,
+ * a write kernel; query and contig names reach the GPU for this writer only) or on the host (mm355_paf.h, the same emitter run serially). */
+typedef struct {
+	int64_t n_reads, n_lines, n_text;
+	int64_t *line_off;              /* n_reads+1; lines of read i = text[line_off[i] .. line_off[i+1]) */
+	char *text;                     /* n_text bytes (and a NUL behind them) */
+	double ms_format;               /* wall time of the formatting step: uploads, kernels and the copy back, or the host loops */
+	int32_t on_device, reserved;    /* 1: the device formatter wrote the text */
+} mm355_text_t;
+#define MM355_PAF_AUTO 0            /* host below a hit count (128 with a CIGAR, 1024 chain-only: measured, see README; MM355_PAF_MIN_HITS=<n> overrides), device from there on */
+#define MM355_PAF_HOST 1
+#define MM355_PAF_DEVICE 2
+/* formats an existing batch result; hits->tags must be there (MM355_EINVAL otherwise, as for a row that points outside its arena, names
+ * no contig or, with a CIGAR, has block_len + n_ambi - n_gap + n_gapo == 0: de would divide by zero).  The %.4f of dv / de is exact for
+ * magnitudes below 2^50, which these fields cannot reach; beyond that the text is "inf", unlike printf.
+ * mo tells CIGAR mode from chain-only; qnames == NULL or qnames[i] == NULL: an unnamed read; qlens[i]: the read's length */
+int mm355_paf_format(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, const mm355_hits_t *hits, const char *const *qnames,
+                     const int32_t *qlens, int where, mm355_text_t **out);
+/* == mm355_map_batch_named with flags | MM355_OUT_TAGS, then mm355_paf_format, then mm355_free_hits: byte for byte */
+int mm355_map_batch_paf(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
+                        const char *const *names, int flags, int where, mm355_text_t **out);
+void mm355_free_text(mm355_text_t *t);
+
+/* --- streaming FASTA / FASTQ reader, plain or gzip: the record rules of the index builder's parser (the name ends at the first blank,
+ * multi-line sequences, a '+' line followed by quality as long as the sequence, CRLF).  A read set is cut into sub-batches without ever
+ * being in memory as a whole.  mm355_fastx_next returns the next records: at least one, at most max_reads, and no record that would take
+ * the sub-batch over max_bases unless it is its first (both limits >= 1); *out = NULL with return 0 at the end of the file.  MM355_EIO: the
+ * file cannot be opened, or its gzip stream is truncated or corrupt (reported when the reader gets there); MM355_EINVAL: a record of 2^31
+ * or more bases.  After an error every further call returns it again.  The reads own what they point to: names[i] is NUL-terminated,
+ * seqs[i] has lens[i] bases. */
+typedef struct mm355_fastx mm355_fastx_t;
+typedef struct { int64_t n; const char *const *seqs; const int32_t *lens; const char *const *names; } mm355_reads_t;
+int mm355_fastx_open(const char *path, mm355_fastx_t **out);
+int mm355_fastx_next(mm355_fastx_t *fx, int64_t max_reads, int64_t max_bases, mm355_reads_t **out);
+void mm355_reads_free(mm355_reads_t *r);
+void mm355_fastx_close(mm355_fastx_t *fx);
+
 /* --- per-stage entry points (same kernels as mm355_map_batch; used by the parity tests and
  * by bench.py to time one kernel with HIP events).  Outputs are caller-allocated host buffers. --- */
 typedef struct {

@@ -12,7 +12,8 @@
 
 // HBM copy of the index on one device (flat table, pos[], the reference packed to 2 bits per base + its sorted N-run intervals, contig
 // offsets/lengths).  Every context of that device shares it.  S (the .mmi's 4-bit image) only exists while the replica is being made.
-struct mm355_replica { int dev = -1; void *slots = 0, *pos = 0, *S = 0, *seq_off = 0, *seq_len = 0, *S2 = 0, *nr = 0, *name_rank = 0; uint32_t n_nr = 0; };
+struct mm355_replica { int dev = -1; void *slots = 0, *pos = 0, *S = 0, *seq_off = 0, *seq_len = 0, *S2 = 0, *nr = 0, *name_rank = 0; uint32_t n_nr = 0;
+	void *tname = 0, *tname_off = 0; };   // contig-name bytes and their n_seq + 1 offsets: made on first use by the PAF writer (mm355_paf.hip), for nothing else
 
 struct mm355_index {
 	int32_t b, w, k, flag;
@@ -43,6 +44,8 @@ int mm355_replica_pack2(const mm355_index *mi, mm355_replica *rp);
 // finds the replica of `dev`, creating it when absent: H2D from the host image, or a peer copy from the device the index was built on
 int mm355_index_replica(const mm355_index *mi, int dev, mm355_replica *out);
 void mm355_index_free_replicas(mm355_index *mi);
+// the contig names of the replica of `dev` in HBM (uploaded by the first call, owned by the replica): mm355_paf.hip
+int mm355_replica_tnames(const mm355_index *mi, int dev, const char **bytes, const int64_t **off);
 
 // lookup on the host image of the flat table (used by tests of the table itself; the product looks up on the device)
 inline uint32_t mm355_host_get(const mm355_index *mi, uint64_t minier, uint64_t *val)

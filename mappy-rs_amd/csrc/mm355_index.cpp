@@ -277,39 +277,146 @@ static mm355_index *build_from_seqs(const mm355_idxopt_t *io, int n_seq, const c
 	return mi;
 }
 
-// FASTA/FASTQ, plain or gzip-compressed (U:bseq.c reads through zlib's gzFile, which passes plain files through unchanged)
+// FASTA/FASTQ, plain or gzip-compressed (U:bseq.c reads through zlib's gzFile, which passes plain files through unchanged).  One record
+// loop serves the index builders (parse_fastx: the whole file) and the streaming reader of read sets (mm355_fastx_next).
+struct mm355_fastx {
+	gzFile gz = 0;
+	std::string line, next_name;          // line: a line that straddles two blocks; next_name: the header line that ended the previous record
+	std::vector<char> buf = std::vector<char>(1 << 20);   // the file is read in blocks and cut into lines here (gzgets costs a call and a strlen per line)
+	size_t pos = 0, end = 0;
+	bool in_qual = false, is_fq = false, eof = false, have_next = false;
+	size_t l_qual = 0; int64_t n_rec = 0;
+	// mm355_fastx_next only: the record that did not fit the previous sub-batch, and the error the reader stopped at
+	std::string held_name, held_seq; bool held = false; int err = 0;
+	~mm355_fastx() { if (gz) gzclose(gz); }
+};
+
+// the next line of any length, without its line end (LF or CRLF): *p / *n point into the block, or into fx->line when the line straddles blocks.
+// false at the end of the file (a last line without a newline is returned first)
+static bool fastx_line(mm355_fastx *fx, const char **p, size_t *n)
+{
+	bool joined = false;
+	for (;;) {
+		const char *beg = fx->buf.data() + fx->pos;
+		const char *nl = fx->end > fx->pos? (const char*)memchr(beg, '\n', fx->end - fx->pos) : 0;
+		if (nl) {
+			if (joined) { fx->line.append(beg, (size_t)(nl - beg)); *p = fx->line.data(); *n = fx->line.size(); }
+			else { *p = beg; *n = (size_t)(nl - beg); }
+			fx->pos = (size_t)(nl + 1 - fx->buf.data());
+			break;
+		}
+		if (!joined) { fx->line.clear(); joined = true; }
+		fx->line.append(beg, fx->end - fx->pos);
+		fx->pos = fx->end = 0;
+		const int r = fx->eof? 0 : gzread(fx->gz, fx->buf.data(), (unsigned)fx->buf.size());
+		if (r <= 0) {
+			fx->eof = true;
+			if (fx->line.empty()) return false;
+			*p = fx->line.data(); *n = fx->line.size();
+			break;
+		}
+		fx->end = (size_t)r;
+	}
+	while (*n > 0 && ((*p)[*n - 1] == '\n' || (*p)[*n - 1] == '\r')) --*n;
+	return true;
+}
+
+// the next record: 1, name filled and the bases APPENDED to seq (a sub-batch collects its reads back to back without a copy); 0 at the end of the
+// file; MM355_EIO when the gzip stream is truncated or corrupt (the records before that point have been handed out by then: a caller that must
+// not use them checks the last return value)
+static int fastx_record(mm355_fastx *fx, std::string &name, std::string &seq)
+{
+	const size_t start = seq.size();
+	bool have = false;
+	if (fx->have_next) { name.swap(fx->next_name); fx->have_next = false; have = true; }
+	const char *line; size_t n;
+	while (fastx_line(fx, &line, &n)) {
+		if (fx->in_qual) { fx->l_qual += n; if (fx->l_qual >= seq.size() - start) fx->in_qual = false; continue; }
+		if (n > 0 && (line[0] == '>' || (line[0] == '@' && (fx->n_rec == 0 || fx->is_fq)))) {
+			fx->is_fq = line[0] == '@';
+			size_t e = 1; while (e < n && line[e] != ' ' && line[e] != '\t') ++e;
+			++fx->n_rec;
+			if (have) { fx->next_name.assign(line + 1, e - 1); fx->have_next = true; return 1; }
+			name.assign(line + 1, e - 1); have = true;
+		} else if (n > 0 && line[0] == '+' && fx->is_fq) { fx->in_qual = have && seq.size() > start; fx->l_qual = 0; }
+		else if (have) {
+			size_t n_blank = 0;
+			for (size_t i = 0; i < n; ++i) n_blank += line[i] <= ' ';
+			if (n_blank == 0) seq.append(line, n);      // (the usual line: one copy)
+			else for (size_t i = 0; i < n; ++i) if (line[i] > ' ') seq.push_back(line[i]);
+		}
+	}
+	int zerr = 0; (void)gzerror(fx->gz, &zerr);
+	if (zerr != Z_OK && zerr != Z_STREAM_END) return MM355_EIO;   // truncated / corrupt gzip stream: no garbage index, no half a read set
+	return have? 1 : 0;
+}
+
 static bool parse_fastx(const char *path, std::vector<std::string> &names, std::vector<std::string> &seqs)
 {
-	gzFile gz = gzopen(path, "rb");
-	if (gz == 0) return false;
-	(void)gzbuffer(gz, 1 << 20);
-	std::string line;
-	std::vector<char> buf(1 << 16);
-	bool in_qual = false, is_fq = false, eof = false; size_t l_qual = 0;
-	while (!eof) {
-		line.clear();
-		for (;;) {   // one line of any length
-			if (gzgets(gz, buf.data(), (int)buf.size()) == 0) { eof = true; break; }
-			const size_t l = strlen(buf.data());
-			line.append(buf.data(), l);
-			if (l > 0 && buf[l - 1] == '\n') break;
+	mm355_fastx fx;
+	fx.gz = gzopen(path, "rb");
+	if (fx.gz == 0) return false;
+	(void)gzbuffer(fx.gz, 1 << 20);
+	std::string name, seq;
+	int rc;
+	while ((rc = fastx_record(&fx, name, seq)) == 1) { names.push_back(name); seqs.emplace_back(); seqs.back().swap(seq); }
+	return rc == 0 && !names.empty();
+}
+
+extern "C" int mm355_fastx_open(const char *path, mm355_fastx_t **out)
+{
+	*out = 0;
+	if (path == 0) return MM355_EINVAL;
+	mm355_fastx *fx = new mm355_fastx();
+	fx->gz = gzopen(path, "rb");
+	if (fx->gz == 0) { delete fx; return MM355_EIO; }
+	(void)gzbuffer(fx->gz, 1 << 20);
+	*out = fx;
+	return 0;
+}
+
+extern "C" void mm355_fastx_close(mm355_fastx_t *fx) { delete fx; }
+
+// a sub-batch of reads and everything its pointers point to (mm355_reads_t is its first member: mm355_reads_free gets the box back)
+struct ReadsBox {
+	mm355_reads_t r;
+	std::string seq_bytes, name_bytes;       // sequences back to back; names, each with its NUL
+	std::vector<size_t> seq_at, name_at;
+	std::vector<const char*> sp, np; std::vector<int32_t> ln;
+};
+
+extern "C" void mm355_reads_free(mm355_reads_t *r) { delete (ReadsBox*)r; }
+
+extern "C" int mm355_fastx_next(mm355_fastx_t *fx, int64_t max_reads, int64_t max_bases, mm355_reads_t **out)
+{
+	*out = 0;
+	if (fx == 0 || max_reads < 1 || max_bases < 1) return MM355_EINVAL;
+	if (fx->err) return fx->err;
+	ReadsBox *B = new ReadsBox();
+	std::string name;
+	while ((int64_t)B->ln.size() < max_reads) {
+		const size_t at = B->seq_bytes.size();
+		if (fx->held) { name.swap(fx->held_name); B->seq_bytes += fx->held_seq; fx->held_seq.clear(); fx->held = false; }
+		else {
+			const int rc = fastx_record(fx, name, B->seq_bytes);      // (the bases land behind the sub-batch's other reads)
+			if (rc == 0) break;
+			if (rc < 0) { fx->err = rc; break; }
+			if (B->seq_bytes.size() - at >= (size_t)1 << 31) { fx->err = MM355_EINVAL; break; }
 		}
-		if (eof && line.empty()) break;
-		size_t n = line.size();
-		while (n > 0 && (line[n-1] == '\n' || line[n-1] == '\r')) --n;
-		line.resize(n);
-		if (in_qual) { l_qual += n; if (l_qual >= seqs.back().size()) in_qual = false; continue; }
-		if (n > 0 && (line[0] == '>' || (line[0] == '@' && (names.empty() || is_fq)))) {
-			is_fq = line[0] == '@';
-			size_t e = 1; while (e < n && line[e] != ' ' && line[e] != '\t') ++e;
-			names.emplace_back(line, 1, e - 1); seqs.emplace_back();
-		} else if (n > 0 && line[0] == '+' && is_fq) { in_qual = !seqs.empty() && seqs.back().size() > 0; l_qual = 0; }
-		else if (!names.empty()) { for (size_t i = 0; i < n; ++i) if (line[i] > ' ') seqs.back().push_back(line[i]); }
+		if (!B->ln.empty() && (int64_t)B->seq_bytes.size() > max_bases) {   // over the base limit and not the first: it opens the next sub-batch
+			fx->held_name.swap(name); fx->held_seq.assign(B->seq_bytes, at, std::string::npos); fx->held = true;
+			B->seq_bytes.resize(at);
+			break;
+		}
+		B->seq_at.push_back(at);
+		B->name_at.push_back(B->name_bytes.size()); B->name_bytes.append(name.c_str(), name.size() + 1);
+		B->ln.push_back((int32_t)(B->seq_bytes.size() - at));
 	}
-	int zerr = 0; (void)gzerror(gz, &zerr);
-	gzclose(gz);
-	if (zerr != Z_OK && zerr != Z_STREAM_END) return false;   // truncated / corrupt gzip stream: no garbage index
-	return !names.empty();
+	if (fx->err || B->ln.empty()) { delete B; return fx->err; }
+	for (size_t i = 0; i < B->ln.size(); ++i) { B->sp.push_back(B->seq_bytes.data() + B->seq_at[i]); B->np.push_back(B->name_bytes.data() + B->name_at[i]); }
+	B->r.n = (int64_t)B->ln.size(); B->r.seqs = B->sp.data(); B->r.lens = B->ln.data(); B->r.names = B->np.data();
+	*out = &B->r;
+	return 0;
 }
 
 // the parsed records as the pointer arrays the builders take (they point into names / seqs)

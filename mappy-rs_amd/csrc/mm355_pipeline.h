@@ -134,6 +134,7 @@ struct mm355_ctx : mm355_streams {
 	DBuf x_jobs, x_cig, x_cs, x_out, x_dense; HBuf h_xjobs, h_xcig, h_xout, h_xcs;   // k_extra (mm_update_extra's walk + cs on the device)
 	DBuf logt, regs_scr, regs_in; HBuf h_regs_in, h_regs_out;  // chain-only region stage (mm355_regs.hip): host-logf table, scratch + rows, read tables
 	bool logt_ok = false;
+	DBuf paf_in, paf_work, paf_text; HBuf h_paf_in, h_paf_out;   // PAF writer (mm355_paf.hip): rows + arenas + names up, lengths / offsets / scan space, the text; pinned staging both ways
 	mm355_stats_t stats;
 	mm355_timer_book timers;           // lazy stage timers (EvTimer, mm355_kt)
 	unsigned long long pairs_land[64] = {};   // landing zone of the chain stage's pair counters (mm355_run_backtrack)

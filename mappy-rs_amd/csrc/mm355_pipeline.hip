@@ -174,6 +174,7 @@ void mm355_index_free_replicas(mm355_index *mi)
 		if (r.slots) (void)hipFree(r.slots); if (r.pos) (void)hipFree(r.pos); if (r.S) (void)hipFree(r.S);
 		if (r.seq_off) (void)hipFree(r.seq_off); if (r.seq_len) (void)hipFree(r.seq_len); if (r.S2) (void)hipFree(r.S2); if (r.nr) (void)hipFree(r.nr);
 		if (r.name_rank) (void)hipFree(r.name_rank);
+		if (r.tname) (void)hipFree(r.tname); if (r.tname_off) (void)hipFree(r.tname_off);
 	}
 	if (!mi->replicas.empty()) (void)hipSetDevice(prev);
 	mi->replicas.clear();

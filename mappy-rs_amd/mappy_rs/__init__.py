@@ -810,6 +810,195 @@ class Aligner:
         st.threads = list(workers) + [tf]
         return AlignmentBatchResultIter(st)
 
+    # ---- PAF text (mm355_map_batch_paf): the lines of mappy_rs.paf_line, formatted by the library -- on the device for large batches
+    def _paf_flags(self, cs, MD):
+        if (cs or MD) and not self._mo.flag & 4:
+            raise ValueError("cs / MD need base-level alignment: this Aligner was created with cigar=False")
+        return (_ffi.OUT_CS if cs else 0) | (_ffi.OUT_MD if MD else 0) | _ffi.OUT_TAGS
+
+    def map_paf(self, seqs, names=None, cs=False, MD=False, *, where=_ffi.PAF_AUTO):
+        """the PAF lines of `seqs` (a list of str) as bytes, in input order: one mm355_map_batch_paf call, no Mapping objects.  Each line is
+        paf_line() of the record map() would return, tagged whatever `tags=` was; names[i] (str or None) is the read's query name as in
+        map(seq, name=...), printed up to its first blank; an unnamed read prints `*`.  An empty sequence writes nothing.
+        where (keyword-only): _ffi.PAF_AUTO (the library picks the formatter by the hit count), PAF_HOST or PAF_DEVICE; which one wrote the
+        text of the last call is kept in `paf_on_device`."""
+        flags = self._paf_flags(cs, MD)
+        seqs = list(seqs)
+        for s in seqs:
+            if not isinstance(s, str):
+                raise TypeError("argument 'seq': 'bytes' object cannot be converted to 'PyString'" if isinstance(s, bytes)
+                                else "argument 'seq' must be str")
+        if names is not None:
+            names = list(names)
+            if len(names) != len(seqs) or not all(nm is None or isinstance(nm, str) for nm in names):
+                raise ValueError("`names` must hold a string or None for every read")
+        L = self._L
+        packed, narr = _ffi.pack_reads(seqs), _ffi.pack_names(names)
+        tp = C.POINTER(_ffi.Text)()
+        with self._lock:
+            rc = L.mm355_map_batch_paf(self._context(), C.byref(self._mo), len(seqs), packed.arr, packed.lens, narr, flags, int(where),
+                                       C.byref(tp))
+        if rc != 0:
+            raise RuntimeError(L.mm355_strerror(rc).decode())
+        try:
+            self.paf_on_device = bool(tp.contents.on_device)
+            return bytes(_ffi.text_view(tp))
+        finally:
+            L.mm355_free_text(tp)
+
+    paf_on_device = None              # whether the device formatter wrote the text of the last map_paf call
+
+    def map_file(self, reads_path, out_path, cs=False, MD=False, n_threads=None, sub_batch_reads=SUB_BATCH_READS, *, where=_ffi.PAF_AUTO):
+        """maps a FASTA / FASTQ file of reads (plain or gzip) to a PAF file, lines in input order -- minimap2's command line from a read set to
+        its overlaps or alignments.  A reader thread cuts sub-batches of `sub_batch_reads` reads (and at most SUB_BATCH_BASES bases) with the
+        library's streaming reader; up to min(n_threads, 8) workers per GPU (n_threads=None: enable_threading's value, or 1), each with a
+        context of the pool, map and format them (mm355_map_batch_paf, GIL released); this thread writes the texts in input order.  At most
+        2 x workers sub-batches exist at any time, as reads or as text: memory does not grow with the file.  No Python work per read or hit.
+        The text is written to `out_path` + ".part" and renamed when it is complete: a failure stops the rest, removes the partly written
+        file and is raised, and a file that was at `out_path` before is still there.  `where` (keyword-only): as for map_paf.
+        Returns {n_reads, n_bases, n_lines, n_sub_batches, seconds} (and ms_format, n_on_device: the formatting step summed over the
+        sub-batches, and how many of them the device formatted)."""
+        flags = self._paf_flags(cs, MD)
+        L = self._L
+        nt = self._n_threads if n_threads is None else int(n_threads)
+        n_workers = max(1, min(nt, 8)) * len(self._devices)
+        sub_batch_reads = int(sub_batch_reads)
+        if sub_batch_reads < 1:
+            raise ValueError("`sub_batch_reads` must be at least 1")
+        t0 = time.perf_counter()
+        fx = C.c_void_p()
+        rc = L.mm355_fastx_open(os.fsencode(reads_path), C.byref(fx))
+        if rc != 0:
+            raise RuntimeError("%s: %s" % (reads_path, L.mm355_strerror(rc).decode()))
+        part = os.fspath(out_path) + (b".part" if isinstance(os.fspath(out_path), bytes) else ".part")
+        try:
+            out = open(part, "wb")          # (an unwritable path raises here: nothing has run, no file is left)
+        except BaseException:
+            L.mm355_fastx_close(fx)
+            raise
+        tokens = threading.Semaphore(2 * n_workers)     # one per sub-batch in existence, from the read to the written text
+        work = queue.Queue()
+        cv = threading.Condition()
+        done, errors, workers = {}, [], []
+        cancel = threading.Event()
+        st = {"n_sub": None, "n_reads": 0, "n_bases": 0}
+        mo, where = self._mo, int(where)
+        acquire, release = self._ctx_acquire, self._ctx_release
+
+        def fail(e):
+            errors.append(e)
+            cancel.set()
+            with cv:
+                cv.notify_all()
+
+        def worker(slot):
+            ctx = None
+            try:
+                ctx = acquire(slot)
+                while True:
+                    item = work.get()
+                    if item is None:
+                        return
+                    k, rp = item
+                    try:
+                        if cancel.is_set():
+                            continue
+                        r = rp.contents
+                        n = int(r.n)
+                        n_bases = int(np.ctypeslib.as_array(r.lens, shape=(n,)).sum(dtype=np.int64))
+                        tp = C.POINTER(_ffi.Text)()
+                        rc = L.mm355_map_batch_paf(ctx[1], C.byref(mo), n, r.seqs, r.lens, r.names, flags, where, C.byref(tp))
+                    finally:
+                        L.mm355_reads_free(rp)
+                    if rc != 0:
+                        raise RuntimeError(L.mm355_strerror(rc).decode())
+                    with cv:
+                        st["n_reads"] += n
+                        st["n_bases"] += n_bases
+                        done[k] = tp
+                        cv.notify_all()
+            except Exception as e:
+                fail(e)
+            finally:
+                if ctx is not None:
+                    release(ctx)
+
+        def reader():
+            k = 0
+            try:
+                while not cancel.is_set():
+                    if not tokens.acquire(timeout=0.2):
+                        continue
+                    rp = C.POINTER(_ffi.Reads)()
+                    rc = L.mm355_fastx_next(fx, sub_batch_reads, SUB_BATCH_BASES, C.byref(rp))
+                    if rc != 0:
+                        raise RuntimeError("%s: %s" % (reads_path, L.mm355_strerror(rc).decode()))
+                    if not rp:
+                        break
+                    work.put((k, rp))
+                    k += 1
+                    if len(workers) < min(n_workers, k):
+                        t = threading.Thread(target=worker, args=(len(workers),), daemon=True)
+                        workers.append(t)
+                        t.start()
+            except Exception as e:
+                fail(e)
+            finally:
+                for _ in workers:
+                    work.put(None)
+                with cv:
+                    st["n_sub"] = k
+                    cv.notify_all()
+
+        n_lines = n_dev = nxt = 0
+        ms_format = 0.0
+        rd = None
+        try:
+            self._names()
+            rd = threading.Thread(target=reader, daemon=True)
+            rd.start()
+            while True:
+                with cv:
+                    while nxt not in done and not cancel.is_set() and (st["n_sub"] is None or nxt < st["n_sub"]):
+                        cv.wait(0.2)
+                    if cancel.is_set() or nxt not in done:
+                        break
+                    tp = done.pop(nxt)
+                try:
+                    t = tp.contents
+                    n_lines += int(t.n_lines); n_dev += int(t.on_device); ms_format += float(t.ms_format)
+                    out.write(_ffi.text_view(tp))
+                finally:
+                    L.mm355_free_text(tp)
+                    tokens.release()
+                nxt += 1
+            if errors:
+                raise errors[0]
+            out.close()
+            os.replace(part, out_path)
+        except BaseException:
+            cancel.set()
+            out.close()
+            try:
+                os.remove(part)
+            except OSError:
+                pass
+            raise
+        finally:
+            if rd is not None:
+                rd.join()
+            for t in workers:
+                t.join()
+            while not work.empty():           # what nobody took: reads of sub-batches after the failure
+                item = work.get()
+                if item is not None:
+                    L.mm355_reads_free(item[1])
+            for tp in done.values():
+                L.mm355_free_text(tp)
+            L.mm355_fastx_close(fx)
+        return {"n_reads": st["n_reads"], "n_bases": st["n_bases"], "n_lines": n_lines, "n_sub_batches": st["n_sub"],
+                "seconds": time.perf_counter() - t0, "ms_format": ms_format, "n_on_device": n_dev}
+
     def _stage_runner(self):
         """per-stage access to the same kernels (parity tests, kernel bench)"""
         return _ffi.StageRunner(self._idx, self._mo, self._device)

@@ -18,6 +18,7 @@ MM355_ENODEV, MM355_EINVAL, MM355_ENOMEM, MM355_EIO, MM355_ENOIDX, MM355_EEMPTY,
     -1, -2, -3, -4, -5, -6, -7, -8
 OUT_CS, OUT_MD, OUT_TAGS = 1, 2, 4
 TAG_INV, TAG_SAM_PRI, TAG_SPLIT_SHIFT = 1, 2, 2      # mm355_tags_t::flags
+PAF_AUTO, PAF_HOST, PAF_DEVICE = 0, 1, 2             # `where` of mm355_paf_format / mm355_map_batch_paf
 
 
 class IdxOpt(C.Structure):
@@ -65,6 +66,15 @@ class Hits(C.Structure):
                 ("tags", C.POINTER(Tags))]      # parallel to hits; NULL unless OUT_TAGS was asked for
 
 
+class Text(C.Structure):       # mm355_text_t: the PAF lines of one batch
+    _fields_ = [("n_reads", C.c_int64), ("n_lines", C.c_int64), ("n_text", C.c_int64), ("line_off", C.POINTER(C.c_int64)),
+                ("text", C.POINTER(C.c_char)), ("ms_format", C.c_double), ("on_device", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Reads(C.Structure):      # mm355_reads_t: one sub-batch of the streaming FASTA / FASTQ reader
+    _fields_ = [("n", C.c_int64), ("seqs", C.POINTER(C.c_char_p)), ("lens", C.POINTER(C.c_int32)), ("names", C.POINTER(C.c_char_p))]
+
+
 class Stats(C.Structure):
     _fields_ = [("n_reads", C.c_int64), ("n_bases", C.c_int64), ("n_mz", C.c_int64), ("n_hit", C.c_int64),
                 ("n_a", C.c_int64), ("n_a_multi", C.c_int64), ("chain_pairs", C.c_int64), ("dp_cells", C.c_int64),
@@ -107,6 +117,7 @@ EXPORTS = [
     "mm355_stage_dp", "mm355_stage_extra", "mm355_get_stats", "mm355_device_count", "mm355_device_synchronize", "mm355_strerror", "mm355_version",
     "mm355_map_batch_named", "mm355_batch_upload_named", "mm355_stage_anchors_named",
     "mm355_index_load_device", "mm355_index_dump", "mm355_index_load_mmi_device",
+    "mm355_paf_format", "mm355_map_batch_paf", "mm355_free_text", "mm355_fastx_open", "mm355_fastx_next", "mm355_reads_free", "mm355_fastx_close",
 ]
 
 _LIB = None
@@ -149,6 +160,17 @@ def lib():
     L.mm355_batch_upload_named.argtypes = [vp, C.c_int64, C.POINTER(C.c_char_p), i32p, C.POINTER(C.c_char_p)]
     L.mm355_stage_anchors_named.argtypes = [vp, C.POINTER(MapOpt), C.c_int64, C.POINTER(C.c_char_p), i32p, C.POINTER(C.c_char_p), C.c_int, vp, vp, C.c_int64, vp, vp]
     L.mm355_free_hits.argtypes = [C.POINTER(Hits)]
+    L.mm355_paf_format.argtypes = [vp, C.POINTER(MapOpt), C.POINTER(Hits), C.POINTER(C.c_char_p), i32p, C.c_int, C.POINTER(C.POINTER(Text))]
+    L.mm355_map_batch_paf.argtypes = [vp, C.POINTER(MapOpt), C.c_int64, C.POINTER(C.c_char_p), i32p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
+                                      C.POINTER(C.POINTER(Text))]
+    L.mm355_free_text.argtypes = [C.POINTER(Text)]
+    L.mm355_free_text.restype = None
+    L.mm355_fastx_open.argtypes = [C.c_char_p, C.POINTER(vp)]
+    L.mm355_fastx_next.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(C.POINTER(Reads))]
+    L.mm355_reads_free.argtypes = [C.POINTER(Reads)]
+    L.mm355_reads_free.restype = None
+    L.mm355_fastx_close.argtypes = [vp]
+    L.mm355_fastx_close.restype = None
     L.mm355_batch_upload.argtypes = [vp, C.c_int64, C.POINTER(C.c_char_p), i32p]
     L.mm355_batch_select.argtypes = [vp, C.c_int]
     L.mm355_map_resident.argtypes = [vp, C.POINTER(MapOpt), C.c_int, C.POINTER(C.POINTER(Hits))]
@@ -272,6 +294,12 @@ def map_raw(L, ctx, mo, reads, flags, names=None, entry="batch", raise_on_error=
         raise Mm355Error(rc)
     v = take_hits(L, hp, int(hp.contents.n_reads)) if rc == 0 else None
     return v if raise_on_error else (rc, v)
+
+
+def text_view(tp):
+    """POINTER(Text) -> a memoryview of its n_text bytes, no copy (valid until mm355_free_text)"""
+    n = int(tp.contents.n_text)
+    return memoryview((C.c_char * n).from_address(C.addressof(tp.contents.text.contents))) if n else memoryview(b"")
 
 
 def get_stats(L, ctx):
