@@ -223,6 +223,42 @@ int mm355_map_batch_paf(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_re
                         const char *const *names, int flags, int where, mm355_text_t **out);
 void mm355_free_text(mm355_text_t *t);
 
+/* --- SAM text: minimap2 -a without a header (format.c::mm_write_sam3, write_sam_cigar, sam_write_sq, write_tags of 2.26), one line per row
+ * of hits[] in row order, and one unmapped record for a read without rows.  Needs MM_F_CIGAR in mo->flag and hits->tags.  With qlen the
+ * read's length, qs / qe / rev (strand < 0) of the row, tab-separated, each line ending in '\n':
+ *   QNAME  the read's name up to its first space or tab; "*" for an unnamed read
+ *   FLAG   0x10 if rev; 0x100 if !is_primary, otherwise 0x800 if the tags row lacks MM355_TAG_SAM_PRI
+ *   RNAME, POS = target_start + 1, MAPQ (unsigned)
+ *   CIGAR  clip5 = rev ? qlen - qe : qs, clip3 = rev ? qs : qlen - qe, each printed when non-zero around the CIGAR words, with the letter H
+ *          when FLAG & 0x800 and soft clipping is off, otherwise S (a secondary too); "*" for a row with n_cigar == 0; no long-CIGAR handling
+ *   RNEXT PNEXT TLEN   "*", 0, 0
+ *   SEQ QUAL   FLAG & 0x900 == 0 or soft clipping on: the whole read, reversed and complemented if rev, and the whole quality, reversed if
+ *          rev ("*" without one); otherwise a secondary: "*", "*"; otherwise (supplementary, hard-clipped) read[qs:qe] and qual[qs:qe]
+ *          treated the same way.  Complement: bytes below 128, case kept, A<->T C<->G R<->Y K<->M B<->V D<->H, U->A, everything else
+ *          unchanged.  The bytes are the caller's; nothing is upper-cased.
+ *   tags   NM ms AS nn tp cm s1, s2 on primaries, de, zd when split (the block PAF prints); SA:Z: on a row with is_primary when the read has
+ *          another row q with is_primary and n_cigar > 0: for each such q in row order "rname,pos,strand,cigar,mapq,nm;" with pos =
+ *          q.target_start + 1, strand + or -, cigar = clip5 S, l_M M, l_I I, l_D D, clip3 S (zero parts left out; if qe - qs < te - ts then
+ *          l_M = qe - qs, l_D = te - ts - l_M, else l_M = te - ts, l_I = qe - qs - l_M), nm = block_len - match_len + n_ambi; cs:Z: / MD:Z:
+ *          when the row has them; rl:i: (the tags row's rep_len) last.
+ * A read without rows (status 0, qlen > 0) writes "QNAME 4 * 0 0 * * 0 0 SEQ QUAL rl:i:<rep_len[i]>", SEQ and QUAL as given, unless
+ * MM355_SAM_HIT_ONLY is set.  A read with status MM355_EEMPTY writes nothing.  n_lines counts the lines; line_off delimits a read's lines.
+ * The text is formed on the device (mm355_sam.hip: a length kernel and a scan, a kernel for the short fields and the CIGAR, a tiled copy
+ * kernel for SEQ and QUAL; reads and qualities are uploaded for this writer) or on the host (mm355_sam.h, the same emitter run serially).
+ * MM355_EINVAL, before anything is allocated or launched: whatever the PAF formatter refuses; an option record without MM_F_CIGAR; a row
+ * outside 0 <= qs <= qe <= qlen; rows on an MM355_EEMPTY read; seqs[i] == NULL where qlens[i] > 0; unknown sam_flags bits; rep_len == NULL
+ * when an unmapped record would print it.  `where` as for the PAF formatter; AUTO picks the host below 48 hits (measured, see
+ * README; MM355_SAM_MIN_HITS=<n> overrides it, read per call). */
+#define MM355_SAM_SOFTCLIP 1        /* minimap2 -Y */
+#define MM355_SAM_HIT_ONLY 2        /* minimap2 --sam-hit-only */
+/* quals == NULL or quals[i] == NULL: no quality ("*"), otherwise qlens[i] bytes; rep_len[i] is read only for reads without rows */
+int mm355_sam_format(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, const mm355_hits_t *hits, const char *const *qnames, const char *const *seqs,
+                     const int32_t *qlens, const char *const *quals, const int32_t *rep_len, int sam_flags, int where, mm355_text_t **out);
+/* == mm355_map_batch_named with flags | MM355_OUT_TAGS, then mm355_sam_format with the call's per-read rep_len, then mm355_free_hits: byte
+ * for byte.  flags: MM355_OUT_CS | MM355_OUT_MD */
+int mm355_map_batch_sam(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
+                        const char *const *names, const char *const *quals, int flags, int sam_flags, int where, mm355_text_t **out);
+
 /* --- streaming FASTA / FASTQ reader, plain or gzip: the record rules of the index builder's parser (the name ends at the first blank,
  * multi-line sequences, a '+' line followed by quality as long as the sequence, CRLF).  A read set is cut into sub-batches without ever
  * being in memory as a whole.  mm355_fastx_next returns the next records: at least one, at most max_reads, and no record that would take
@@ -235,6 +271,10 @@ typedef struct { int64_t n; const char *const *seqs; const int32_t *lens; const 
 int mm355_fastx_open(const char *path, mm355_fastx_t **out);
 int mm355_fastx_next(mm355_fastx_t *fx, int64_t max_reads, int64_t max_bases, mm355_reads_t **out);
 void mm355_reads_free(mm355_reads_t *r);
+/* the same reader keeping FASTQ qualities: the quality strings of a sub-batch, parallel to seqs[] -- NULL for a reader opened without
+ * quality; an entry is NULL for a FASTA record or a record whose quality length differs from its sequence length, otherwise lens[i] bytes */
+int mm355_fastx_open_qual(const char *path, mm355_fastx_t **out);
+const char *const *mm355_reads_quals(const mm355_reads_t *r);
 void mm355_fastx_close(mm355_fastx_t *fx);
 
 /* --- per-stage entry points (same kernels as mm355_map_batch; used by the parity tests and

@@ -288,6 +288,8 @@ struct mm355_fastx {
 	size_t l_qual = 0; int64_t n_rec = 0;
 	// mm355_fastx_next only: the record that did not fit the previous sub-batch, and the error the reader stopped at
 	std::string held_name, held_seq; bool held = false; int err = 0;
+	// mm355_fastx_open_qual: the quality of the record fastx_record has just returned (has_qual: a FASTQ record with a '+' line), and the held record's
+	bool keep_qual = false, has_qual = false, held_has_qual = false; std::string qual, held_qual;
 	~mm355_fastx() { if (gz) gzclose(gz); }
 };
 
@@ -328,17 +330,18 @@ static int fastx_record(mm355_fastx *fx, std::string &name, std::string &seq)
 {
 	const size_t start = seq.size();
 	bool have = false;
+	if (fx->keep_qual) { fx->qual.clear(); fx->has_qual = false; }
 	if (fx->have_next) { name.swap(fx->next_name); fx->have_next = false; have = true; }
 	const char *line; size_t n;
 	while (fastx_line(fx, &line, &n)) {
-		if (fx->in_qual) { fx->l_qual += n; if (fx->l_qual >= seq.size() - start) fx->in_qual = false; continue; }
+		if (fx->in_qual) { if (fx->keep_qual) fx->qual.append(line, n); fx->l_qual += n; if (fx->l_qual >= seq.size() - start) fx->in_qual = false; continue; }
 		if (n > 0 && (line[0] == '>' || (line[0] == '@' && (fx->n_rec == 0 || fx->is_fq)))) {
 			fx->is_fq = line[0] == '@';
 			size_t e = 1; while (e < n && line[e] != ' ' && line[e] != '\t') ++e;
 			++fx->n_rec;
 			if (have) { fx->next_name.assign(line + 1, e - 1); fx->have_next = true; return 1; }
 			name.assign(line + 1, e - 1); have = true;
-		} else if (n > 0 && line[0] == '+' && fx->is_fq) { fx->in_qual = have && seq.size() > start; fx->l_qual = 0; }
+		} else if (n > 0 && line[0] == '+' && fx->is_fq) { fx->in_qual = have && seq.size() > start; fx->l_qual = 0; if (have) fx->has_qual = true; }
 		else if (have) {
 			size_t n_blank = 0;
 			for (size_t i = 0; i < n; ++i) n_blank += line[i] <= ' ';
@@ -375,6 +378,13 @@ extern "C" int mm355_fastx_open(const char *path, mm355_fastx_t **out)
 	return 0;
 }
 
+extern "C" int mm355_fastx_open_qual(const char *path, mm355_fastx_t **out)
+{
+	const int rc = mm355_fastx_open(path, out);
+	if (rc == 0) (*out)->keep_qual = true;
+	return rc;
+}
+
 extern "C" void mm355_fastx_close(mm355_fastx_t *fx) { delete fx; }
 
 // a sub-batch of reads and everything its pointers point to (mm355_reads_t is its first member: mm355_reads_free gets the box back)
@@ -383,9 +393,12 @@ struct ReadsBox {
 	std::string seq_bytes, name_bytes;       // sequences back to back; names, each with its NUL
 	std::vector<size_t> seq_at, name_at;
 	std::vector<const char*> sp, np; std::vector<int32_t> ln;
+	// a reader that keeps quality: the strings back to back, qual_at[i] < 0 for a record without one (FASTA, or a length other than the sequence's)
+	bool keep_qual = false; std::string qual_bytes; std::vector<int64_t> qual_at; std::vector<const char*> qp;
 };
 
 extern "C" void mm355_reads_free(mm355_reads_t *r) { delete (ReadsBox*)r; }
+extern "C" const char *const *mm355_reads_quals(const mm355_reads_t *r) { const ReadsBox *B = (const ReadsBox*)r; return B && B->keep_qual? B->qp.data() : 0; }
 
 extern "C" int mm355_fastx_next(mm355_fastx_t *fx, int64_t max_reads, int64_t max_bases, mm355_reads_t **out)
 {
@@ -393,27 +406,36 @@ extern "C" int mm355_fastx_next(mm355_fastx_t *fx, int64_t max_reads, int64_t ma
 	if (fx == 0 || max_reads < 1 || max_bases < 1) return MM355_EINVAL;
 	if (fx->err) return fx->err;
 	ReadsBox *B = new ReadsBox();
-	std::string name;
+	B->keep_qual = fx->keep_qual;
+	std::string name, qual; bool has_qual = false;
 	while ((int64_t)B->ln.size() < max_reads) {
 		const size_t at = B->seq_bytes.size();
-		if (fx->held) { name.swap(fx->held_name); B->seq_bytes += fx->held_seq; fx->held_seq.clear(); fx->held = false; }
+		if (fx->held) { name.swap(fx->held_name); B->seq_bytes += fx->held_seq; fx->held_seq.clear(); fx->held = false; qual.swap(fx->held_qual); has_qual = fx->held_has_qual; }
 		else {
 			const int rc = fastx_record(fx, name, B->seq_bytes);      // (the bases land behind the sub-batch's other reads)
 			if (rc == 0) break;
 			if (rc < 0) { fx->err = rc; break; }
 			if (B->seq_bytes.size() - at >= (size_t)1 << 31) { fx->err = MM355_EINVAL; break; }
+			if (fx->keep_qual) { qual.swap(fx->qual); has_qual = fx->has_qual; }
 		}
 		if (!B->ln.empty() && (int64_t)B->seq_bytes.size() > max_bases) {   // over the base limit and not the first: it opens the next sub-batch
 			fx->held_name.swap(name); fx->held_seq.assign(B->seq_bytes, at, std::string::npos); fx->held = true;
+			fx->held_qual.swap(qual); fx->held_has_qual = has_qual;
 			B->seq_bytes.resize(at);
 			break;
 		}
 		B->seq_at.push_back(at);
 		B->name_at.push_back(B->name_bytes.size()); B->name_bytes.append(name.c_str(), name.size() + 1);
 		B->ln.push_back((int32_t)(B->seq_bytes.size() - at));
+		if (fx->keep_qual) {
+			const bool ok = has_qual && qual.size() == B->seq_bytes.size() - at;
+			B->qual_at.push_back(ok? (int64_t)B->qual_bytes.size() : -1);
+			if (ok) B->qual_bytes += qual;
+		}
 	}
 	if (fx->err || B->ln.empty()) { delete B; return fx->err; }
 	for (size_t i = 0; i < B->ln.size(); ++i) { B->sp.push_back(B->seq_bytes.data() + B->seq_at[i]); B->np.push_back(B->name_bytes.data() + B->name_at[i]); }
+	for (size_t i = 0; i < B->qual_at.size(); ++i) B->qp.push_back(B->qual_at[i] < 0? (const char*)0 : B->qual_bytes.data() + B->qual_at[i]);
 	B->r.n = (int64_t)B->ln.size(); B->r.seqs = B->sp.data(); B->r.lens = B->ln.data(); B->r.names = B->np.data();
 	*out = &B->r;
 	return 0;

@@ -382,6 +382,15 @@ extern "C" int mm355_map_batch_named(mm355_ctx_t *c, const mm355_mapopt_t *mo, i
 	return mm355_map_resident(c, mo, flags, out);
 }
 
+int mm355_map_batch_rl(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens, const char *const *names,
+                       int flags, mm355_hits_t **out, const int32_t **rep_len)
+{
+	*rep_len = 0;
+	const int rc = mm355_map_batch_named(c, mo, n_reads, seqs, lens, names, flags, out);
+	if (rc == 0 && (int64_t)c->hb.rep_len.size() == n_reads) *rep_len = c->hb.rep_len.data();
+	return rc;
+}
+
 // maps the batch that mm355_batch_upload left resident in HBM (bench.py times this call: inputs already on the device)
 extern "C" int mm355_map_resident(mm355_ctx_t *c, const mm355_mapopt_t *mo, int flags, mm355_hits_t **out)
 {

@@ -83,6 +83,27 @@ struct PafLine {
 
 template <typename S> MM_HD void paf_tag_i(S &s, const char *tag, int64_t v) { paf_lit(s, tag); paf_i64(s, v); }
 
+// the tag block PAF and SAM share (format.c::write_tags up to zd): with a CIGAR NM ms AS nn; tp cm s1, s2 on primaries; de with a CIGAR,
+// otherwise dv when it was estimated; zd on split regions
+template <typename S> MM_HD void paf_emit_tags(S &s, const mm355_hit_t &h, const mm355_tags_t &t, bool has_cigar)
+{
+	if (has_cigar) {
+		paf_tag_i(s, "\tNM:i:", h.NM); paf_tag_i(s, "\tms:i:", h.dp_max); paf_tag_i(s, "\tAS:i:", h.dp_score); paf_tag_i(s, "\tnn:i:", t.n_ambi);
+	}
+	const bool inv = (t.flags & MM355_TAG_INV) != 0, pri = h.is_primary != 0;
+	paf_lit(s, "\ttp:A:"); s.ch(pri? (inv? 'I' : 'P') : (inv? 'i' : 'S'));
+	paf_tag_i(s, "\tcm:i:", h.cnt);
+	paf_tag_i(s, "\ts1:i:", t.score);
+	if (pri) paf_tag_i(s, "\ts2:i:", h.subsc);
+	if (has_cigar) {   // gap-compressed divergence: this order, in double
+		const double den = (double)((int64_t)h.block_len + t.n_ambi - t.n_gap + t.n_gapo);
+		const double r = (double)h.match_len / den;
+		paf_lit(s, "\tde:f:"); paf_f4(s, 1.0 - r);
+	} else if (t.div >= 0.0f && t.div <= 1.0f) { paf_lit(s, "\tdv:f:"); paf_f4(s, (double)t.div); }
+	const uint32_t zd = t.flags >> MM355_TAG_SPLIT_SHIFT & 3;
+	if (zd) paf_tag_i(s, "\tzd:i:", zd);
+}
+
 template <typename S> MM_HD void paf_emit_line(S &s, const PafLine &L)
 {
 	const mm355_hit_t &h = *L.h; const mm355_tags_t &t = *L.t;
@@ -98,21 +119,7 @@ template <typename S> MM_HD void paf_emit_line(S &s, const PafLine &L)
 	s.ch('\t'); paf_i64(s, h.match_len);
 	s.ch('\t'); paf_i64(s, h.block_len);
 	s.ch('\t'); paf_u64(s, h.mapq);
-	if (L.has_cigar) {
-		paf_tag_i(s, "\tNM:i:", h.NM); paf_tag_i(s, "\tms:i:", h.dp_max); paf_tag_i(s, "\tAS:i:", h.dp_score); paf_tag_i(s, "\tnn:i:", t.n_ambi);
-	}
-	const bool inv = (t.flags & MM355_TAG_INV) != 0, pri = h.is_primary != 0;
-	paf_lit(s, "\ttp:A:"); s.ch(pri? (inv? 'I' : 'P') : (inv? 'i' : 'S'));
-	paf_tag_i(s, "\tcm:i:", h.cnt);
-	paf_tag_i(s, "\ts1:i:", t.score);
-	if (pri) paf_tag_i(s, "\ts2:i:", h.subsc);
-	if (L.has_cigar) {   // gap-compressed divergence: this order, in double
-		const double den = (double)((int64_t)h.block_len + t.n_ambi - t.n_gap + t.n_gapo);
-		const double r = (double)h.match_len / den;
-		paf_lit(s, "\tde:f:"); paf_f4(s, 1.0 - r);
-	} else if (t.div >= 0.0f && t.div <= 1.0f) { paf_lit(s, "\tdv:f:"); paf_f4(s, (double)t.div); }
-	const uint32_t zd = t.flags >> MM355_TAG_SPLIT_SHIFT & 3;
-	if (zd) paf_tag_i(s, "\tzd:i:", zd);
+	paf_emit_tags(s, h, t, L.has_cigar);
 	paf_tag_i(s, "\trl:i:", t.rep_len);
 	if (L.has_cigar) {
 		paf_lit(s, "\tcg:Z:"); s.cigar(L.cigar + h.cigar_off, h.n_cigar);
@@ -136,6 +143,28 @@ struct PafWriteSink {
 	MM_HD void bytes(const char *b, int64_t l) { for (int64_t i = 0; i < l; ++i) p[n++] = b[i]; }
 	MM_HD void cigar(const uint32_t *w, int64_t k) { for (int64_t i = 0; i < k; ++i) { paf_u64(*this, w[i] >> 4); ch(paf_cigar_op(w[i])); } }
 };
+
+#ifdef __HIPCC__
+#include "mm355_wave.h"
+// the text of nc CIGAR words, written by a whole wave in tiles of 64 operations: a prefix sum of the operations' widths, every lane its own
+// digits and letter, the running offset carried from tile to tile (uniform trip count: the scan needs every lane)
+__device__ __forceinline__ void paf_wave_cigar(char *dst, const uint32_t *w, int64_t nc, int lane)
+{
+	for (int64_t base = 0; base < nc; base += 64) {
+		const bool have = base + lane < nc;
+		const uint32_t x = have? w[base + lane] : 0u;
+		const int32_t wid = have? paf_cigar_width(x) : 0;
+		const int32_t incl = wave_incl_scan_add(wid);
+		if (have) {
+			char *q = dst + (incl - wid);
+			uint32_t v = x >> 4;
+			for (int i = wid - 2; i >= 0; --i) { q[i] = (char)('0' + v % 10); v /= 10; }
+			q[wid - 1] = paf_cigar_op(x);
+		}
+		dst += __builtin_amdgcn_readlane(incl, 63);
+	}
+}
+#endif
 
 // ------------------------------------------------------------------ host side
 #include <stdlib.h>

@@ -6,8 +6,7 @@
 //                through hit_off.  The total crosses to the host with the call's one synchronisation before the write; the text buffer is sized from it.
 //   k_paf_write  lane 0 runs the emitter with the writing sink: single bytes go straight to the text, runs that exist in memory already
 //                (the two names, cs, MD) and the CIGAR are noted down with their place in the line.  Then the whole wave copies the runs,
-//                lane-strided, and writes the CIGAR in tiles of 64 operations: a prefix sum of the operations' widths, every lane its own
-//                digits and letter, the running offset carried from tile to tile.
+//                lane-strided, and writes the CIGAR in tiles of 64 operations (paf_wave_cigar, shared with the SAM writer).
 // Every byte of the text has one writer: plain vector stores, no atomics.  What is uploaded per call: the hit and tags rows, the CIGAR words
 // and the string arena (a result of mm355_map_batch lives on the host), the hit-to-read map, the read lengths, the query names cut at their
 // first blank.  The contig names are uploaded once per index replica, on first use, and belong to the replica.
@@ -100,22 +99,7 @@ __global__ __launch_bounds__(256) void k_paf_write(PafDev D, const int64_t *off,
 		const int64_t l = runs[wv][r].len;
 		for (int64_t i = lane; i < l; i += 64) dst[i] = src[i];
 	}
-	const uint32_t *w = (const uint32_t*)runs[wv][PAF_RUNS].src;
-	const int64_t nc = runs[wv][PAF_RUNS].len;
-	char *dst = line + runs[wv][PAF_RUNS].at;
-	for (int64_t base = 0; base < nc; base += 64) {        // (uniform trip count: the scan below needs every lane)
-		const bool have = base + lane < nc;
-		const uint32_t x = have? w[base + lane] : 0u;
-		const int32_t wid = have? paf_cigar_width(x) : 0;
-		const int32_t incl = wave_incl_scan_add(wid);
-		if (have) {
-			char *q = dst + (incl - wid);
-			uint32_t v = x >> 4;
-			for (int i = wid - 2; i >= 0; --i) { q[i] = (char)('0' + v % 10); v /= 10; }
-			q[wid - 1] = paf_cigar_op(x);
-		}
-		dst += __builtin_amdgcn_readlane(incl, 63);
-	}
+	paf_wave_cigar(line + runs[wv][PAF_RUNS].at, (const uint32_t*)runs[wv][PAF_RUNS].src, runs[wv][PAF_RUNS].len, lane);
 }
 
 // ------------------------------------------------------------------ host side

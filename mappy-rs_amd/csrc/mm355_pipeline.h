@@ -135,6 +135,7 @@ struct mm355_ctx : mm355_streams {
 	DBuf logt, regs_scr, regs_in; HBuf h_regs_in, h_regs_out;  // chain-only region stage (mm355_regs.hip): host-logf table, scratch + rows, read tables
 	bool logt_ok = false;
 	DBuf paf_in, paf_work, paf_text; HBuf h_paf_in, h_paf_out;   // PAF writer (mm355_paf.hip): rows + arenas + names up, lengths / offsets / scan space, the text; pinned staging both ways
+	DBuf sam_in, sam_work, sam_text; HBuf h_sam_in, h_sam_out;   // SAM writer (mm355_sam.hip): the same roles; sam_in also holds the reads and qualities the lines print
 	mm355_stats_t stats;
 	mm355_timer_book timers;           // lazy stage timers (EvTimer, mm355_kt)
 	unsigned long long pairs_land[64] = {};   // landing zone of the chain stage's pair counters (mm355_run_backtrack)
@@ -149,6 +150,9 @@ int mm355_check_opts(const mm355_mapopt_t *mo, const mm355_index *mi);
 // stage drivers (each leaves its outputs resident on the device and the per-read counts in ctx->hb)
 extern "C" int mm355_map_resident(mm355_ctx_t *c, const mm355_mapopt_t *mo, int flags, mm355_hits_t **out);
 extern void (*mm355_parallel_hook)(int64_t n, const std::function<void(int64_t)> &f);   // the host pool's parallel loop (mm355_map.hip), or null
+// mm355_map_batch_named, and the call's per-read rep_len (HostBatch::rep_len: valid until the context's next call; null when nothing was sketched)
+int mm355_map_batch_rl(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens, const char *const *names,
+                       int flags, mm355_hits_t **out, const int32_t **rep_len);
 int mm355_run_pack(mm355_ctx *ctx, int64_t n_reads, const char *const *seqs, const int32_t *lens);
 // the query names of the batch mm355_run_pack has just packed (names == 0 or names[i] == 0: unnamed); they stay with the batch
 void mm355_set_names(mm355_ctx *ctx, int64_t n_reads, const char *const *names);

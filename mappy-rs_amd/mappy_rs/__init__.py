@@ -27,7 +27,7 @@ import numpy as np
 
 from . import _ffi
 
-__all__ = ["Aligner", "Mapping", "paf_line", "shard_by_bases", "order_by_length"]
+__all__ = ["Aligner", "Mapping", "paf_line", "sam_lines", "shard_by_bases", "order_by_length"]
 
 _CIGAR_OPS = "MIDNSHP=X"
 
@@ -262,6 +262,23 @@ def _f4(x):
     return "0" if x == 0.0 else "%.4f" % x
 
 
+def _tag_block(m, t, has_cigar):
+    """the tags PAF and SAM share, in write_tags' order: NM ms AS nn with a CIGAR; tp cm s1, s2 on primaries; de or dv; zd on split regions"""
+    f = []
+    if has_cigar:
+        f += ["NM:i:%d" % m.NM, "ms:i:%d" % t[_G_MS], "AS:i:%d" % t[_G_AS], "nn:i:%d" % t[_G_NN]]
+    f += ["tp:A:" + m.tp, "cm:i:%d" % t[_G_CM], "s1:i:%d" % t[_G_S1]]
+    if m.is_primary:
+        f.append("s2:i:%d" % t[_G_S2])
+    if has_cigar:
+        f.append("de:f:" + _f4(m.de))
+    elif 0.0 <= t[_G_DIV] <= 1.0:
+        f.append("dv:f:" + _f4(t[_G_DIV]))
+    if m.zd:
+        f.append("zd:i:%d" % m.zd)
+    return f
+
+
 def paf_line(m, name, qlen):
     """one PAF line of the record `m` of the read `name` (length `qlen`): the twelve columns and the tags in the order of minimap2's PAF
     writer (format.c::mm_write_paf + write_tags).  Needs a record mapped with Aligner(tags=True): ValueError otherwise.
@@ -278,17 +295,7 @@ def paf_line(m, name, qlen):
     has_cigar = m._has_cigar()
     f = [name, qlen, m.query_start, m.query_end, "+" if m.strand > 0 else "-", m.target_name, m.target_len, m.target_start, m.target_end,
          m.match_len, m.block_len, m.mapq]
-    if has_cigar:
-        f += ["NM:i:%d" % m.NM, "ms:i:%d" % t[_G_MS], "AS:i:%d" % t[_G_AS], "nn:i:%d" % t[_G_NN]]
-    f += ["tp:A:" + m.tp, "cm:i:%d" % t[_G_CM], "s1:i:%d" % t[_G_S1]]
-    if m.is_primary:
-        f.append("s2:i:%d" % t[_G_S2])
-    if has_cigar:
-        f.append("de:f:" + _f4(m.de))
-    elif 0.0 <= t[_G_DIV] <= 1.0:
-        f.append("dv:f:" + _f4(t[_G_DIV]))
-    if m.zd:
-        f.append("zd:i:%d" % m.zd)
+    f += _tag_block(m, t, has_cigar)
     f.append("rl:i:%d" % t[_G_RL])
     if has_cigar:
         f.append("cg:Z:" + m.cigar_str)
@@ -297,6 +304,84 @@ def paf_line(m, name, qlen):
         if m.MD is not None:
             f.append("MD:Z:" + m.MD)
     return "\t".join(str(x) for x in f)
+
+
+# minimap2's seq_comp_table: bytes below 128, case kept; everything else (S W N among them) is its own complement
+_SAM_COMP = {ord(a): ord(b) for a, b in zip("ACGTURYKMBVDHacgturykmbvdh", "TGCAAYRMKVBHDtgcaayrmkvbhd")}
+
+
+def _sam_clips(m, qlen):
+    """(clip5, clip3) of a record on a read of qlen bases, in the order the line prints them"""
+    return (qlen - m.query_end, m.query_start) if m.strand < 0 else (m.query_start, qlen - m.query_end)
+
+
+def sam_lines(ms, name, seq, qual=None, *, softclip=False, rl=None):
+    """the SAM lines (str, no newline) of one read's records `ms` (mapped with Aligner(tags=True), base-level), as minimap2 -a writes them
+    (format.c::mm_write_sam3, write_sam_cigar, sam_write_sq, write_tags of 2.26), one per record in order.  name: the read's name (printed
+    up to its first blank; None prints `*`); seq / qual: the read and its quality string (None: `*`) as they were given to the mapping call;
+    softclip: minimap2 -Y.  Empty `ms` gives the one unmapped record and needs rl, the read's rep_len.
+
+    QNAME; FLAG = 0x10 on the reverse strand, 0x100 on a secondary, otherwise 0x800 on a supplementary; RNAME; POS = target_start + 1; MAPQ;
+    CIGAR with the clipped read ends around it (H on a supplementary without softclip, otherwise S; `*` without a CIGAR); `*` 0 0; SEQ and
+    QUAL: the whole read (reverse-complemented / reversed on the reverse strand) on the first primary and under softclip, `*` `*` on a
+    secondary, the aligned slice on a hard-clipped supplementary; then NM ms AS nn tp cm s1 [s2] de [zd], SA:Z: on a primary when the read
+    has other primaries with a CIGAR (rname,pos,strand,cigar,mapq,nm; each, the cigar as clip5 S, M, I, D, clip3 S), cs:Z: / MD:Z:, rl:i:.
+    Records without tags, or chain-only records: ValueError.  Like paf_line, the layout is written from knowledge of minimap2's writer and
+    has not been diffed against its output."""
+    qn = "*" if name is None else name.replace("\t", " ").split(" ")[0]
+    qlen = len(seq)
+    if not ms:
+        if rl is None:
+            raise ValueError("the unmapped record needs `rl`, the read's rep_len")
+        return ["\t".join([qn, "4", "*", "0", "0", "*", "*", "0", "0", seq, "*" if qual is None else qual, "rl:i:%d" % rl])]
+    for m in ms:
+        if m._tags() is None or not m._has_cigar():
+            raise ValueError("sam_lines needs records mapped with Aligner(tags=True) and base-level alignment")
+    out = []
+    for m in ms:
+        t = m._tags()
+        rev = m.strand < 0
+        flag = (0x10 if rev else 0) | (0x100 if not m.is_primary else 0 if t[_G_FL] & _ffi.TAG_SAM_PRI else 0x800)
+        clip5, clip3 = _sam_clips(m, qlen)
+        if len(m.cigar):
+            letter = "H" if flag & 0x800 and not softclip else "S"
+            cig = ("%d%s" % (clip5, letter) if clip5 else "") + m.cigar_str + ("%d%s" % (clip3, letter) if clip3 else "")
+        else:
+            cig = "*"
+        if flag & 0x900 == 0 or softclip:
+            s, q = seq, qual
+        elif flag & 0x100:
+            s, q = None, None
+        else:
+            s, q = seq[m.query_start:m.query_end], None if qual is None else qual[m.query_start:m.query_end]
+        if s is None:
+            s = q = "*"
+        else:
+            if rev:
+                s, q = s[::-1].translate(_SAM_COMP), None if q is None else q[::-1]
+            q = "*" if q is None else q
+        f = [qn, flag, m.target_name, m.target_start + 1, m.mapq, cig, "*", 0, 0, s, q]
+        f += _tag_block(m, t, True)
+        if m.is_primary:
+            sa = []
+            for o in ms:
+                if o is m or not o.is_primary or not len(o.cigar):
+                    continue
+                c5, c3 = _sam_clips(o, qlen)
+                ql, tl = o.query_end - o.query_start, o.target_end - o.target_start
+                l_m, l_i, l_d = (ql, 0, tl - ql) if ql < tl else (tl, ql - tl, 0)
+                oc = "".join("%d%s" % (n, c) for n, c in ((c5, "S"), (l_m, "M"), (l_i, "I"), (l_d, "D"), (c3, "S")) if n)
+                sa.append("%s,%d,%s,%s,%d,%d;" % (o.target_name, o.target_start + 1, "-" if o.strand < 0 else "+", oc, o.mapq,
+                                                  o.block_len - o.match_len + o._tags()[_G_NN]))
+            if sa:
+                f.append("SA:Z:" + "".join(sa))
+        if m.cs is not None:
+            f.append("cs:Z:" + m.cs)
+        if m.MD is not None:
+            f.append("MD:Z:" + m.MD)
+        f.append("rl:i:%d" % t[_G_RL])
+        out.append("\t".join(str(x) for x in f))
+    return out
 
 
 def shard_by_bases(lengths, n_shards):
@@ -846,9 +931,60 @@ class Aligner:
         finally:
             L.mm355_free_text(tp)
 
-    paf_on_device = None              # whether the device formatter wrote the text of the last map_paf call
+    paf_on_device = None              # whether the device formatter wrote the text of the last map_paf / map_sam call
 
-    def map_file(self, reads_path, out_path, cs=False, MD=False, n_threads=None, sub_batch_reads=SUB_BATCH_READS, *, where=_ffi.PAF_AUTO):
+    # ---- SAM text (mm355_map_batch_sam): the lines of mappy_rs.sam_lines, formatted by the library
+    def sam_header(self):
+        """the SAM header of this index as bytes: @HD (unsorted, grouped by query), one @SQ per contig in index order, @PG of this library"""
+        L = self._L
+        sq = "".join("@SQ\tSN:%s\tLN:%d\n" % (nm, L.mm355_index_seq_len(self._idx, i)) for i, nm in enumerate(self._names()))
+        return ("@HD\tVN:1.6\tSO:unsorted\tGO:query\n" + sq + "@PG\tID:mappy_rs\tPN:mappy_rs\n").encode()
+
+    def _sam_flags(self, cs, MD):
+        if not self._mo.flag & 4:
+            raise ValueError("SAM needs base-level alignment: this Aligner was created with cigar=False")
+        return (_ffi.OUT_CS if cs else 0) | (_ffi.OUT_MD if MD else 0)
+
+    def map_sam(self, seqs, names=None, quals=None, cs=False, MD=False, *, softclip=False, hit_only=False, where=_ffi.PAF_AUTO):
+        """the SAM lines of `seqs` (a list of str) as bytes, without a header (sam_header()), in input order: one mm355_map_batch_sam call, no
+        Mapping objects.  The lines of a read are sam_lines() of the records map() would return with tags; a read without hits writes one
+        unmapped record unless hit_only (minimap2 --sam-hit-only); an empty sequence writes nothing.  names as in map_paf; quals[i] is None or
+        a str as long as the read; softclip: minimap2 -Y.  where and `paf_on_device`: as for map_paf."""
+        flags = self._sam_flags(cs, MD)
+        seqs = list(seqs)
+        for s in seqs:
+            if not isinstance(s, str):
+                raise TypeError("argument 'seq': 'bytes' object cannot be converted to 'PyString'" if isinstance(s, bytes)
+                                else "argument 'seq' must be str")
+        if names is not None:
+            names = list(names)
+            if len(names) != len(seqs) or not all(nm is None or isinstance(nm, str) for nm in names):
+                raise ValueError("`names` must hold a string or None for every read")
+        qarr = qkeep = None
+        if quals is not None:
+            quals = list(quals)
+            if len(quals) != len(seqs) or not all(q is None or (isinstance(q, str) and len(q) == len(s) and q.isascii()) for q, s in zip(quals, seqs)):
+                raise ValueError("`quals` must hold None or an ASCII string of the read's length for every read")
+            if not all(q is None or s.isascii() for q, s in zip(quals, seqs)):
+                raise ValueError("a read that has a quality string must be ASCII: its quality is matched to it byte by byte")
+            qkeep = [None if q is None else q.encode() for q in quals]
+            qarr = (C.c_char_p * len(qkeep))(*qkeep)
+        L = self._L
+        packed, narr = _ffi.pack_reads(seqs), _ffi.pack_names(names)
+        sam_flags = (_ffi.SAM_SOFTCLIP if softclip else 0) | (_ffi.SAM_HIT_ONLY if hit_only else 0)
+        tp = C.POINTER(_ffi.Text)()
+        with self._lock:
+            rc = L.mm355_map_batch_sam(self._context(), C.byref(self._mo), len(seqs), packed.arr, packed.lens, narr, qarr, flags, sam_flags,
+                                       int(where), C.byref(tp))
+        if rc != 0:
+            raise RuntimeError(L.mm355_strerror(rc).decode())
+        try:
+            self.paf_on_device = bool(tp.contents.on_device)
+            return bytes(_ffi.text_view(tp))
+        finally:
+            L.mm355_free_text(tp)
+
+    def map_file(self, reads_path, out_path, cs=False, MD=False, n_threads=None, sub_batch_reads=SUB_BATCH_READS, *, where=_ffi.PAF_AUTO, format="paf"):
         """maps a FASTA / FASTQ file of reads (plain or gzip) to a PAF file, lines in input order -- minimap2's command line from a read set to
         its overlaps or alignments.  A reader thread cuts sub-batches of `sub_batch_reads` reads (and at most SUB_BATCH_BASES bases) with the
         library's streaming reader; up to min(n_threads, 8) workers per GPU (n_threads=None: enable_threading's value, or 1), each with a
@@ -857,8 +993,16 @@ class Aligner:
         The text is written to `out_path` + ".part" and renamed when it is complete: a failure stops the rest, removes the partly written
         file and is raised, and a file that was at `out_path` before is still there.  `where` (keyword-only): as for map_paf.
         Returns {n_reads, n_bases, n_lines, n_sub_batches, seconds} (and ms_format, n_on_device: the formatting step summed over the
-        sub-batches, and how many of them the device formatted)."""
-        flags = self._paf_flags(cs, MD)
+        sub-batches, and how many of them the device formatted).
+        format (keyword-only): "paf", or "sam": the header of sam_header(), then the lines of map_sam (mm355_map_batch_sam; the reader keeps
+        FASTQ qualities, a FASTA read prints `*`; reads without hits write their unmapped record).  A SAM sub-batch's text is about 2.2 x its
+        bases (a PAF one's a few hundred bytes per hit), and 2 x workers of them exist at a time.  Any other value: ValueError, before a
+        file is opened."""
+        if format not in ("paf", "sam"):
+            raise ValueError("`format` must be \"paf\" or \"sam\"")
+        sam = format == "sam"
+        flags = self._sam_flags(cs, MD) if sam else self._paf_flags(cs, MD)
+        header = self.sam_header() if sam else b""
         L = self._L
         nt = self._n_threads if n_threads is None else int(n_threads)
         n_workers = max(1, min(nt, 8)) * len(self._devices)
@@ -867,7 +1011,7 @@ class Aligner:
             raise ValueError("`sub_batch_reads` must be at least 1")
         t0 = time.perf_counter()
         fx = C.c_void_p()
-        rc = L.mm355_fastx_open(os.fsencode(reads_path), C.byref(fx))
+        rc = (L.mm355_fastx_open_qual if sam else L.mm355_fastx_open)(os.fsencode(reads_path), C.byref(fx))
         if rc != 0:
             raise RuntimeError("%s: %s" % (reads_path, L.mm355_strerror(rc).decode()))
         part = os.fspath(out_path) + (b".part" if isinstance(os.fspath(out_path), bytes) else ".part")
@@ -907,7 +1051,10 @@ class Aligner:
                         n = int(r.n)
                         n_bases = int(np.ctypeslib.as_array(r.lens, shape=(n,)).sum(dtype=np.int64))
                         tp = C.POINTER(_ffi.Text)()
-                        rc = L.mm355_map_batch_paf(ctx[1], C.byref(mo), n, r.seqs, r.lens, r.names, flags, where, C.byref(tp))
+                        if sam:
+                            rc = L.mm355_map_batch_sam(ctx[1], C.byref(mo), n, r.seqs, r.lens, r.names, L.mm355_reads_quals(rp), flags, 0, where, C.byref(tp))
+                        else:
+                            rc = L.mm355_map_batch_paf(ctx[1], C.byref(mo), n, r.seqs, r.lens, r.names, flags, where, C.byref(tp))
                     finally:
                         L.mm355_reads_free(rp)
                     if rc != 0:
@@ -955,6 +1102,7 @@ class Aligner:
         rd = None
         try:
             self._names()
+            out.write(header)
             rd = threading.Thread(target=reader, daemon=True)
             rd.start()
             while True:

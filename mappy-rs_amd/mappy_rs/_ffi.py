@@ -18,7 +18,8 @@ MM355_ENODEV, MM355_EINVAL, MM355_ENOMEM, MM355_EIO, MM355_ENOIDX, MM355_EEMPTY,
     -1, -2, -3, -4, -5, -6, -7, -8
 OUT_CS, OUT_MD, OUT_TAGS = 1, 2, 4
 TAG_INV, TAG_SAM_PRI, TAG_SPLIT_SHIFT = 1, 2, 2      # mm355_tags_t::flags
-PAF_AUTO, PAF_HOST, PAF_DEVICE = 0, 1, 2             # `where` of mm355_paf_format / mm355_map_batch_paf
+PAF_AUTO, PAF_HOST, PAF_DEVICE = 0, 1, 2             # `where` of mm355_paf_format / mm355_map_batch_paf and of the SAM calls
+SAM_SOFTCLIP, SAM_HIT_ONLY = 1, 2                    # `sam_flags` of mm355_sam_format / mm355_map_batch_sam
 
 
 class IdxOpt(C.Structure):
@@ -118,6 +119,7 @@ EXPORTS = [
     "mm355_map_batch_named", "mm355_batch_upload_named", "mm355_stage_anchors_named",
     "mm355_index_load_device", "mm355_index_dump", "mm355_index_load_mmi_device",
     "mm355_paf_format", "mm355_map_batch_paf", "mm355_free_text", "mm355_fastx_open", "mm355_fastx_next", "mm355_reads_free", "mm355_fastx_close",
+    "mm355_sam_format", "mm355_map_batch_sam", "mm355_fastx_open_qual", "mm355_reads_quals",
 ]
 
 _LIB = None
@@ -163,6 +165,13 @@ def lib():
     L.mm355_paf_format.argtypes = [vp, C.POINTER(MapOpt), C.POINTER(Hits), C.POINTER(C.c_char_p), i32p, C.c_int, C.POINTER(C.POINTER(Text))]
     L.mm355_map_batch_paf.argtypes = [vp, C.POINTER(MapOpt), C.c_int64, C.POINTER(C.c_char_p), i32p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
                                       C.POINTER(C.POINTER(Text))]
+    L.mm355_sam_format.argtypes = [vp, C.POINTER(MapOpt), C.POINTER(Hits), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), i32p, C.POINTER(C.c_char_p), i32p,
+                                   C.c_int, C.c_int, C.POINTER(C.POINTER(Text))]
+    L.mm355_map_batch_sam.argtypes = [vp, C.POINTER(MapOpt), C.c_int64, C.POINTER(C.c_char_p), i32p, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
+                                      C.c_int, C.c_int, C.c_int, C.POINTER(C.POINTER(Text))]
+    L.mm355_fastx_open_qual.argtypes = [C.c_char_p, C.POINTER(vp)]
+    L.mm355_reads_quals.argtypes = [C.POINTER(Reads)]
+    L.mm355_reads_quals.restype = C.POINTER(C.c_char_p)
     L.mm355_free_text.argtypes = [C.POINTER(Text)]
     L.mm355_free_text.restype = None
     L.mm355_fastx_open.argtypes = [C.c_char_p, C.POINTER(vp)]
