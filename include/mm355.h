@@ -259,6 +259,50 @@ int mm355_sam_format(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, const mm355_hit
 int mm355_map_batch_sam(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
                         const char *const *names, const char *const *quals, int flags, int sam_flags, int where, mm355_text_t **out);
 
+/* --- BAM records: uncompressed BAM, that is BGZF with stored deflate blocks (what `samtools view -u` writes and every htslib tool reads).
+ * The rule: a record is the BAM encoding of the SAM line mm355_sam_format writes for the same row under the same sam_flags -- the SAM/BAM
+ * specification's encoding, with htslib's choices where the specification leaves one.  Little-endian, field by field:
+ *   block_size   the length of the rest of the record
+ *   refID = rid, pos = target_start, l_read_name = printed name length + 1, mapq (one byte),
+ *   bin = reg2bin(pos, pos + max(1, reflen)) & 0xffff, reflen = the summed lengths of the row's M D N = X words, in 64 bits,
+ *   n_cigar_op, flag (the SAM line's), l_seq, next_refID = -1, next_pos = -1, tlen = 0, read_name and a NUL
+ *   CIGAR  clip5 (H or S by the SAM line's rule), the row's words unchanged (len << 4 | op is BAM's word), clip3; a row with n_cigar == 0 has
+ *          no words.  More than 65535 words: htslib's long-CIGAR form -- n_cigar_op = 2, the words (uint32)l_seq << 4 | S and
+ *          (uint32)reflen << 4 | N, and the real words in a CG:B:I tag, the record's last
+ *   SEQ    what the SAM line prints as SEQ (l_seq = 0 and no bytes where it prints "*": a secondary without soft clipping), two bases per
+ *          byte, high nibble first, a final odd base padded with 0; code = index in "=ACMGRSVTWYHKDBN" in either case, every other byte (U
+ *          and u among them) 15.  On the reverse strand the byte is complemented first, as the line's is: U -> A -> 1
+ *   QUAL   l_seq bytes: the quality byte minus 33 mod 256, last byte first on the reverse strand; 0xFF each for a read without quality
+ *   tags   in the SAM line's order: NM ms AS nn tp cm s1 [s2] de [zd] [SA] [cs] [MD] rl [CG].  An i tag takes htslib's smallest type: C up to
+ *          255, S up to 65535, else I; c down to -128, s down to -32768, else i.  tp is A.  de is f: the float32 of the double N / 10000.0, N
+ *          the integer behind the line's %.4f digits (0 for the printed "0", the sign kept) -- (float)strtod(text) without the text.  SA, cs
+ *          and MD are Z with a NUL, SA's text the SAM line's
+ * The unmapped record: refID -1, pos -1, mapq 0, bin 4680, flag 4, no CIGAR, SEQ and QUAL as given, rl.
+ * One thing the text cannot say and the record can: a SEQ or QUAL of one byte that is `*` (a one-base read or hard-clipped slice) prints the
+ * SAM marker of a missing field; the record holds what the read holds (l_seq 1, code 15; quality 9).
+ * MM355_EINVAL, before anything is allocated or launched (the library's check is mm355_bam.h::mm355_bam_check): whatever the SAM formatter
+ * refuses; a row with mapq > 255; a printed read name of more than 254 bytes on a read that writes a record; a clip of 2^28 bases or more
+ * (a word's length has 28 bits).
+ * BGZF: the stream of records is cut every 0xff00 bytes (htslib's block payload; records may straddle blocks).  A block is the 18-byte gzip
+ * header with the BC extra field and BSIZE, one stored deflate block (01, LEN, NLEN), the payload, CRC-32 and ISIZE: payload + 31 bytes, so
+ * block b starts at b * (0xff00 + 31).  One call's output is a whole number of blocks, and the outputs of consecutive calls, one behind
+ * the other, are a valid stream of records; the header blocks and the empty 28-byte EOF block are the file writer's, once per file.
+ * In the result `text` is the BGZF bytes, n_lines the number of records, and line_off[i] the offset of read i's first record IN THE UNFRAMED
+ * STREAM of records (byte x of it is byte x + 23 + 31 * (x / 0xff00) of text).  Formed on the device (mm355_bam.hip: a length kernel and two
+ * scans, a kernel for the fields, a tiled kernel that packs SEQ and QUAL, a framing kernel with a workgroup per block) or on the host
+ * (mm355_bam.h: the same emitter run serially, zlib's crc32).  `where` as for the PAF formatter; AUTO picks the host below 24 hits
+ * (measured, see README; MM355_BAM_MIN_HITS=<n> overrides it, read per call). */
+int mm355_bam_format(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, const mm355_hits_t *hits, const char *const *qnames, const char *const *seqs,
+                     const int32_t *qlens, const char *const *quals, const int32_t *rep_len, int sam_flags, int where, mm355_text_t **out);
+/* == mm355_map_batch_named with flags | MM355_OUT_TAGS, then mm355_bam_format with the call's per-read rep_len, then mm355_free_hits: byte
+ * for byte.  flags: MM355_OUT_CS | MM355_OUT_MD */
+int mm355_map_batch_bam(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
+                        const char *const *names, const char *const *quals, int flags, int sam_flags, int where, mm355_text_t **out);
+/* the framing stage by itself: n arbitrary bytes into stored BGZF blocks (n == 0: zero bytes), on the host (ctx may be NULL) or on the
+ * device (an upload, the framing kernel, a copy back); AUTO is the host: the bytes are in host memory, and either transfer moves as much
+ * as the host's crc32 reads.  n_lines counts the blocks, n_reads is 0.  The BAM header of a file goes through here. */
+int mm355_bgzf_wrap(mm355_ctx_t *ctx, const void *data, int64_t n, int where, mm355_text_t **out);
+
 /* --- streaming FASTA / FASTQ reader, plain or gzip: the record rules of the index builder's parser (the name ends at the first blank,
  * multi-line sequences, a '+' line followed by quality as long as the sequence, CRLF).  A read set is cut into sub-batches without ever
  * being in memory as a whole.  mm355_fastx_next returns the next records: at least one, at most max_reads, and no record that would take

@@ -41,15 +41,19 @@ template <typename S> MM_HD void paf_lit(S &s, const char *z) { for (; *z; ++z) 
 // the code takes that branch from sh = 120 on, which is what keeps the 128-bit shift count in range, and computes the (zero) quotient in
 // between.  NaN prints "nan"; values of 2^50 and more print "inf", which is not what printf does with a large finite value: the fields
 // this serves are a divergence in [0, 1] and 1 - mlen / n with 32-bit integers, at most 2^31 + 1 in magnitude.
-template <typename S> MM_HD void paf_f4(S &s, double x)
+// The number behind the text: what x is (PAF_F4_ZERO: exactly zero, "0"; PAF_F4_NAN; PAF_F4_INF; PAF_F4_NUM), its sign bit, and for a
+// number q = |x| * 10000 rounded half to even, so that the text is q / 10000 "." and four digits of q % 10000 (the BAM writer stores q / 10000.0)
+enum { PAF_F4_ZERO, PAF_F4_NAN, PAF_F4_INF, PAF_F4_NUM };
+MM_HD int paf_f4_scaled(double x, bool *neg, uint64_t *q_out)
 {
 	union { double d; uint64_t u; } z; z.d = x;
 	const int e = (int)(z.u >> 52 & 0x7ff);
 	const uint64_t frac = z.u & ((1ULL << 52) - 1);
-	if (e == 0 && frac == 0) { s.ch('0'); return; }
-	if (e == 0x7ff && frac) { paf_lit(s, "nan"); return; }
-	if (z.u >> 63) s.ch('-');
-	if (e >= 1023 + 50) { paf_lit(s, "inf"); return; }
+	*neg = false; *q_out = 0;
+	if (e == 0 && frac == 0) return PAF_F4_ZERO;
+	if (e == 0x7ff && frac) return PAF_F4_NAN;
+	*neg = z.u >> 63 != 0;
+	if (e >= 1023 + 50) return PAF_F4_INF;
 	const uint64_t m = e? frac | 1ULL << 52 : frac;
 	const int sh = e? 1075 - e : 1074;                      // 3 .. 1074
 	uint64_t q = 0;
@@ -59,6 +63,17 @@ template <typename S> MM_HD void paf_f4(S &s, double x)
 		q = (uint64_t)(p >> sh);
 		if (rem > half || (rem == half && (q & 1))) ++q;
 	}
+	*q_out = q;
+	return PAF_F4_NUM;
+}
+template <typename S> MM_HD void paf_f4(S &s, double x)
+{
+	bool neg; uint64_t q;
+	const int kind = paf_f4_scaled(x, &neg, &q);
+	if (kind == PAF_F4_ZERO) { s.ch('0'); return; }
+	if (kind == PAF_F4_NAN) { paf_lit(s, "nan"); return; }
+	if (neg) s.ch('-');
+	if (kind == PAF_F4_INF) { paf_lit(s, "inf"); return; }
 	paf_u64(s, q / 10000);
 	s.ch('.');
 	const uint32_t f = (uint32_t)(q % 10000);
@@ -82,6 +97,13 @@ struct PafLine {
 };
 
 template <typename S> MM_HD void paf_tag_i(S &s, const char *tag, int64_t v) { paf_lit(s, tag); paf_i64(s, v); }
+// gap-compressed divergence (de): this order, in double
+MM_HD double paf_de(const mm355_hit_t &h, const mm355_tags_t &t)
+{
+	const double den = (double)((int64_t)h.block_len + t.n_ambi - t.n_gap + t.n_gapo);
+	const double r = (double)h.match_len / den;
+	return 1.0 - r;
+}
 
 // the tag block PAF and SAM share (format.c::write_tags up to zd): with a CIGAR NM ms AS nn; tp cm s1, s2 on primaries; de with a CIGAR,
 // otherwise dv when it was estimated; zd on split regions
@@ -95,11 +117,8 @@ template <typename S> MM_HD void paf_emit_tags(S &s, const mm355_hit_t &h, const
 	paf_tag_i(s, "\tcm:i:", h.cnt);
 	paf_tag_i(s, "\ts1:i:", t.score);
 	if (pri) paf_tag_i(s, "\ts2:i:", h.subsc);
-	if (has_cigar) {   // gap-compressed divergence: this order, in double
-		const double den = (double)((int64_t)h.block_len + t.n_ambi - t.n_gap + t.n_gapo);
-		const double r = (double)h.match_len / den;
-		paf_lit(s, "\tde:f:"); paf_f4(s, 1.0 - r);
-	} else if (t.div >= 0.0f && t.div <= 1.0f) { paf_lit(s, "\tdv:f:"); paf_f4(s, (double)t.div); }
+	if (has_cigar) { paf_lit(s, "\tde:f:"); paf_f4(s, paf_de(h, t)); }
+	else if (t.div >= 0.0f && t.div <= 1.0f) { paf_lit(s, "\tdv:f:"); paf_f4(s, (double)t.div); }
 	const uint32_t zd = t.flags >> MM355_TAG_SPLIT_SHIFT & 3;
 	if (zd) paf_tag_i(s, "\tzd:i:", zd);
 }

@@ -136,6 +136,7 @@ struct mm355_ctx : mm355_streams {
 	bool logt_ok = false;
 	DBuf paf_in, paf_work, paf_text; HBuf h_paf_in, h_paf_out;   // PAF writer (mm355_paf.hip): rows + arenas + names up, lengths / offsets / scan space, the text; pinned staging both ways
 	DBuf sam_in, sam_work, sam_text; HBuf h_sam_in, h_sam_out;   // SAM writer (mm355_sam.hip): the same roles; sam_in also holds the reads and qualities the lines print
+	DBuf bam_out;                          // BAM writer (mm355_bam.hip): the BGZF blocks; its uploads, tables and unframed records use the SAM writer's buffers
 	mm355_stats_t stats;
 	mm355_timer_book timers;           // lazy stage timers (EvTimer, mm355_kt)
 	unsigned long long pairs_land[64] = {};   // landing zone of the chain stage's pair counters (mm355_run_backtrack)

@@ -15,6 +15,7 @@ import collections.abc
 import ctypes as C
 import os
 import queue
+import struct
 import threading
 import time
 import weakref
@@ -382,6 +383,21 @@ def sam_lines(ms, name, seq, qual=None, *, softclip=False, rl=None):
         f.append("rl:i:%d" % t[_G_RL])
         out.append("\t".join(str(x) for x in f))
     return out
+
+
+# the empty BGZF block that ends a BAM file
+BAM_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def bgzf_wrap(data):
+    """`data` (bytes) in stored BGZF blocks of at most 0xff00 bytes of payload each (mm355_bgzf_wrap on the host); b"" gives b"" """
+    L = _ffi.lib()
+    tp = C.POINTER(_ffi.Text)()
+    _ffi.check(L.mm355_bgzf_wrap(None, data, len(data), _ffi.PAF_HOST, C.byref(tp)))
+    try:
+        return bytes(_ffi.text_view(tp))
+    finally:
+        L.mm355_free_text(tp)
 
 
 def shard_by_bases(lengths, n_shards):
@@ -950,6 +966,10 @@ class Aligner:
         Mapping objects.  The lines of a read are sam_lines() of the records map() would return with tags; a read without hits writes one
         unmapped record unless hit_only (minimap2 --sam-hit-only); an empty sequence writes nothing.  names as in map_paf; quals[i] is None or
         a str as long as the read; softclip: minimap2 -Y.  where and `paf_on_device`: as for map_paf."""
+        return self._map_records(self._L.mm355_map_batch_sam, seqs, names, quals, cs, MD, softclip, hit_only, where)
+
+    def _map_records(self, call, seqs, names, quals, cs, MD, softclip, hit_only, where):
+        """map_sam / map_bam: the arguments checked, one call of mm355_map_batch_sam or mm355_map_batch_bam, the text as bytes"""
         flags = self._sam_flags(cs, MD)
         seqs = list(seqs)
         for s in seqs:
@@ -974,8 +994,7 @@ class Aligner:
         sam_flags = (_ffi.SAM_SOFTCLIP if softclip else 0) | (_ffi.SAM_HIT_ONLY if hit_only else 0)
         tp = C.POINTER(_ffi.Text)()
         with self._lock:
-            rc = L.mm355_map_batch_sam(self._context(), C.byref(self._mo), len(seqs), packed.arr, packed.lens, narr, qarr, flags, sam_flags,
-                                       int(where), C.byref(tp))
+            rc = call(self._context(), C.byref(self._mo), len(seqs), packed.arr, packed.lens, narr, qarr, flags, sam_flags, int(where), C.byref(tp))
         if rc != 0:
             raise RuntimeError(L.mm355_strerror(rc).decode())
         try:
@@ -983,6 +1002,33 @@ class Aligner:
             return bytes(_ffi.text_view(tp))
         finally:
             L.mm355_free_text(tp)
+
+    # ---- BAM records (mm355_map_batch_bam): the BAM encoding of map_sam's lines in stored BGZF blocks, formed by the library
+    def map_bam(self, seqs, names=None, quals=None, cs=False, MD=False, *, softclip=False, hit_only=False, where=_ffi.PAF_AUTO):
+        """the BAM records of `seqs` as bytes: whole BGZF blocks (stored, not compressed) without the header (bam_header()) and without the
+        EOF block (BAM_EOF), in input order; one mm355_map_batch_bam call.  A record is the BAM encoding of the line map_sam writes for the
+        same arguments (include/mm355.h states it field by field); the results of consecutive calls, one behind the other, continue the
+        stream.  Besides what map_sam refuses: a read name of more than 254 bytes (RuntimeError).  Arguments and `paf_on_device` as for map_sam."""
+        return self._map_records(self._L.mm355_map_batch_bam, seqs, names, quals, cs, MD, softclip, hit_only, where)
+
+    def bam_header(self):
+        """the BAM header of this index as BGZF blocks: the magic, sam_header() as the text, the contigs with their lengths"""
+        text, L = self.sam_header(), self._L
+        refs = []
+        for i, nm in enumerate(self._names()):
+            b = nm.encode()
+            refs.append(struct.pack("<I", len(b) + 1) + b + b"\0" + struct.pack("<I", L.mm355_index_seq_len(self._idx, i)))
+        return bgzf_wrap(b"BAM\1" + struct.pack("<I", len(text)) + text + struct.pack("<I", len(refs)) + b"".join(refs))
+
+    def map_bam_file(self, reads_path, out_path, cs=False, MD=False, n_threads=None, sub_batch_reads=SUB_BATCH_READS, *, where=_ffi.PAF_AUTO,
+                     softclip=False, hit_only=False):
+        """maps a FASTA / FASTQ file of reads to an uncompressed BAM file (what `samtools view -u` writes; ready for `samtools sort` /
+        `index` without a SAM parse): bam_header(), the records of map_bam per sub-batch in input order, BAM_EOF.  The reader, the workers,
+        the bound on memory, the ".part" file and its rename, what a failure leaves behind and the returned dict are map_file's; n_lines
+        counts records.  A record takes about 1.5 bytes per base with qualities (a SAM line 2) and as much from a FASTA (0xFF per base where
+        SAM prints one `*`): the gain is the consumer's, which parses nothing."""
+        sam_flags = (_ffi.SAM_SOFTCLIP if softclip else 0) | (_ffi.SAM_HIT_ONLY if hit_only else 0)
+        return self._map_file("bam", reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags)
 
     def map_file(self, reads_path, out_path, cs=False, MD=False, n_threads=None, sub_batch_reads=SUB_BATCH_READS, *, where=_ffi.PAF_AUTO, format="paf"):
         """maps a FASTA / FASTQ file of reads (plain or gzip) to a PAF file, lines in input order -- minimap2's command line from a read set to
@@ -1000,9 +1046,14 @@ class Aligner:
         file is opened."""
         if format not in ("paf", "sam"):
             raise ValueError("`format` must be \"paf\" or \"sam\"")
-        sam = format == "sam"
+        return self._map_file(format, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, 0)
+
+    def _map_file(self, kind, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags):
+        """map_file (kind "paf" / "sam") and map_bam_file ("bam"): reader thread, workers, ordered writer, .part file"""
+        sam = kind != "paf"                               # the reader keeps qualities, the call takes them and sam_flags
         flags = self._sam_flags(cs, MD) if sam else self._paf_flags(cs, MD)
-        header = self.sam_header() if sam else b""
+        header = self.sam_header() if kind == "sam" else self.bam_header() if kind == "bam" else b""
+        trailer = BAM_EOF if kind == "bam" else b""
         L = self._L
         nt = self._n_threads if n_threads is None else int(n_threads)
         n_workers = max(1, min(nt, 8)) * len(self._devices)
@@ -1028,6 +1079,7 @@ class Aligner:
         st = {"n_sub": None, "n_reads": 0, "n_bases": 0}
         mo, where = self._mo, int(where)
         acquire, release = self._ctx_acquire, self._ctx_release
+        map_records = L.mm355_map_batch_bam if kind == "bam" else L.mm355_map_batch_sam
 
         def fail(e):
             errors.append(e)
@@ -1052,7 +1104,7 @@ class Aligner:
                         n_bases = int(np.ctypeslib.as_array(r.lens, shape=(n,)).sum(dtype=np.int64))
                         tp = C.POINTER(_ffi.Text)()
                         if sam:
-                            rc = L.mm355_map_batch_sam(ctx[1], C.byref(mo), n, r.seqs, r.lens, r.names, L.mm355_reads_quals(rp), flags, 0, where, C.byref(tp))
+                            rc = map_records(ctx[1], C.byref(mo), n, r.seqs, r.lens, r.names, L.mm355_reads_quals(rp), flags, sam_flags, where, C.byref(tp))
                         else:
                             rc = L.mm355_map_batch_paf(ctx[1], C.byref(mo), n, r.seqs, r.lens, r.names, flags, where, C.byref(tp))
                     finally:
@@ -1122,6 +1174,7 @@ class Aligner:
                 nxt += 1
             if errors:
                 raise errors[0]
+            out.write(trailer)
             out.close()
             os.replace(part, out_path)
         except BaseException:

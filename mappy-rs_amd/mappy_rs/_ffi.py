@@ -67,7 +67,7 @@ class Hits(C.Structure):
                 ("tags", C.POINTER(Tags))]      # parallel to hits; NULL unless OUT_TAGS was asked for
 
 
-class Text(C.Structure):       # mm355_text_t: the PAF lines of one batch
+class Text(C.Structure):       # mm355_text_t: the PAF or SAM lines of one batch, or its BAM records as BGZF blocks
     _fields_ = [("n_reads", C.c_int64), ("n_lines", C.c_int64), ("n_text", C.c_int64), ("line_off", C.POINTER(C.c_int64)),
                 ("text", C.POINTER(C.c_char)), ("ms_format", C.c_double), ("on_device", C.c_int32), ("reserved", C.c_int32)]
 
@@ -120,6 +120,7 @@ EXPORTS = [
     "mm355_index_load_device", "mm355_index_dump", "mm355_index_load_mmi_device",
     "mm355_paf_format", "mm355_map_batch_paf", "mm355_free_text", "mm355_fastx_open", "mm355_fastx_next", "mm355_reads_free", "mm355_fastx_close",
     "mm355_sam_format", "mm355_map_batch_sam", "mm355_fastx_open_qual", "mm355_reads_quals",
+    "mm355_bam_format", "mm355_map_batch_bam", "mm355_bgzf_wrap",
 ]
 
 _LIB = None
@@ -169,6 +170,9 @@ def lib():
                                    C.c_int, C.c_int, C.POINTER(C.POINTER(Text))]
     L.mm355_map_batch_sam.argtypes = [vp, C.POINTER(MapOpt), C.c_int64, C.POINTER(C.c_char_p), i32p, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                       C.c_int, C.c_int, C.c_int, C.POINTER(C.POINTER(Text))]
+    L.mm355_bam_format.argtypes = L.mm355_sam_format.argtypes        # the SAM calls' arguments; the text is BGZF blocks of BAM records
+    L.mm355_map_batch_bam.argtypes = L.mm355_map_batch_sam.argtypes
+    L.mm355_bgzf_wrap.argtypes = [vp, C.c_char_p, C.c_int64, C.c_int, C.POINTER(C.POINTER(Text))]
     L.mm355_fastx_open_qual.argtypes = [C.c_char_p, C.POINTER(vp)]
     L.mm355_reads_quals.argtypes = [C.POINTER(Reads)]
     L.mm355_reads_quals.restype = C.POINTER(C.c_char_p)
