@@ -1152,8 +1152,12 @@ __global__ __launch_bounds__(256) void k_chain_small(DevParams pr, DevBatch bt, 
 #define CH_NEAR (CH_RING - 2 * WAVE)    // j is served from the rings when i - j <= CH_NEAR (the a[] ring also holds one chunk ahead)
 __device__ __forceinline__ void chain_big_segment(const DevParams &pr, const DevBatch &bt, const DevAnchors &an, const ChainSeg *segs, unsigned int n_segs, unsigned long long *pairs_ctr, const unsigned int bid)
 {
-	// t[] marks of the active window, circular by anchor index: 15 bits of the marking anchor + a valid bit (a stale mark
-	// would need an index distance that is a multiple of 32768, larger than window + ring size)
+	// t[] marks of the active window, circular by anchor index: 15 bits of the marking anchor + a valid bit.  The only question ever asked
+	// is `tw[j] == mark of the current i`.  A slot keeps what was written until one of its aliases (s + 8192 k) is somebody's predecessor
+	// again, which may be never, so a mark could still be there 32768 anchors later, when its value comes round, and answer for j + 32768.
+	// The table is therefore cleared again whenever (i & 0x7fff) == 0 (below): every mark in it was then written at an anchor of the
+	// current run of 32768, within which the 15 bits are distinct, so a slot equals the mark of i only if it was written at i; within one
+	// anchor the window holds at most 8000 j (max_chain_iter is checked by the host), fewer than the slots, so no two of them share one.
 	__shared__ uint16_t tw[TW_SIZE];
 	// The last CH_RING anchors and their f/p/v live in LDS rings: the loop-carried dependence of the chain never waits for HBM.
 	// a[] enters the ring one 64-anchor chunk ahead of the sweep (coalesced load, issued a chunk earlier); f/p/v are written by
@@ -1190,6 +1194,10 @@ __device__ __forceinline__ void chain_big_segment(const DevParams &pr, const Dev
 		if (((i - i_begin) & (WAVE - 1)) == 0) {   // chunk boundary: publish the prefetched chunk, fetch the next one
 			if (i + lane < n) { rax[(i + lane) & CH_XMASK] = nx.x; ray[(i + lane) & CH_RMASK] = nx.y; }
 			if (i + WAVE + lane < n) nx = a[i + WAVE + lane];
+			CH_SYNC();
+		}
+		if ((i & 0x7fff) == 0) {                   // the marks come round: none of an earlier anchor is needed again (see tw[] above)
+			for (int k = lane; k < TW_SIZE; k += WAVE) tw[k] = 0;
 			CH_SYNC();
 		}
 		const uint64_t aix = rax[i & CH_XMASK], aiy = ray[i & CH_RMASK];

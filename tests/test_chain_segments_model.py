@@ -8,6 +8,7 @@ import pytest
 
 from oracle import oracle as O
 import synthdata as S
+from _chain_census import segment_starts
 
 
 @pytest.fixture(scope="module")
@@ -37,8 +38,7 @@ def test_segments_chain_independently(world, kw):
         mdx = mo.max_gap_ref if mo.max_gap_ref > 0 else (max(mo.max_frag_len - qlen, mo.max_gap) if mo.max_frag_len > 0 else mo.max_gap)
         mdx = max(mdx, mo.bw)
         x = a[:, 0]
-        start = np.ones(n, bool)
-        start[1:] = ((x[1:] >> np.uint64(32)) != (x[:-1] >> np.uint64(32))) | (x[1:] > x[:-1] + np.uint64(mdx))      # the rule of k_chain_segments
+        start = segment_starts(x, mdx)      # the rule of k_chain_segments
         f, p, v, t = orc.chain_fill(a, qlen)
         bounds = np.append(np.nonzero(start)[0], n)
         for b, e in zip(bounds[:-1], bounds[1:]):
