@@ -1,7 +1,7 @@
 // mm355_bam.h -- the BAM records of one read and their BGZF framing, stated once (the rule is written out in include/mm355.h): a record is the
 // BAM encoding of the SAM line sam_emit_line writes for the same row under the same sam_flags.  One emitter, templated on a sink, as
-// mm355_sam.h: the counting sink and the writing sinks run the same code, and the host formatter below is that emitter run serially plus
-// host framing with zlib's crc32.  Plain C++ that also compiles as device code (tests/host_harness/bam_host.cpp builds it with g++ alone).
+// mm355_sam.h: the counting sink and the writing sinks run the same code, and the host formatter (mm355_bam_format_host) is that emitter
+// run serially plus host framing with zlib's crc32.  Plain C++ that also compiles as device code (tests/host_harness/bam_host.cpp builds it with g++ alone).
 //
 // A sink has binary primitives: ch(c) / u8(v) one byte, u16(v) and u32(v) little-endian, bytes(p, n) a run that exists in memory (names,
 // cs, MD), cigar(w, n) n packed CIGAR words as they are (len<<4 | op is BAM's own word), seq4(p, n, rev) n bases packed two per byte,
@@ -290,46 +290,26 @@ inline void mm355_bgzf_frame_host(const char *data, int64_t n, char *out)
 	}
 }
 
-// The host formatter: the emitter run serially, once to count and once to write, then the framing.  The arguments must have passed
-// mm355_bam_check.  line_off counts in the unframed stream of records.
+// ---- the format as the shared writers see it (the host walk of mm355_sam.h; the device record writer, mm355_recdev.h)
+struct BamFmt {
+	typedef SamLine Line; typedef BamCountSink HostCount; typedef BamWriteSink HostWrite;
+	enum { RUNS = 5 };                                                 // runs of a record the wave copies: qname, the CIGAR words, cs, MD, the CG words
+	static constexpr bool WAVE_CIGAR = false, TILED = true, FRAMED = true;   // the CIGAR is a run of words; SEQ and QUAL go in tiles; the result is the stream in BGZF blocks
+	// the fixed part of a record is 36 bytes, and block_size is 32 bits; records the upload takes (the tile table has two runs per record)
+	static constexpr int64_t MIN_RECORD = 36, MAX_RECORD = (int64_t)UINT32_MAX + 4, MAX_LINES = INT32_MAX / 2;
+	static MM_HD int64_t word_term(uint32_t w) { return bam_ref_len(w); }   // summed over a row's CIGAR words: the reference length (the bin needs it)
+	template <typename S> static MM_HD void emit(S &s, const SamLine &L, int64_t reflen, uint32_t block_size) { bam_emit_record(s, L, reflen, block_size); }
+	static int64_t n_lines(const mm355_hits_t *H, const int32_t *qlens, int sam_flags, int64_t i) { return mm355_sam_n_lines(H, qlens, sam_flags, i); }
+	static int64_t host_sum(const mm355_hits_t *H, const mm355_hit_t &h) { return mm355_bam_reflen(H, h); }
+	static int64_t out_size(int64_t n) { return bgzf_size(n); }
+	static void frame_host(const char *raw, int64_t n, char *out) { mm355_bgzf_frame_host(raw, n, out); }
+};
+
+// line_off counts in the unframed stream of records
 inline int mm355_bam_format_host(const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens, const char *const *quals,
                                  const int32_t *rep_len, const PafNames &pn, int sam_flags, mm355_text_t **out)
 {
-	*out = 0;
-	const SamNames nm(pn);
-	std::vector<int64_t> off, first((size_t)H->n_reads + 1);
-	int64_t tot = 0;
-	for (int64_t i = 0; i < H->n_reads; ++i) {
-		first[i] = (int64_t)off.size();
-		const int64_t nl = mm355_sam_n_lines(H, qlens, sam_flags, i);
-		if (nl == 0) continue;
-		const SamRead R = mm355_sam_read_of(H, i, qnames, seqs, qlens, quals, rep_len, nm, sam_flags);
-		for (int64_t j = 0; j < nl; ++j) {
-			BamCountSink cs;
-			bam_emit_record(cs, SamLine{ &R, R.n_rows? (int32_t)j : -1 }, R.n_rows? mm355_bam_reflen(H, R.rows[j]) : 0, 0);
-			if (cs.n - 4 > (int64_t)UINT32_MAX) return MM355_EINVAL;     // (block_size is 32 bits)
-			off.push_back(tot); tot += cs.n;
-		}
-	}
-	first[H->n_reads] = (int64_t)off.size();
-	off.push_back(tot);
-	std::vector<char> raw((size_t)tot + 1);
-	mm355_text_t *T = mm355_text_alloc(H->n_reads, (int64_t)off.size() - 1, bgzf_size(tot));
-	if (T == 0) return MM355_ENOMEM;
-	for (int64_t i = 0; i <= H->n_reads; ++i) T->line_off[i] = off[first[i]];
-	for (int64_t i = 0; i < H->n_reads; ++i) {
-		if (first[i + 1] == first[i]) continue;
-		const SamRead R = mm355_sam_read_of(H, i, qnames, seqs, qlens, quals, rep_len, nm, sam_flags);
-		for (int64_t l = first[i]; l < first[i + 1]; ++l) {
-			BamWriteSink ws(raw.data() + off[l]);
-			const int32_t j = (int32_t)(l - first[i]);
-			bam_emit_record(ws, SamLine{ &R, R.n_rows? j : -1 }, R.n_rows? mm355_bam_reflen(H, R.rows[j]) : 0, (uint32_t)(off[l + 1] - off[l] - 4));
-			if (ws.n != off[l + 1] - off[l]) { mm355_free_text_host(T); return MM355_EINVAL; }   // the two passes disagree: a bug, never a short record
-		}
-	}
-	mm355_bgzf_frame_host(raw.data(), tot, T->text);
-	*out = T;
-	return 0;
+	return mm355_rec_format_host<BamFmt>(H, qnames, seqs, qlens, quals, rep_len, pn, sam_flags, out);
 }
 
 // mm355_bgzf_wrap on the host

@@ -1,6 +1,7 @@
 // mm355_paf.h -- the PAF line of one hit, stated once: mappy_rs.paf_line (format.c::mm_write_paf + write_tags) byte for byte.
 // One emitter, templated on a sink: a counting sink and a writing sink run the same code, so the length pass and the write pass of the
-// device formatter (mm355_paf.hip) cannot disagree, and the host formatter below is that emitter run serially -- the readable statement.
+// device formatter (mm355_recdev.h, instantiated with PafFmt) cannot disagree, and the host formatter below is that emitter run serially --
+// the readable statement.
 // Plain C++ that also compiles as device code (tests/host_harness/paf_host.cpp builds it with g++ alone).
 //
 // A sink has: ch(c) one byte; bytes(p, n) a run of bytes that exists in memory already (names, cs, MD); cigar(w, n) the text of n packed
@@ -148,6 +149,18 @@ template <typename S> MM_HD void paf_emit_line(S &s, const PafLine &L)
 	s.ch('\n');
 }
 
+// ---- the format as the shared record writer sees it (mm355_recdev.h): compile-time facts only
+struct PafFmt {
+	typedef PafLine Line;
+	enum { RUNS = 4 };                                                 // runs of a line the wave copies: qname, tname, cs, MD
+	static constexpr bool WAVE_CIGAR = true, TILED = false;            // the CIGAR is text, which the wave writes; a line has no SEQ and QUAL
+	static constexpr int64_t MIN_RECORD = 1, MAX_LINES = INT32_MAX;    // every line has its newline at least; what the upload takes
+	static MM_HD int64_t word_term(uint32_t w) { return paf_cigar_width(w); }   // summed over a row's CIGAR words: the length of the cg:Z: text
+	template <typename S> static MM_HD void emit(S &s, const PafLine &L, int64_t, uint32_t) { paf_emit_line(s, L); }
+	// how many lines read i writes: its hits (H->status may be absent)
+	static int64_t n_lines(const mm355_hits_t *H, const int32_t *, int, int64_t i) { return H->hit_off[i + 1] - H->hit_off[i]; }
+};
+
 // ---- the serial sinks
 struct PafCountSink {
 	int64_t n = 0;
@@ -162,28 +175,6 @@ struct PafWriteSink {
 	MM_HD void bytes(const char *b, int64_t l) { for (int64_t i = 0; i < l; ++i) p[n++] = b[i]; }
 	MM_HD void cigar(const uint32_t *w, int64_t k) { for (int64_t i = 0; i < k; ++i) { paf_u64(*this, w[i] >> 4); ch(paf_cigar_op(w[i])); } }
 };
-
-#ifdef __HIPCC__
-#include "mm355_wave.h"
-// the text of nc CIGAR words, written by a whole wave in tiles of 64 operations: a prefix sum of the operations' widths, every lane its own
-// digits and letter, the running offset carried from tile to tile (uniform trip count: the scan needs every lane)
-__device__ __forceinline__ void paf_wave_cigar(char *dst, const uint32_t *w, int64_t nc, int lane)
-{
-	for (int64_t base = 0; base < nc; base += 64) {
-		const bool have = base + lane < nc;
-		const uint32_t x = have? w[base + lane] : 0u;
-		const int32_t wid = have? paf_cigar_width(x) : 0;
-		const int32_t incl = wave_incl_scan_add(wid);
-		if (have) {
-			char *q = dst + (incl - wid);
-			uint32_t v = x >> 4;
-			for (int i = wid - 2; i >= 0; --i) { q[i] = (char)('0' + v % 10); v /= 10; }
-			q[wid - 1] = paf_cigar_op(x);
-		}
-		dst += __builtin_amdgcn_readlane(incl, 63);
-	}
-}
-#endif
 
 // ------------------------------------------------------------------ host side
 #include <stdlib.h>

@@ -134,9 +134,8 @@ struct mm355_ctx : mm355_streams {
 	DBuf x_jobs, x_cig, x_cs, x_out, x_dense; HBuf h_xjobs, h_xcig, h_xout, h_xcs;   // k_extra (mm_update_extra's walk + cs on the device)
 	DBuf logt, regs_scr, regs_in; HBuf h_regs_in, h_regs_out;  // chain-only region stage (mm355_regs.hip): host-logf table, scratch + rows, read tables
 	bool logt_ok = false;
-	DBuf paf_in, paf_work, paf_text; HBuf h_paf_in, h_paf_out;   // PAF writer (mm355_paf.hip): rows + arenas + names up, lengths / offsets / scan space, the text; pinned staging both ways
-	DBuf sam_in, sam_work, sam_text; HBuf h_sam_in, h_sam_out;   // SAM writer (mm355_sam.hip): the same roles; sam_in also holds the reads and qualities the lines print
-	DBuf bam_out;                          // BAM writer (mm355_bam.hip): the BGZF blocks; its uploads, tables and unframed records use the SAM writer's buffers
+	DBuf rec_in, rec_work, rec_text; HBuf h_rec_in, h_rec_out;   // record writer (mm355_recdev.h; PAF, SAM and BAM, one call at a time): rows + arenas + names + reads up, lengths / offsets / runs / scan space, the unframed text; pinned staging both ways
+	DBuf bam_out;                          // BAM writer (mm355_bam.hip): the BGZF blocks
 	mm355_stats_t stats;
 	mm355_timer_book timers;           // lazy stage timers (EvTimer, mm355_kt)
 	unsigned long long pairs_land[64] = {};   // landing zone of the chain stage's pair counters (mm355_run_backtrack)

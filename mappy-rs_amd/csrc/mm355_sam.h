@@ -181,40 +181,66 @@ inline SamRead mm355_sam_read_of(const mm355_hits_t *H, int64_t i, const char *c
 	return R;
 }
 
-// The host formatter: the emitter run serially, once to count and once to write.  The arguments must have passed mm355_sam_check.
-inline int mm355_sam_format_host(const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens, const char *const *quals,
-                                 const int32_t *rep_len, const PafNames &pn, int sam_flags, mm355_text_t **out)
+// ---- the format as the shared writers see it (the host walk below; the device record writer, mm355_recdev.h): compile-time facts only
+struct SamFmt {
+	typedef SamLine Line; typedef SamCountSink HostCount; typedef SamWriteSink HostWrite;
+	enum { RUNS = 4 };                                                 // runs of a line the wave copies: qname, rname, cs, MD
+	static constexpr bool WAVE_CIGAR = true, TILED = true, FRAMED = false;   // the CIGAR is text, which the wave writes; SEQ and QUAL go in tiles; the text is the result
+	// every line has its newline at least, and none is too long; lines the upload takes (the tile table has two runs per line)
+	static constexpr int64_t MIN_RECORD = 1, MAX_RECORD = INT64_MAX, MAX_LINES = INT32_MAX / 2;
+	static MM_HD int64_t word_term(uint32_t w) { return paf_cigar_width(w); }   // summed over a row's CIGAR words: the length of the CIGAR text
+	template <typename S> static MM_HD void emit(S &s, const SamLine &L, int64_t, uint32_t) { sam_emit_line(s, L); }
+	static int64_t n_lines(const mm355_hits_t *H, const int32_t *qlens, int sam_flags, int64_t i) { return mm355_sam_n_lines(H, qlens, sam_flags, i); }
+	static int64_t host_sum(const mm355_hits_t *, const mm355_hit_t &) { return 0; }   // (the serial sinks spell the CIGAR out)
+	static int64_t out_size(int64_t n) { return n; }
+};
+
+// The host formatter of a format whose records carry the read (SamFmt; BamFmt of mm355_bam.h): the emitter run serially, once to count and
+// once to write, then the format's framing if it has one.  The arguments must have passed the format's check.  line_off counts in the
+// unframed text.
+template <typename F> inline int mm355_rec_format_host(const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens,
+                                                       const char *const *quals, const int32_t *rep_len, const PafNames &pn, int sam_flags, mm355_text_t **out)
 {
 	*out = 0;
 	const SamNames nm(pn);
-	std::vector<int64_t> off;
-	std::vector<int64_t> first((size_t)H->n_reads + 1);
+	std::vector<int64_t> off, first((size_t)H->n_reads + 1);
 	int64_t tot = 0;
 	for (int64_t i = 0; i < H->n_reads; ++i) {
 		first[i] = (int64_t)off.size();
-		const int64_t nl = mm355_sam_n_lines(H, qlens, sam_flags, i);
+		const int64_t nl = F::n_lines(H, qlens, sam_flags, i);
 		if (nl == 0) continue;
 		const SamRead R = mm355_sam_read_of(H, i, qnames, seqs, qlens, quals, rep_len, nm, sam_flags);
 		for (int64_t j = 0; j < nl; ++j) {
-			SamCountSink cs;
-			sam_emit_line(cs, SamLine{ &R, R.n_rows? (int32_t)j : -1 });
+			typename F::HostCount cs;
+			F::emit(cs, SamLine{ &R, R.n_rows? (int32_t)j : -1 }, R.n_rows? F::host_sum(H, R.rows[j]) : 0, 0);
+			if (cs.n > F::MAX_RECORD) return MM355_EINVAL;
 			off.push_back(tot); tot += cs.n;
 		}
 	}
 	first[H->n_reads] = (int64_t)off.size();
 	off.push_back(tot);
-	mm355_text_t *T = mm355_text_alloc(H->n_reads, (int64_t)off.size() - 1, tot);
+	std::vector<char> raw(F::FRAMED? (size_t)tot + 1 : 0);
+	mm355_text_t *T = mm355_text_alloc(H->n_reads, (int64_t)off.size() - 1, F::out_size(tot));
 	if (T == 0) return MM355_ENOMEM;
+	char *dst = F::FRAMED? raw.data() : T->text;
 	for (int64_t i = 0; i <= H->n_reads; ++i) T->line_off[i] = off[first[i]];
 	for (int64_t i = 0; i < H->n_reads; ++i) {
 		if (first[i + 1] == first[i]) continue;
 		const SamRead R = mm355_sam_read_of(H, i, qnames, seqs, qlens, quals, rep_len, nm, sam_flags);
 		for (int64_t l = first[i]; l < first[i + 1]; ++l) {
-			SamWriteSink ws(T->text + off[l]);
-			sam_emit_line(ws, SamLine{ &R, R.n_rows? (int32_t)(l - first[i]) : -1 });
-			if (ws.n != off[l + 1] - off[l]) { mm355_free_text_host(T); return MM355_EINVAL; }   // the two passes disagree: a bug, never a short line
+			typename F::HostWrite ws(dst + off[l]);
+			const int32_t j = (int32_t)(l - first[i]);
+			F::emit(ws, SamLine{ &R, R.n_rows? j : -1 }, R.n_rows? F::host_sum(H, R.rows[j]) : 0, (uint32_t)(off[l + 1] - off[l] - 4));
+			if (ws.n != off[l + 1] - off[l]) { mm355_free_text_host(T); return MM355_EINVAL; }   // the two passes disagree: a bug, never a short record
 		}
 	}
+	if constexpr (F::FRAMED) F::frame_host(raw.data(), tot, T->text);
 	*out = T;
 	return 0;
+}
+
+inline int mm355_sam_format_host(const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens, const char *const *quals,
+                                 const int32_t *rep_len, const PafNames &pn, int sam_flags, mm355_text_t **out)
+{
+	return mm355_rec_format_host<SamFmt>(H, qnames, seqs, qlens, quals, rep_len, pn, sam_flags, out);
 }

@@ -1,7 +1,8 @@
-"""The BAM writer on the GPU (mm355_bam.hip: k_bam_len, the scans, k_bam_fields, k_bam_bulk, k_bgzf_frame): the framing kernel against
+"""The BAM writer on the GPU (mm355_recdev.h with BamFmt: k_rec_len, the scans, k_rec_fields; mm355_bam.hip: k_bam_bulk, k_bgzf_frame): the framing kernel against
 tests/_bam.py::frame byte for byte; the device formatter against the host formatter and record_of of mappy_rs.sam_lines on constructed
 result sets (tests/_bam_sets.py); end to end through Aligner.map_bam on the two-contig world of tests/test_gpu_tags.py, and from a reads
-file to a BAM file through Aligner.map_bam_file.  CPU side: tests/test_bam_host.py."""
+file to a BAM file through Aligner.map_bam_file; and the three writers in turn on one context, whose one set of buffers they share.
+CPU side: tests/test_bam_host.py."""
 import ctypes as C
 import gzip
 import os
@@ -16,9 +17,10 @@ import synthdata as S
 import _bam
 import _bam_sets as BS
 import _capi
+import _paf_sets as PS
 import _sam_sets as SS
 from test_gpu_tags import world, _rc          # noqa: F401  (the fixture: its genome and reads)
-from test_gpu_sam import _sam_reads, _write_fastq_gz
+from test_gpu_sam import _format as _sam_format, _sam_reads, _write_fastq_gz
 
 OUT_CS, OUT_MD, OUT_TAGS = 1, 2, 4
 P = _bam.PAYLOAD
@@ -173,6 +175,70 @@ def test_format_refuses_what_bam_cannot_hold(stage):
         for name, s in BS.refused_sets():
             rc = _format(stage, SS.sam_args(s), where, raw=True, sam_flags=s["sam_flags"])
             assert rc == (0 if name in ("good", "name254") else _ffi.MM355_EINVAL), (where, name)
+
+
+# ---------------------------------------------------------------- all writers on one context
+def _shared_buffer_sets(rng):
+    """large: three reads -- one of 2 * TILE + 1 bases with quality, whose primary has a CIGAR of 150 operations and cs and MD strings and whose
+    reverse-strand hard-clipped supplementary has 70 operations and takes more than a tile, one without quality, one without hits: more than
+    one tile per run, more than one CIGAR tile of the wave.  small: one read of 40 bases, one hit."""
+    cigar, sbuf = [], b":17*ac:5\0" + b"17A3^C" * 40 + b"\0"
+    (sq0, ql0), (sq1, _), (sq2, ql2) = SS.random_read(rng, 2 * TILE + 1), SS.random_read(rng, 333), SS.random_read(rng, 77)
+    rows = [_row(0, len(sq0), 1, 0, cigar, 150), _row(17, 17 + TILE + 5, -1, 1, cigar, 70, 1), _row(3, 300, -1, 2, cigar, 3, 2)]
+    rows[0][0].update(cs_off=0, cs_len=9, md_off=10, md_len=240)
+    large = BS.scrub(SS.make_set([r for r, _ in rows], [t for _, t in rows], [0, 2, 3, 3], [0, 0, 0], ["first read", "second", None], [sq0, sq1, sq2],
+                                 [ql0, None, ql2], [0, 0, 5], 0, cigar=cigar, sbuf=sbuf), rng)
+    cigar = []
+    sq, ql = SS.random_read(rng, 40)
+    r, t = _row(2, 38, 1, 0, cigar)
+    small = BS.scrub(SS.make_set([r], [t], [0, 1], [0], ["s"], [sq], [ql], [0], 0, cigar=cigar), rng)
+    return large, small
+
+
+def test_all_writers_share_one_context(built, tmp_path):
+    """mm355_bam_format, _paf_format, _sam_format, _paf_format, _bam_format, mm355_bgzf_wrap, _sam_format on one context, on the device, the
+    large and the small set by turns, beginning once with the small one on a context that has written nothing (every buffer has to grow for
+    the large one) and once with the large one: each result is the host formatter's on the same set.  A length taken from a buffer's
+    capacity, or from what the call before left there, shows in a small call after a large one."""
+    import mappy_rs
+    from mappy_rs import _ffi
+    fa = str(tmp_path / "three.fa")
+    S.write_fasta(fa, S.make_genome(5, [3000, 3000, 3000]), SS.CONTIGS)
+    al = mappy_rs.Aligner(fa, preset="map-ont")
+    L = al._L
+
+    def bam(s, where):
+        return _format(al, s, where)
+
+    def paf(s, where):
+        h, qn, ql, keep = PS.hits_struct(s)
+        tp = C.POINTER(_ffi.Text)()
+        _ffi.check(L.mm355_paf_format(al._context(), C.byref(al._mo), C.byref(h), qn, ql, where, C.byref(tp)))   # (al._mo: CIGAR mode)
+        try:
+            t = tp.contents
+            return bytes(_ffi.text_view(tp)), [t.line_off[i] for i in range(t.n_reads + 1)], t.on_device, t.n_lines
+        finally:
+            L.mm355_free_text(tp)
+
+    def sam(s, where):
+        text, off, on = _sam_format(al, s, where)
+        return text, off, on, text.count(b"\n")
+
+    def wrap(s, where):
+        data = b"".join(BS.expected(s)[0])
+        return _wrap(al, data, where) + (len(data),)
+
+    sets = _shared_buffer_sets(np.random.default_rng(31))
+    assert len(sets[0]["cigar"]) > 64 and sets[0]["hits"][1]["strand"] < 0 and len(sets[0]["seqs"][0]) == 2 * TILE + 1 and len(sets[1]["seqs"][0]) == 40
+    calls = (bam, paf, sam, paf, bam, wrap, sam)
+    want = {(f, k): f(s, _ffi.PAF_HOST) for f in set(calls) for k, s in enumerate(sets)}
+    assert all(w[-2] == 0 for w in want.values()) and want[(paf, 0)][3] == 3 and want[(sam, 0)][3] == 4 and want[(paf, 1)][3] == 1
+    for first in (1, 0):
+        for n, f in enumerate(calls):
+            k = (first + n) % 2
+            got = f(sets[k], _ffi.PAF_DEVICE)
+            w = want[(f, k)]
+            assert got[-2] == 1 and got[0] == w[0] and (f is wrap or got[1] == w[1]) and got[-1] == w[-1], (first, n, k, len(got[0]), len(w[0]))
 
 
 # ---------------------------------------------------------------- end to end

@@ -1,4 +1,4 @@
-"""The PAF writer on the GPU (mm355_paf.hip: k_paf_len, the scan, k_paf_write): the device formatter against the host formatter and
+"""The PAF writer on the GPU (mm355_recdev.h with PafFmt: k_rec_len, the scan, k_rec_fields): the device formatter against the host formatter and
 mappy_rs.paf_line, byte for byte -- on constructed result sets (tests/_paf_sets.py), end to end through Aligner.map_paf on the two-contig
 world of tests/test_gpu_tags.py, and from a reads file to a PAF file through Aligner.map_file.  CPU side: tests/test_paf_host.py."""
 import ctypes as C

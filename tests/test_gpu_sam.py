@@ -1,4 +1,4 @@
-"""The SAM writer on the GPU (mm355_sam.hip: k_sam_len, the scans, k_sam_fields, k_sam_copy): the device formatter against the host formatter
+"""The SAM writer on the GPU (mm355_recdev.h with SamFmt: k_rec_len, the scans, k_rec_fields; mm355_sam.hip: k_sam_copy): the device formatter against the host formatter
 and mappy_rs.sam_lines, byte for byte -- on constructed result sets (tests/_sam_sets.py), end to end through Aligner.map_sam on the
 two-contig world of tests/test_gpu_tags.py, and from a reads file to a SAM file through Aligner.map_file.  CPU side: tests/test_sam_host.py."""
 import ctypes as C
