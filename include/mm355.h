@@ -303,6 +303,22 @@ int mm355_map_batch_bam(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_re
  * as the host's crc32 reads.  n_lines counts the blocks, n_reads is 0.  The BAM header of a file goes through here. */
 int mm355_bgzf_wrap(mm355_ctx_t *ctx, const void *data, int64_t n, int where, mm355_text_t **out);
 
+/* --- compressed BAM: the three calls above with `int level` -- 0: the stored blocks, byte for byte what the call without it writes (which is
+ * this one at level 0); 1: every BGZF payload as one dynamic-Huffman deflate block (RFC 1951: LZ77 matches inside the payload, one code set per
+ * payload), or stored as at level 0 where that would not be shorter, so that no block is longer than at level 0 and BSIZE always fits; any
+ * other level: MM355_EINVAL, before anything is allocated, mapped or launched.  The gzip header, CRC-32 and ISIZE are level 0's; BSIZE is the
+ * block's real size.  What `samtools view -b` writes and htslib reads.  The coder is stated once (mm355_deflate.h) and runs as a kernel with
+ * a workgroup per payload (mm355_bam.hip: k_bgzf_deflate, a scan of the block sizes, k_bgzf_compact) or serially on the host: the same bytes,
+ * and the same bytes from call to call.  `text` is the blocks, n_lines the records (the blocks for mm355_bgzf_deflate), and line_off still
+ * points into the UNFRAMED stream: the arithmetic block-offset formula above holds at level 0 only -- at level 1 walk the blocks by BSIZE.
+ * `where` as for the level-0 calls, with the same thresholds.  MM355_BAM_TIMES=1: a level-1 call on the device prints a line of its own on
+ * stderr (the kernels' time between two events, bytes in and out, stored blocks). */
+int mm355_bam_format_deflate(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, const mm355_hits_t *hits, const char *const *qnames, const char *const *seqs,
+                             const int32_t *qlens, const char *const *quals, const int32_t *rep_len, int sam_flags, int where, int level, mm355_text_t **out);
+int mm355_map_batch_bam_deflate(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
+                                const char *const *names, const char *const *quals, int flags, int sam_flags, int where, int level, mm355_text_t **out);
+int mm355_bgzf_deflate(mm355_ctx_t *ctx, const void *data, int64_t n, int where, int level, mm355_text_t **out);
+
 /* --- streaming FASTA / FASTQ reader, plain or gzip: the record rules of the index builder's parser (the name ends at the first blank,
  * multi-line sequences, a '+' line followed by quality as long as the sequence, CRLF).  A read set is cut into sub-batches without ever
  * being in memory as a whole.  mm355_fastx_next returns the next records: at least one, at most max_reads, and no record that would take

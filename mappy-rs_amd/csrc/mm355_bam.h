@@ -302,7 +302,7 @@ struct BamFmt {
 	static int64_t n_lines(const mm355_hits_t *H, const int32_t *qlens, int sam_flags, int64_t i) { return mm355_sam_n_lines(H, qlens, sam_flags, i); }
 	static int64_t host_sum(const mm355_hits_t *H, const mm355_hit_t &h) { return mm355_bam_reflen(H, h); }
 	static int64_t out_size(int64_t n) { return bgzf_size(n); }
-	static void frame_host(const char *raw, int64_t n, char *out) { mm355_bgzf_frame_host(raw, n, out); }
+	static int64_t frame_host(const char *raw, int64_t n, char *out) { mm355_bgzf_frame_host(raw, n, out); return bgzf_size(n); }   // the bytes written: out_size(n) at most
 };
 
 // line_off counts in the unframed stream of records

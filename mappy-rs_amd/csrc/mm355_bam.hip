@@ -11,8 +11,15 @@
 //   k_bgzf_frame  one workgroup per BGZF block of the unframed stream: header, payload (aligned 16-byte stores from shifted source dwords),
 //                 CRC-32 by lanes with fixed-length chunks read 16 bytes at a time and a table in LDS (mm355_bam.h: bgzf_lane_crc, the combine
 //                 and the tail of a short last block), ISIZE.  Block b starts at b * (0xff00 + 31): the output offsets are arithmetic.
+// or (level 1) deflated by a pass that takes k_bgzf_frame's place:
+//   k_bgzf_deflate  a workgroup per payload, a grid of resident workgroups that loops over the blocks: the coder of mm355_deflate.h, its lanes
+//                 the threads -- the hash table in LDS, candidates and tokens in the workgroup's 255 KB of global scratch, the histograms by LDS
+//                 atomics, the ranking by all threads and the codes by one, a scan of the segments' bits, and the block (gzip header, stream,
+//                 CRC-32 by the framing kernel's lanes, ISIZE) OR-ed together in the LDS the table had, then stored to the staging buffer in
+//                 16-byte pieces at DFL_STRIDE * block.  A payload that deflate would not shorten is framed exactly as k_bgzf_frame does.
+//   k_bgzf_compact  after an exclusive scan of the blocks' sizes: every block to its place, aligned 16-byte stores from shifted source dwords.
 #include "mm355_recdev.h"
-#include "mm355_bam.h"
+#include "mm355_deflate.h"
 
 #define BAM_TILE 4096         // output bytes of one k_bam_bulk block: 256 threads x 16 bytes
 
@@ -88,20 +95,10 @@ __global__ __launch_bounds__(256) void k_bam_bulk(const RecTileRun *bulk, const 
 	}
 }
 
-// in: n bytes, readable for 8 more (whole dwords are read around a span); out: bgzf_size(n) bytes; one workgroup per block
-__global__ __launch_bounds__(BGZF_LANES) void k_bgzf_frame(const char *in, int64_t n, char *out)
+// len bytes from src to dst by the block's threads: a thread owns an aligned 16-byte piece of the destination, the ragged ends are byte
+// stores; src is readable for 8 bytes more (whole dwords are read around a span)
+__device__ __forceinline__ void bgzf_copy(const char *src, char *dst, uint32_t len, int tid)
 {
-	__shared__ uint32_t tab[256], reg[BGZF_LANES], x_pow[8];
-	const int tid = threadIdx.x;
-	tab[tid] = crc32_tab_entry((uint32_t)tid);
-	if (tid < 8) x_pow[tid] = crc32_x2n(11 + tid);
-	const int64_t b = blockIdx.x, at = b * BGZF_PAYLOAD;
-	const uint32_t len = (uint32_t)(n - at < BGZF_PAYLOAD? n - at : BGZF_PAYLOAD);
-	const char *src = in + at;
-	char *o = out + b * (BGZF_PAYLOAD + BGZF_EXTRA);
-	if (tid < BGZF_HEAD) o[tid] = (char)bgzf_head_byte(tid, len);
-	// the payload: a thread owns an aligned 16-byte piece of the destination, the ragged ends are byte stores
-	char *dst = o + BGZF_HEAD;
 	const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + len;
 	for (uintptr_t c = (d0 & ~(uintptr_t)15) + 16 * (uintptr_t)tid; c < d1; c += 16 * BGZF_LANES) {
 		if (c >= d0 && c + 16 <= d1) {
@@ -113,7 +110,10 @@ __global__ __launch_bounds__(BGZF_LANES) void k_bgzf_frame(const char *in, int64
 			for (uintptr_t a = c > d0? c : d0; a < e; ++a) *(char*)a = src[a - d0];
 		}
 	}
-	__syncthreads();
+}
+// the CRC-32 of a payload by the block's lanes; thread 0 has it.  tab and x_pow are filled and a barrier has passed since
+__device__ __forceinline__ uint32_t bgzf_block_crc(const char *src, uint32_t len, const uint32_t *tab, uint32_t *reg, const uint32_t *x_pow, int tid)
+{
 	reg[tid] = bgzf_lane_crc((const unsigned char*)src, len, tid, tab);
 	__syncthreads();
 	for (int level = 0; level < 8; ++level) {
@@ -124,10 +124,118 @@ __global__ __launch_bounds__(BGZF_LANES) void k_bgzf_frame(const char *in, int64
 		if (mine) reg[tid] = x;
 		__syncthreads();
 	}
-	if (tid == 0) {
-		const uint32_t crc = ~bgzf_tail_crc((const unsigned char*)src, len, reg[0], tab);
+	return tid == 0? ~bgzf_tail_crc((const unsigned char*)src, len, reg[0], tab) : 0u;
+}
+// one stored block at o: header, payload, CRC-32, ISIZE
+__device__ __forceinline__ void bgzf_stored_block(const char *src, uint32_t len, char *o, const uint32_t *tab, uint32_t *reg, const uint32_t *x_pow, int tid)
+{
+	if (tid < BGZF_HEAD) o[tid] = (char)bgzf_head_byte(tid, len);
+	char *dst = o + BGZF_HEAD;
+	bgzf_copy(src, dst, len, tid);
+	__syncthreads();
+	const uint32_t crc = bgzf_block_crc(src, len, tab, reg, x_pow, tid);
+	if (tid == 0)
 		for (int i = 0; i < 4; ++i) { dst[len + i] = (char)(crc >> 8 * i); dst[len + 4 + i] = (char)(len >> 8 * i); }
+}
+
+// in: n bytes, readable for 8 more (whole dwords are read around a span); out: bgzf_size(n) bytes; one workgroup per block
+__global__ __launch_bounds__(BGZF_LANES) void k_bgzf_frame(const char *in, int64_t n, char *out)
+{
+	__shared__ uint32_t tab[256], reg[BGZF_LANES], x_pow[8];
+	const int tid = threadIdx.x;
+	tab[tid] = crc32_tab_entry((uint32_t)tid);
+	if (tid < 8) x_pow[tid] = crc32_x2n(11 + tid);
+	const int64_t b = blockIdx.x, at = b * BGZF_PAYLOAD;
+	const uint32_t len = (uint32_t)(n - at < BGZF_PAYLOAD? n - at : BGZF_PAYLOAD);
+	bgzf_stored_block(in + at, len, out + b * (BGZF_PAYLOAD + BGZF_EXTRA), tab, reg, x_pow, tid);
+}
+
+#define DFL_STRIDE 65312      // a block's place in the staging buffer: BGZF_PAYLOAD + BGZF_EXTRA up to a multiple of 16
+#define DFL_MAX_GRID 512      // resident workgroups (two per CU: 71 KB of LDS each); the token scratch is sized by them, not by the blocks
+static_assert(DFL_STRIDE % 16 == 0 && DFL_STRIDE >= BGZF_PAYLOAD + BGZF_EXTRA && BGZF_LANES == DFL_SEGS && BGZF_LANES == DFL_ROUND, "a thread is a CRC lane, a segment and a position of a round");
+
+// in: n bytes in n_blocks payloads, readable for 8 more; scratch: BGZF_PAYLOAD words per workgroup of the grid; stage: n_blocks * DFL_STRIDE
+// bytes, block b at b * DFL_STRIDE; size[b]: its bytes
+__global__ __launch_bounds__(BGZF_LANES, 2) void k_bgzf_deflate(const char *in, int64_t n, int64_t n_blocks, uint32_t *scratch, char *stage, int64_t *size)
+{
+	__shared__ __attribute__((aligned(16))) uint32_t buf[DFL_BUF_WORDS];   // the hash table; from the emission on the block
+	__shared__ DflWork W;
+	__shared__ uint32_t tab[256], reg[BGZF_LANES], x_pow[8];
+	const uint32_t tid = threadIdx.x;
+	tab[tid] = crc32_tab_entry(tid);
+	if (tid < 8) x_pow[tid] = crc32_x2n(11 + (int)tid);
+	uint32_t *scr = scratch + (size_t)blockIdx.x * BGZF_PAYLOAD;
+	for (int64_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+		const int64_t at = b * BGZF_PAYLOAD;
+		const uint32_t len = (uint32_t)(n - at < BGZF_PAYLOAD? n - at : BGZF_PAYLOAD);
+		const unsigned char *src = (const unsigned char*)in + at;
+		char *o = stage + b * DFL_STRIDE;
+		for (uint32_t i = tid; i < DFL_BUF_WORDS; i += BGZF_LANES) buf[i] = 0;
+		for (uint32_t i = tid; i < sizeof(DflWork) / 4; i += BGZF_LANES) ((uint32_t*)&W)[i] = 0;
+		__syncthreads();
+		// candidates: the hashes of eight rounds are loaded ahead (they need no table), then a round is two LDS steps between barriers
+		const uint32_t rounds = (len + DFL_ROUND - 1) / DFL_ROUND;
+		for (uint32_t r0 = 0; r0 < rounds; r0 += 8) {
+			uint32_t h1[8];
+			for (uint32_t k = 0; k < 8; ++k) h1[k] = dfl_hash1(src, len, (r0 + k) * DFL_ROUND + tid);
+			for (uint32_t k = 0; k < 8 && r0 + k < rounds; ++k) {
+				const uint32_t p = (r0 + k) * DFL_ROUND + tid;
+				dfl_round_read(p, len, h1[k], buf, scr);
+				__syncthreads();
+				dfl_round_raise(p, h1[k], buf);
+				__syncthreads();
+			}
+		}
+		W.n_tok[tid] = dfl_parse(src, len, tid, scr, W.ll_f, W.d_f);
+		if (tid == 0) W.ll_f[DFL_EOB] = 1;
+		__syncthreads();
+		for (int s = (int)tid; s < DFL_N_LL; s += BGZF_LANES) dfl_rank(W.ll_f, DFL_N_LL, s, W.ll_sorted);
+		if (tid < DFL_N_D) dfl_rank(W.d_f, DFL_N_D, (int)tid, W.d_sorted);
+		__syncthreads();
+		if (tid == 0) dfl_build(W);
+		__syncthreads();
+		// the segments' bits, their inclusive scan, and from it every segment's first bit in the stream
+		const uint32_t mine = dfl_seg_bits(W, tid, scr);
+		W.seg_bits[tid] = mine;
+		__syncthreads();
+		for (uint32_t d = 1; d < DFL_SEGS; d <<= 1) {
+			const uint32_t v = tid >= d? W.seg_bits[tid - d] : 0u;
+			__syncthreads();
+			W.seg_bits[tid] += v;
+			__syncthreads();
+		}
+		const uint32_t incl = W.seg_bits[tid], token_bits = W.seg_bits[DFL_SEGS - 1];
+		__syncthreads();
+		W.seg_bits[tid] = W.head_bits + incl - mine;
+		if (tid == 0) W.n_bytes = dfl_stream_bytes(W, token_bits);
+		__syncthreads();
+		if (W.n_bytes >= len + 5) {                            // (the whole workgroup)
+			bgzf_stored_block((const char*)src, len, o, tab, reg, x_pow, (int)tid);
+			if (tid == 0) size[b] = (int64_t)len + BGZF_EXTRA;
+		} else {
+			for (uint32_t i = tid; i < DFL_BUF_WORDS; i += BGZF_LANES) buf[i] = 0;
+			__syncthreads();
+			if (tid == 0) dfl_emit_head(W, buf);
+			dfl_emit_seg(W, tid, scr, buf);
+			const uint32_t crc = bgzf_block_crc((const char*)src, len, tab, reg, x_pow, (int)tid);
+			if (tid == 0) dfl_emit_tail(W, W.head_bits + token_bits, crc, len, buf);
+			__syncthreads();
+			const uint32_t total = DFL_GZ_HEAD + W.n_bytes + 8;    // (o is 16-byte aligned: whole pieces, then the last one's bytes)
+			for (uint32_t i = 16 * tid; i < total; i += 16 * BGZF_LANES) {
+				if (i + 16 <= total) *(uint4*)(o + i) = *(const uint4*)(buf + i / 4);
+				else for (uint32_t j = i; j < total; ++j) o[j] = (char)(buf[j >> 2] >> 8 * (j & 3));
+			}
+			if (tid == 0) size[b] = total;
+		}
+		__syncthreads();
 	}
+}
+
+// block b, size[b] bytes at stage + b * DFL_STRIDE (readable for 8 more), to out + off[b]; one workgroup per block
+__global__ __launch_bounds__(BGZF_LANES) void k_bgzf_compact(const char *stage, const int64_t *size, const int64_t *off, char *out)
+{
+	const int64_t b = blockIdx.x;
+	bgzf_copy(stage + b * DFL_STRIDE, out + off[b], (uint32_t)size[b], threadIdx.x);
 }
 
 // ------------------------------------------------------------------ host side
@@ -148,6 +256,59 @@ static int bam_frame_device(mm355_ctx *c, int64_t n, char *to, bool timed, doubl
 	if (timed) { float ms = 0; (void)hipEventElapsedTime(&ms, c->ev0, c->ev1); *k_us = (double)ms * 1e3; }
 	return 0;
 }
+
+// deflates the n bytes at c->rec_text.p (readable for 8 more) into c->bam_out: *n_out bytes of blocks, which the caller copies; timed: the two
+// kernels and the scan between the context's two events, microseconds in *k_us, and the count of blocks that were written stored
+static int bam_deflate_device(mm355_ctx *c, int64_t n, int64_t *n_out, bool timed, double *k_us, int64_t *n_stored)
+{
+	hipStream_t st = c->st;
+	*n_out = 0; *n_stored = 0;
+	if (n == 0) return 0;
+	const int64_t nb = bgzf_blocks(n);
+	if (nb > (int64_t)INT32_MAX) return MM355_EINVAL;
+	const unsigned grid = (unsigned)(nb < DFL_MAX_GRID? nb : DFL_MAX_GRID);
+	size_t tb = 0;
+	(void)rocprim::exclusive_scan(nullptr, tb, (int64_t*)0, (int64_t*)0, (int64_t)0, (size_t)nb + 1, rocprim::plus<int64_t>(), st);
+	const size_t w1 = up256((size_t)(nb + 1) * 8), w_size = 0, w_off = w1, w_tmp = 2 * w1, w_scr = w_tmp + up256(tb + 256);
+	if (c->bam_work.ensure(w_scr + (size_t)grid * BGZF_PAYLOAD * 4) || c->bam_stage.ensure((size_t)nb * DFL_STRIDE + 64) || c->bam_out.ensure((size_t)bgzf_size(n) + 64) ||
+	    c->h_rec_out.ensure(64, 1 << 20)) return MM355_ENOMEM;
+	char *dw = (char*)c->bam_work.p;
+	int64_t *d_size = (int64_t*)(dw + w_size), *d_off = (int64_t*)(dw + w_off);
+	HIPCHK(hipMemsetAsync(d_size + nb, 0, 8, st));
+	if (timed) (void)hipEventRecord(c->ev0, st);
+	hipLaunchKernelGGL(k_bgzf_deflate, dim3(grid), dim3(BGZF_LANES), 0, st, (const char*)c->rec_text.p, n, nb, (uint32_t*)(dw + w_scr), (char*)c->bam_stage.p, d_size);
+	HIPCHK(hipGetLastError());
+	HIPCHK(rocprim::exclusive_scan(dw + w_tmp, tb, d_size, d_off, (int64_t)0, (size_t)nb + 1, rocprim::plus<int64_t>(), st));
+	hipLaunchKernelGGL(k_bgzf_compact, dim3((unsigned)nb), dim3(BGZF_LANES), 0, st, (const char*)c->bam_stage.p, d_size, d_off, (char*)c->bam_out.p);
+	HIPCHK(hipGetLastError());
+	if (timed) (void)hipEventRecord(c->ev1, st);
+	int64_t *h_tot = (int64_t*)c->h_rec_out.p;
+	HIPCHK(hipMemcpyAsync(h_tot, d_off + nb, 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(mm355_wait_stream(st));
+	if (h_tot[0] < nb * (DFL_GZ_HEAD + 8) || h_tot[0] > bgzf_size(n)) return MM355_EHIP;   // (no block is longer than its stored form)
+	*n_out = h_tot[0];
+	if (timed) {
+		float ms = 0; (void)hipEventElapsedTime(&ms, c->ev0, c->ev1); *k_us = (double)ms * 1e3;
+		std::vector<int64_t> hs((size_t)nb);
+		HIPCHK(hipMemcpy(hs.data(), d_size, (size_t)nb * 8, hipMemcpyDeviceToHost));
+		for (int64_t b = 0; b < nb; ++b) *n_stored += hs[b] == (n - b * BGZF_PAYLOAD < BGZF_PAYLOAD? n - b * BGZF_PAYLOAD : BGZF_PAYLOAD) + BGZF_EXTRA;
+	}
+	return 0;
+}
+// the n_out bytes of blocks in c->bam_out to the host
+static int bam_blocks_back(mm355_ctx *c, int64_t n_out, char *to)
+{
+	if (n_out) HIPCHK(hipMemcpyAsync(to, c->bam_out.p, (size_t)n_out, hipMemcpyDeviceToHost, c->st));
+	HIPCHK(mm355_wait_stream(c->st));
+	return 0;
+}
+// MM355_BAM_TIMES=1: the line of a deflate call
+static void bam_deflate_times(const char *who, int64_t n, int64_t n_out, int64_t n_stored, double k_us, bool device)
+{
+	fprintf(stderr, "[mm355] bgzf_deflate_times %s %s blocks %lld bytes_in %lld bytes_out %lld stored_blocks %lld k_bgzf_deflate_compact_us %.1f\n", who, device? "device" : "host",
+	        (long long)bgzf_blocks(n), (long long)n, (long long)n_out, (long long)n_stored, k_us);
+}
+static bool bam_times_on() { const char *te = getenv("MM355_BAM_TIMES"); return te && *te && *te != '0'; }
 
 // BamFmt as the device writes it
 struct BamDevFmt : BamFmt {
@@ -180,13 +341,17 @@ struct BamDevFmt : BamFmt {
 	}
 	static int finish(mm355_ctx *c, RecCall &k, const int64_t *d_lo, mm355_text_t **out)
 	{
-		mm355_text_t *T = mm355_text_alloc(k.n_reads, k.n_lines, bgzf_size(k.n_text));
+		double k_us = 0, d_us = 0;
+		int64_t n_out = bgzf_size(k.n_text), n_stored = 0;
+		if (c->bgzf_level)
+			if (int rc = bam_deflate_device(c, k.n_text, &n_out, k.times, &d_us, &n_stored)) return rc;
+		mm355_text_t *T = mm355_text_alloc(k.n_reads, k.n_lines, n_out);
 		if (T == 0) return MM355_ENOMEM;
-		double k_us = 0;
 		hipError_t e = hipMemcpyAsync(T->line_off, d_lo, (size_t)(k.n_reads + 1) * 8, hipMemcpyDeviceToHost, c->st);
-		int rc = e == hipSuccess? bam_frame_device(c, k.n_text, T->text, k.times, &k_us) : MM355_EHIP;
+		int rc = e != hipSuccess? MM355_EHIP : c->bgzf_level? bam_blocks_back(c, n_out, T->text) : bam_frame_device(c, k.n_text, T->text, k.times, &k_us);
 		if (rc) { fprintf(stderr, "[mm355] error %d in the BAM writer (%s)\n", rc, hipGetErrorString(e)); mm355_free_text_host(T); return rc; }
-		if (k.times)
+		if (k.times && c->bgzf_level) bam_deflate_times("records", k.n_text, n_out, n_stored, d_us, true);
+		else if (k.times)
 			fprintf(stderr, "[mm355] bam_times records %lld stream_bytes %lld blocks %lld tiles %lld pack_ms %.3f k_bgzf_frame_us %.1f total_ms %.3f\n", (long long)k.n_lines,
 			        (long long)k.n_text, (long long)bgzf_blocks(k.n_text), (long long)k.n_tiles, k.t_packed - k.t_begin, k_us, mm355_now_ms() - k.t_begin);
 		*out = T;
@@ -200,49 +365,90 @@ struct BamDevFmt : BamFmt {
 // earlier than for SAM.  MM355_BAM_MIN_HITS=<n> overrides (read per call: the tests switch it).
 #define MM355_BAM_MIN_HITS_DEFAULT 24
 
-extern "C" int mm355_bam_format(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs,
-                                const int32_t *qlens, const char *const *quals, const int32_t *rep_len, int sam_flags, int where, mm355_text_t **out)
+// the host formatter at level 1: BamFmt with the deflating frame
+struct BamDeflateFmt : BamFmt {
+	static int64_t frame_host(const char *raw, int64_t n, char *out) { return mm355_bgzf_deflate_host(raw, n, out); }
+};
+
+extern "C" int mm355_bam_format_deflate(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs,
+                                        const int32_t *qlens, const char *const *quals, const int32_t *rep_len, int sam_flags, int where, int level, mm355_text_t **out)
 {
 	if (out == 0) return MM355_EINVAL;
 	*out = 0;
-	if (c == 0 || mo == 0 || H == 0 || where < MM355_PAF_AUTO || where > MM355_PAF_DEVICE) return MM355_EINVAL;
+	if (c == 0 || mo == 0 || H == 0 || where < MM355_PAF_AUTO || where > MM355_PAF_DEVICE || level < 0 || level > 1) return MM355_EINVAL;
 	if (c->mi == 0) return MM355_ENOIDX;
 	if (int rc = mm355_bam_check(H, c->mi->n_seq, (mo->flag & MMF_CIGAR) != 0, qnames, seqs, qlens, rep_len, sam_flags)) return rc;
 	const PafNames nm = { c->mi->names.data(), c->mi->n_seq };
+	c->bgzf_level = level;
 	return rec_format_where(where, H->n_hits, "MM355_BAM_MIN_HITS", MM355_BAM_MIN_HITS_DEFAULT,
-	                        [&] { return mm355_bam_format_host(H, qnames, seqs, qlens, quals, rep_len, nm, sam_flags, out); },
+	                        [&] { return level? mm355_rec_format_host<BamDeflateFmt>(H, qnames, seqs, qlens, quals, rep_len, nm, sam_flags, out)
+	                                          : mm355_bam_format_host(H, qnames, seqs, qlens, quals, rep_len, nm, sam_flags, out); },
 	                        [&] { return rec_format_device<BamDevFmt>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out); }, out);
+}
+
+extern "C" int mm355_bam_format(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs,
+                                const int32_t *qlens, const char *const *quals, const int32_t *rep_len, int sam_flags, int where, mm355_text_t **out)
+{
+	return mm355_bam_format_deflate(c, mo, H, qnames, seqs, qlens, quals, rep_len, sam_flags, where, 0, out);
+}
+
+static int mm355_bam_format_1(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens,
+                              const char *const *quals, const int32_t *rep_len, int sam_flags, int where, mm355_text_t **out)
+{
+	return mm355_bam_format_deflate(c, mo, H, qnames, seqs, qlens, quals, rep_len, sam_flags, where, 1, out);
+}
+
+extern "C" int mm355_map_batch_bam_deflate(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
+                                           const char *const *names, const char *const *quals, int flags, int sam_flags, int where, int level, mm355_text_t **out)
+{
+	if (out == 0) return MM355_EINVAL;
+	*out = 0;
+	if (level < 0 || level > 1) return MM355_EINVAL;           // (before anything is mapped)
+	return rec_map_batch(level? mm355_bam_format_1 : mm355_bam_format, c, mo, n_reads, seqs, lens, names, quals, flags, sam_flags, where, out);
 }
 
 extern "C" int mm355_map_batch_bam(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
                                    const char *const *names, const char *const *quals, int flags, int sam_flags, int where, mm355_text_t **out)
 {
-	return rec_map_batch(mm355_bam_format, c, mo, n_reads, seqs, lens, names, quals, flags, sam_flags, where, out);
+	return mm355_map_batch_bam_deflate(c, mo, n_reads, seqs, lens, names, quals, flags, sam_flags, where, 0, out);
 }
 
-extern "C" int mm355_bgzf_wrap(mm355_ctx_t *c, const void *data, int64_t n, int where, mm355_text_t **out)
+extern "C" int mm355_bgzf_deflate(mm355_ctx_t *c, const void *data, int64_t n, int where, int level, mm355_text_t **out)
 {
 	if (out == 0) return MM355_EINVAL;
 	*out = 0;
-	if (n < 0 || (n > 0 && data == 0) || where < MM355_PAF_AUTO || where > MM355_PAF_DEVICE || (where == MM355_PAF_DEVICE && c == 0)) return MM355_EINVAL;
+	if (n < 0 || (n > 0 && data == 0) || where < MM355_PAF_AUTO || where > MM355_PAF_DEVICE || (where == MM355_PAF_DEVICE && c == 0) || level < 0 || level > 1) return MM355_EINVAL;
 	const double t0 = mm355_now_ms();
+	const bool times = level && bam_times_on();
+	int64_t n_out = bgzf_size(n), n_stored = 0;
+	double k_us = 0;
 	// AUTO: the host.  The bytes are the caller's, in host memory: the device would frame them between an upload and a copy back that each
 	// move as much as the host's crc32 reads
 	if (where != MM355_PAF_DEVICE) {
-		if (int rc = mm355_bgzf_wrap_host(data, n, out)) return rc;
+		if (int rc = mm355_bgzf_wrap_host(data, n, out)) return rc;               // (stored blocks: the largest a level-1 result can be)
+		if (level) {
+			std::vector<char> z((size_t)n_out + 1);
+			n_out = mm355_bgzf_deflate_host((const char*)data, n, z.data(), &n_stored);
+			memcpy((*out)->text, z.data(), (size_t)n_out);
+			(*out)->n_text = n_out; (*out)->text[n_out] = 0;
+		}
 	} else {
 		HIPCHK(hipSetDevice(c->dev));
 		if (c->rec_text.ensure((size_t)n + 64)) return MM355_ENOMEM;
-		mm355_text_t *T = mm355_text_alloc(0, bgzf_blocks(n), bgzf_size(n));
+		if (n) HIPCHK(hipMemcpyAsync(c->rec_text.p, data, (size_t)n, hipMemcpyHostToDevice, c->st));
+		if (level)
+			if (int rc = bam_deflate_device(c, n, &n_out, times, &k_us, &n_stored)) return rc;
+		mm355_text_t *T = mm355_text_alloc(0, bgzf_blocks(n), n_out);
 		if (T == 0) return MM355_ENOMEM;
 		T->line_off[0] = 0;
-		double k_us = 0;
-		hipError_t e = n? hipMemcpyAsync(c->rec_text.p, data, (size_t)n, hipMemcpyHostToDevice, c->st) : hipSuccess;
-		const int rc = e == hipSuccess? bam_frame_device(c, n, T->text, false, &k_us) : MM355_EHIP;
+		const int rc = level? bam_blocks_back(c, n_out, T->text) : bam_frame_device(c, n, T->text, false, &k_us);
 		if (rc) { mm355_free_text_host(T); return rc; }
 		*out = T;
 	}
+	if (times) bam_deflate_times("wrap", n, n_out, n_stored, k_us, where == MM355_PAF_DEVICE);
 	(*out)->on_device = where == MM355_PAF_DEVICE;
 	(*out)->ms_format = mm355_now_ms() - t0;
 	return 0;
 }
+
+extern "C" int mm355_bgzf_wrap(mm355_ctx_t *c, const void *data, int64_t n, int where, mm355_text_t **out) { return mm355_bgzf_deflate(c, data, n, where, 0, out); }

@@ -234,7 +234,7 @@ template <typename F> inline int mm355_rec_format_host(const mm355_hits_t *H, co
 			if (ws.n != off[l + 1] - off[l]) { mm355_free_text_host(T); return MM355_EINVAL; }   // the two passes disagree: a bug, never a short record
 		}
 	}
-	if constexpr (F::FRAMED) F::frame_host(raw.data(), tot, T->text);
+	if constexpr (F::FRAMED) { T->n_text = F::frame_host(raw.data(), tot, T->text); T->text[T->n_text] = 0; }   // (a deflating frame writes less than out_size(tot))
 	*out = T;
 	return 0;
 }

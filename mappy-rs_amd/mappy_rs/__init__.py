@@ -389,11 +389,15 @@ def sam_lines(ms, name, seq, qual=None, *, softclip=False, rl=None):
 BAM_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 
 
-def bgzf_wrap(data):
-    """`data` (bytes) in stored BGZF blocks of at most 0xff00 bytes of payload each (mm355_bgzf_wrap on the host); b"" gives b"" """
+def bgzf_wrap(data, *, compress=False):
+    """`data` (bytes) in stored BGZF blocks of at most 0xff00 bytes of payload each (mm355_bgzf_wrap on the host); b"" gives b"".
+    compress=True: every block deflated where that is shorter (mm355_bgzf_deflate at level 1, on the host)"""
     L = _ffi.lib()
     tp = C.POINTER(_ffi.Text)()
-    _ffi.check(L.mm355_bgzf_wrap(None, data, len(data), _ffi.PAF_HOST, C.byref(tp)))
+    if compress:
+        _ffi.check(L.mm355_bgzf_deflate(None, data, len(data), _ffi.PAF_HOST, 1, C.byref(tp)))
+    else:
+        _ffi.check(L.mm355_bgzf_wrap(None, data, len(data), _ffi.PAF_HOST, C.byref(tp)))
     try:
         return bytes(_ffi.text_view(tp))
     finally:
@@ -1004,31 +1008,38 @@ class Aligner:
             L.mm355_free_text(tp)
 
     # ---- BAM records (mm355_map_batch_bam): the BAM encoding of map_sam's lines in stored BGZF blocks, formed by the library
-    def map_bam(self, seqs, names=None, quals=None, cs=False, MD=False, *, softclip=False, hit_only=False, where=_ffi.PAF_AUTO):
+    def map_bam(self, seqs, names=None, quals=None, cs=False, MD=False, *, softclip=False, hit_only=False, where=_ffi.PAF_AUTO, compress=False):
         """the BAM records of `seqs` as bytes: whole BGZF blocks (stored, not compressed) without the header (bam_header()) and without the
         EOF block (BAM_EOF), in input order; one mm355_map_batch_bam call.  A record is the BAM encoding of the line map_sam writes for the
         same arguments (include/mm355.h states it field by field); the results of consecutive calls, one behind the other, continue the
-        stream.  Besides what map_sam refuses: a read name of more than 254 bytes (RuntimeError).  Arguments and `paf_on_device` as for map_sam."""
+        stream.  Besides what map_sam refuses: a read name of more than 254 bytes (RuntimeError).  Arguments and `paf_on_device` as for map_sam.
+        compress=True: the blocks deflated (mm355_map_batch_bam_deflate at level 1; on the device by a kernel, a workgroup per block): the same
+        records behind gzip.decompress, blocks of their real size."""
+        if compress:
+            L = self._L
+            return self._map_records(lambda *a: L.mm355_map_batch_bam_deflate(*a[:-1], 1, a[-1]), seqs, names, quals, cs, MD, softclip, hit_only, where)
         return self._map_records(self._L.mm355_map_batch_bam, seqs, names, quals, cs, MD, softclip, hit_only, where)
 
-    def bam_header(self):
-        """the BAM header of this index as BGZF blocks: the magic, sam_header() as the text, the contigs with their lengths"""
+    def bam_header(self, compress=False):
+        """the BAM header of this index as BGZF blocks (compress=True: deflated): the magic, sam_header() as the text, the contigs with their lengths"""
         text, L = self.sam_header(), self._L
         refs = []
         for i, nm in enumerate(self._names()):
             b = nm.encode()
             refs.append(struct.pack("<I", len(b) + 1) + b + b"\0" + struct.pack("<I", L.mm355_index_seq_len(self._idx, i)))
-        return bgzf_wrap(b"BAM\1" + struct.pack("<I", len(text)) + text + struct.pack("<I", len(refs)) + b"".join(refs))
+        return bgzf_wrap(b"BAM\1" + struct.pack("<I", len(text)) + text + struct.pack("<I", len(refs)) + b"".join(refs), compress=bool(compress))
 
     def map_bam_file(self, reads_path, out_path, cs=False, MD=False, n_threads=None, sub_batch_reads=SUB_BATCH_READS, *, where=_ffi.PAF_AUTO,
-                     softclip=False, hit_only=False):
+                     softclip=False, hit_only=False, compress=False):
         """maps a FASTA / FASTQ file of reads to an uncompressed BAM file (what `samtools view -u` writes; ready for `samtools sort` /
         `index` without a SAM parse): bam_header(), the records of map_bam per sub-batch in input order, BAM_EOF.  The reader, the workers,
         the bound on memory, the ".part" file and its rename, what a failure leaves behind and the returned dict are map_file's; n_lines
         counts records.  A record takes about 1.5 bytes per base with qualities (a SAM line 2) and as much from a FASTA (0xFF per base where
-        SAM prints one `*`): the gain is the consumer's, which parses nothing."""
+        SAM prints one `*`): the gain is the consumer's, which parses nothing.
+        compress=True: a compressed BAM file (what `samtools view -b` writes): bam_header(compress=True), the records of
+        map_bam(compress=True) per sub-batch, BAM_EOF; the returned dict also has n_bytes_out, the size of the file."""
         sam_flags = (_ffi.SAM_SOFTCLIP if softclip else 0) | (_ffi.SAM_HIT_ONLY if hit_only else 0)
-        return self._map_file("bam", reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags)
+        return self._map_file("bam", reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags, compress=bool(compress))
 
     def map_file(self, reads_path, out_path, cs=False, MD=False, n_threads=None, sub_batch_reads=SUB_BATCH_READS, *, where=_ffi.PAF_AUTO, format="paf"):
         """maps a FASTA / FASTQ file of reads (plain or gzip) to a PAF file, lines in input order -- minimap2's command line from a read set to
@@ -1048,11 +1059,11 @@ class Aligner:
             raise ValueError("`format` must be \"paf\" or \"sam\"")
         return self._map_file(format, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, 0)
 
-    def _map_file(self, kind, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags):
+    def _map_file(self, kind, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags, compress=False):
         """map_file (kind "paf" / "sam") and map_bam_file ("bam"): reader thread, workers, ordered writer, .part file"""
         sam = kind != "paf"                               # the reader keeps qualities, the call takes them and sam_flags
         flags = self._sam_flags(cs, MD) if sam else self._paf_flags(cs, MD)
-        header = self.sam_header() if kind == "sam" else self.bam_header() if kind == "bam" else b""
+        header = self.sam_header() if kind == "sam" else self.bam_header(compress) if kind == "bam" else b""
         trailer = BAM_EOF if kind == "bam" else b""
         L = self._L
         nt = self._n_threads if n_threads is None else int(n_threads)
@@ -1080,6 +1091,9 @@ class Aligner:
         mo, where = self._mo, int(where)
         acquire, release = self._ctx_acquire, self._ctx_release
         map_records = L.mm355_map_batch_bam if kind == "bam" else L.mm355_map_batch_sam
+        if compress:
+            def map_records(*a):
+                return L.mm355_map_batch_bam_deflate(*a[:-1], 1, a[-1])
 
         def fail(e):
             errors.append(e)
@@ -1150,6 +1164,7 @@ class Aligner:
                     cv.notify_all()
 
         n_lines = n_dev = nxt = 0
+        n_out = len(header) + len(trailer)
         ms_format = 0.0
         rd = None
         try:
@@ -1166,7 +1181,7 @@ class Aligner:
                     tp = done.pop(nxt)
                 try:
                     t = tp.contents
-                    n_lines += int(t.n_lines); n_dev += int(t.on_device); ms_format += float(t.ms_format)
+                    n_lines += int(t.n_lines); n_dev += int(t.on_device); ms_format += float(t.ms_format); n_out += int(t.n_text)
                     out.write(_ffi.text_view(tp))
                 finally:
                     L.mm355_free_text(tp)
@@ -1197,8 +1212,11 @@ class Aligner:
             for tp in done.values():
                 L.mm355_free_text(tp)
             L.mm355_fastx_close(fx)
-        return {"n_reads": st["n_reads"], "n_bases": st["n_bases"], "n_lines": n_lines, "n_sub_batches": st["n_sub"],
-                "seconds": time.perf_counter() - t0, "ms_format": ms_format, "n_on_device": n_dev}
+        res = {"n_reads": st["n_reads"], "n_bases": st["n_bases"], "n_lines": n_lines, "n_sub_batches": st["n_sub"],
+               "seconds": time.perf_counter() - t0, "ms_format": ms_format, "n_on_device": n_dev}
+        if compress:
+            res["n_bytes_out"] = n_out
+        return res
 
     def _stage_runner(self):
         """per-stage access to the same kernels (parity tests, kernel bench)"""

@@ -121,6 +121,7 @@ EXPORTS = [
     "mm355_paf_format", "mm355_map_batch_paf", "mm355_free_text", "mm355_fastx_open", "mm355_fastx_next", "mm355_reads_free", "mm355_fastx_close",
     "mm355_sam_format", "mm355_map_batch_sam", "mm355_fastx_open_qual", "mm355_reads_quals",
     "mm355_bam_format", "mm355_map_batch_bam", "mm355_bgzf_wrap",
+    "mm355_bam_format_deflate", "mm355_map_batch_bam_deflate", "mm355_bgzf_deflate",
 ]
 
 _LIB = None
@@ -173,6 +174,10 @@ def lib():
     L.mm355_bam_format.argtypes = L.mm355_sam_format.argtypes        # the SAM calls' arguments; the text is BGZF blocks of BAM records
     L.mm355_map_batch_bam.argtypes = L.mm355_map_batch_sam.argtypes
     L.mm355_bgzf_wrap.argtypes = [vp, C.c_char_p, C.c_int64, C.c_int, C.POINTER(C.POINTER(Text))]
+    # the three with `level` in front of the result: 0 stored blocks, 1 deflate
+    L.mm355_bam_format_deflate.argtypes = L.mm355_sam_format.argtypes[:-1] + [C.c_int, C.POINTER(C.POINTER(Text))]
+    L.mm355_map_batch_bam_deflate.argtypes = L.mm355_map_batch_sam.argtypes[:-1] + [C.c_int, C.POINTER(C.POINTER(Text))]
+    L.mm355_bgzf_deflate.argtypes = [vp, C.c_char_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.POINTER(Text))]
     L.mm355_fastx_open_qual.argtypes = [C.c_char_p, C.POINTER(vp)]
     L.mm355_reads_quals.argtypes = [C.POINTER(Reads)]
     L.mm355_reads_quals.restype = C.POINTER(C.c_char_p)
