@@ -319,6 +319,24 @@ int mm355_map_batch_bam_deflate(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int6
                                 const char *const *names, const char *const *quals, int flags, int sam_flags, int where, int level, mm355_text_t **out);
 int mm355_bgzf_deflate(mm355_ctx_t *ctx, const void *data, int64_t n, int where, int level, mm355_text_t **out);
 
+/* --- BGZF input: the inverse of mm355_bgzf_deflate.  `data` is n bytes of BGZF members (what mm355_bgzf_wrap / _deflate, bgzip or any BAM
+ * writer produced): gzip members with the BC extra subfield (other subfields may stand in front of it; MTIME, XFL and OS are ignored), cdata of
+ * at most 64 KB holding any RFC 1951 stream -- several deflate blocks, stored, fixed and dynamic ones, run symbols 16 - 18, codes of 15 bits,
+ * a single one-bit distance code or none, distances up to 32768, ISIZE 0 (the EOF block) to 65536.  The host walks the members by BSIZE
+ * (mm355_bgzfwalk.h), which gives every payload its place; the members are inflated by the decoder of mm355_inflate.h, one after the other
+ * on the host (ctx may be NULL) or a workgroup per member on the device (mm355_inflate.hip: k_bgzf_inflate; an upload, the kernel, a copy
+ * back).  `where`: MM355_PAF_HOST, MM355_PAF_DEVICE, or MM355_PAF_AUTO, which is the host here as for mm355_bgzf_wrap.  `text` is the
+ * payloads back to back, n_lines the number of members (the empty EOF member counts), n_reads 0; n == 0 gives zero bytes.
+ * The input is untrusted: the decoder reads and writes inside the spans the walk gave and refuses a member for BTYPE 11, stored LEN != ~NLEN,
+ * an over-subscribed code, an incomplete one (but a single code of one bit, and a distance set without any code), a missing end-of-block
+ * code, a run symbol without a previous length or past HLIT + HDIST, literal/length symbols 286 / 287 and distance symbols 30 / 31, a
+ * distance before the payload's first byte, output beyond or short of ISIZE, input that ends inside a symbol, and a CRC-32 that is not the
+ * trailer's -- what zlib's inflate refuses.  Bytes between the last deflate block and the trailer are ignored.
+ * MM355_EINVAL: the data's first bytes are no BGZF member (plain gzip, text).  MM355_EIO: a later member is malformed, the data ends inside a
+ * member, or a member was refused.  Nothing is returned then.  A missing EOF member is no error.
+ * MM355_INFLATE_TIMES=1: a device call prints a line on stderr (members, bytes in and out, the kernel's time between two events). */
+int mm355_bgzf_inflate(mm355_ctx_t *ctx, const void *data, int64_t n, int where, mm355_text_t **out);
+
 /* --- streaming FASTA / FASTQ reader, plain or gzip: the record rules of the index builder's parser (the name ends at the first blank,
  * multi-line sequences, a '+' line followed by quality as long as the sequence, CRLF).  A read set is cut into sub-batches without ever
  * being in memory as a whole.  mm355_fastx_next returns the next records: at least one, at most max_reads, and no record that would take
@@ -336,6 +354,20 @@ void mm355_reads_free(mm355_reads_t *r);
 int mm355_fastx_open_qual(const char *path, mm355_fastx_t **out);
 const char *const *mm355_reads_quals(const mm355_reads_t *r);
 void mm355_fastx_close(mm355_fastx_t *fx);
+/* BAM as a reads file: when the (inflated) stream begins "BAM\1", mm355_fastx_next reads BAM records instead of text, whichever open made the
+ * handle -- unaligned BAM as basecallers write it, or an aligned one.  The header is skipped; a record with flag & 0x900 (secondary,
+ * supplementary) is skipped as `samtools fastq` skips it; the name is read_name, the bases come from the nibbles ("=ACMGRSVTWYHKDBN"), the
+ * quality is qual + 33 (first byte 0xff: none); a record with flag 0x10 is reverse-complemented and its quality reversed, back to the read
+ * as sequenced.  Aux tags are dropped.  MM355_EIO: block_size below 32, l_read_name 0, name + CIGAR + SEQ + QUAL beyond block_size, or a
+ * stream that ends inside the header or a record.  The index builders do not read BAM: a BAM is no reference.
+ * mm355_fastx_open_device: the same reader over a BGZF file (bgzip FASTQ / FASTA, BAM) whose members GPU `device` inflates
+ * (k_bgzf_inflate).  The file is read in pieces of 32 MB of compressed bytes (MM355_INFLATE_PIECE=<bytes> overrides it; a piece always
+ * holds at least one whole member) into two pinned buffers; upload, kernel and the copy of the inflated bytes back run on a stream the
+ * handle owns while the next piece is read and walked; the record loop on the host cuts the bytes.  keep_qual != 0: as mm355_fastx_open_qual.
+ * MM355_EINVAL: the file's first bytes are no BGZF member (plain text, plain gzip) -- nothing is opened and no device is touched: open it with
+ * mm355_fastx_open.  MM355_EIO: unreadable.  MM355_ENODEV / ENOMEM / EHIP.  A malformed or refused member surfaces as MM355_EIO from
+ * mm355_fastx_next when the reader gets there.  MM355_INFLATE_TIMES=1: a line per piece on stderr. */
+int mm355_fastx_open_device(const char *path, int keep_qual, int device, mm355_fastx_t **out);
 
 /* --- per-stage entry points (same kernels as mm355_map_batch; used by the parity tests and
  * by bench.py to time one kernel with HIP events).  Outputs are caller-allocated host buffers. --- */

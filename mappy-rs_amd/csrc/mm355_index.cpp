@@ -16,6 +16,7 @@
 #include <zlib.h>
 #include "mm355_host.h"
 #include "mm355_mmiwalk.h"
+#include "mm355_bamread.h"
 
 #define mm_seq4_set(s, i, c) ((s)[(i)>>3] |= (uint32_t)(c) << (((i)&7)<<2))
 #define mm_seq4_get(s, i)    ((s)[(i)>>3] >> (((i)&7)<<2) & 0xf)
@@ -278,9 +279,26 @@ static mm355_index *build_from_seqs(const mm355_idxopt_t *io, int n_seq, const c
 }
 
 // FASTA/FASTQ, plain or gzip-compressed (U:bseq.c reads through zlib's gzFile, which passes plain files through unchanged).  One record
-// loop serves the index builders (parse_fastx: the whole file) and the streaming reader of read sets (mm355_fastx_next).
+// loop serves the index builders (parse_fastx: the whole file) and the streaming reader of read sets (mm355_fastx_next).  The bytes come
+// through a ByteSource (mm355_bamread.h): zlib here, or the device inflater's stream (mm355_inflate.hip: mm355_fastx_open_device).
+struct GzSource : ByteSource {
+	gzFile gz;
+	explicit GzSource(gzFile g) : gz(g) { (void)gzbuffer(gz, 1 << 20); }
+	~GzSource() { gzclose(gz); }
+	int64_t read(void *buf, size_t cap)
+	{
+		const int r = gzread(gz, buf, (unsigned)cap);
+		if (r > 0) return r;
+		int zerr = 0; (void)gzerror(gz, &zerr);
+		return r < 0 || (zerr != Z_OK && zerr != Z_STREAM_END)? MM355_EIO : 0;   // truncated / corrupt gzip stream
+	}
+};
+
 struct mm355_fastx {
-	gzFile gz = 0;
+	ByteSource *src = 0;
+	int io_err = 0;                       // the source's error: the stream ended there
+	// mm355_fastx_next only: the stream's first four bytes have been looked at; "BAM\1": the BAM loop of mm355_bamread.h reads it (header_done: its header is behind)
+	bool sniffed = false, is_bam = false, header_done = false;
 	std::string line, next_name;          // line: a line that straddles two blocks; next_name: the header line that ended the previous record
 	std::vector<char> buf = std::vector<char>(1 << 20);   // the file is read in blocks and cut into lines here (gzgets costs a call and a strlen per line)
 	size_t pos = 0, end = 0;
@@ -290,8 +308,19 @@ struct mm355_fastx {
 	std::string held_name, held_seq; bool held = false; int err = 0;
 	// mm355_fastx_open_qual: the quality of the record fastx_record has just returned (has_qual: a FASTQ record with a '+' line), and the held record's
 	bool keep_qual = false, has_qual = false, held_has_qual = false; std::string qual, held_qual;
-	~mm355_fastx() { if (gz) gzclose(gz); }
+	~mm355_fastx() { delete src; }
 };
+
+// the next block of the stream into the (used up) buffer; false at the end, or at the source's error
+static bool fastx_refill(mm355_fastx *fx)
+{
+	fx->pos = fx->end = 0;
+	int64_t r = fx->eof? 0 : fx->src->read(fx->buf.data(), fx->buf.size());
+	if (r < 0) { fx->io_err = (int)r; r = 0; }
+	if (r == 0) { fx->eof = true; return false; }
+	fx->end = (size_t)r;
+	return true;
+}
 
 // the next line of any length, without its line end (LF or CRLF): *p / *n point into the block, or into fx->line when the line straddles blocks.
 // false at the end of the file (a last line without a newline is returned first)
@@ -309,15 +338,11 @@ static bool fastx_line(mm355_fastx *fx, const char **p, size_t *n)
 		}
 		if (!joined) { fx->line.clear(); joined = true; }
 		fx->line.append(beg, fx->end - fx->pos);
-		fx->pos = fx->end = 0;
-		const int r = fx->eof? 0 : gzread(fx->gz, fx->buf.data(), (unsigned)fx->buf.size());
-		if (r <= 0) {
-			fx->eof = true;
+		if (!fastx_refill(fx)) {
 			if (fx->line.empty()) return false;
 			*p = fx->line.data(); *n = fx->line.size();
 			break;
 		}
-		fx->end = (size_t)r;
 	}
 	while (*n > 0 && ((*p)[*n - 1] == '\n' || (*p)[*n - 1] == '\r')) --*n;
 	return true;
@@ -349,17 +374,55 @@ static int fastx_record(mm355_fastx *fx, std::string &name, std::string &seq)
 			else for (size_t i = 0; i < n; ++i) if (line[i] > ' ') seq.push_back(line[i]);
 		}
 	}
-	int zerr = 0; (void)gzerror(fx->gz, &zerr);
-	if (zerr != Z_OK && zerr != Z_STREAM_END) return MM355_EIO;   // truncated / corrupt gzip stream: no garbage index, no half a read set
+	if (fx->io_err) return MM355_EIO;   // truncated / corrupt stream: no garbage index, no half a read set
 	return have? 1 : 0;
+}
+
+// the stream as the BAM loop takes it: n bytes to dst (0: skipped), fewer at the end
+struct FastxTake {
+	mm355_fastx *fx;
+	int64_t take(void *dst, size_t n)
+	{
+		size_t got = 0;
+		while (got < n) {
+			if (fx->pos == fx->end && !fastx_refill(fx)) break;
+			const size_t k = std::min(n - got, fx->end - fx->pos);
+			if (dst) memcpy((char*)dst + got, fx->buf.data() + fx->pos, k);
+			fx->pos += k; got += k;
+		}
+		return (int64_t)got;
+	}
+	int err() const { return fx->io_err; }
+};
+
+// fastx_record for the streaming reader: a stream that begins "BAM\1" gives its records as reads (fx->qual, fx->has_qual: the record's quality)
+static int reads_record(mm355_fastx *fx, std::string &name, std::string &seq)
+{
+	if (!fx->sniffed) {
+		fx->sniffed = true;
+		while (fx->end < 4 && !fx->eof) {                        // (the buffer is empty: nothing has been read)
+			int64_t r = fx->src->read(fx->buf.data() + fx->end, fx->buf.size() - fx->end);
+			if (r < 0) { fx->io_err = (int)r; r = 0; }
+			if (r == 0) fx->eof = true;
+			fx->end += (size_t)r;
+		}
+		fx->is_bam = fx->end >= 4 && memcmp(fx->buf.data(), "BAM\1", 4) == 0;
+	}
+	if (!fx->is_bam) return fastx_record(fx, name, seq);
+	FastxTake t = { fx };
+	if (!fx->header_done) {
+		if (bam_read_header(t)) return MM355_EIO;
+		fx->header_done = true;
+	}
+	return bam_read_record(t, name, seq, fx->qual, &fx->has_qual);
 }
 
 static bool parse_fastx(const char *path, std::vector<std::string> &names, std::vector<std::string> &seqs)
 {
 	mm355_fastx fx;
-	fx.gz = gzopen(path, "rb");
-	if (fx.gz == 0) return false;
-	(void)gzbuffer(fx.gz, 1 << 20);
+	gzFile gz = gzopen(path, "rb");
+	if (gz == 0) return false;
+	fx.src = new GzSource(gz);
 	std::string name, seq;
 	int rc;
 	while ((rc = fastx_record(&fx, name, seq)) == 1) { names.push_back(name); seqs.emplace_back(); seqs.back().swap(seq); }
@@ -370,12 +433,17 @@ extern "C" int mm355_fastx_open(const char *path, mm355_fastx_t **out)
 {
 	*out = 0;
 	if (path == 0) return MM355_EINVAL;
-	mm355_fastx *fx = new mm355_fastx();
-	fx->gz = gzopen(path, "rb");
-	if (fx->gz == 0) { delete fx; return MM355_EIO; }
-	(void)gzbuffer(fx->gz, 1 << 20);
-	*out = fx;
+	gzFile gz = gzopen(path, "rb");
+	if (gz == 0) return MM355_EIO;
+	*out = mm355_fastx_from_source(new GzSource(gz), false);
 	return 0;
+}
+
+mm355_fastx *mm355_fastx_from_source(ByteSource *src, bool keep_qual)
+{
+	mm355_fastx *fx = new mm355_fastx();
+	fx->src = src; fx->keep_qual = keep_qual;
+	return fx;
 }
 
 extern "C" int mm355_fastx_open_qual(const char *path, mm355_fastx_t **out)
@@ -412,7 +480,7 @@ extern "C" int mm355_fastx_next(mm355_fastx_t *fx, int64_t max_reads, int64_t ma
 		const size_t at = B->seq_bytes.size();
 		if (fx->held) { name.swap(fx->held_name); B->seq_bytes += fx->held_seq; fx->held_seq.clear(); fx->held = false; qual.swap(fx->held_qual); has_qual = fx->held_has_qual; }
 		else {
-			const int rc = fastx_record(fx, name, B->seq_bytes);      // (the bases land behind the sub-batch's other reads)
+			const int rc = reads_record(fx, name, B->seq_bytes);      // (the bases land behind the sub-batch's other reads)
 			if (rc == 0) break;
 			if (rc < 0) { fx->err = rc; break; }
 			if (B->seq_bytes.size() - at >= (size_t)1 << 31) { fx->err = MM355_EINVAL; break; }

@@ -28,7 +28,7 @@ import numpy as np
 
 from . import _ffi
 
-__all__ = ["Aligner", "Mapping", "paf_line", "sam_lines", "shard_by_bases", "order_by_length"]
+__all__ = ["Aligner", "Mapping", "paf_line", "sam_lines", "shard_by_bases", "order_by_length", "bgzf_unwrap"]
 
 _CIGAR_OPS = "MIDNSHP=X"
 
@@ -398,6 +398,19 @@ def bgzf_wrap(data, *, compress=False):
         _ffi.check(L.mm355_bgzf_deflate(None, data, len(data), _ffi.PAF_HOST, 1, C.byref(tp)))
     else:
         _ffi.check(L.mm355_bgzf_wrap(None, data, len(data), _ffi.PAF_HOST, C.byref(tp)))
+    try:
+        return bytes(_ffi.text_view(tp))
+    finally:
+        L.mm355_free_text(tp)
+
+
+def bgzf_unwrap(data):
+    """the host inverse of bgzf_wrap: the payloads of the BGZF members of `data` (bytes), back to back (mm355_bgzf_inflate on the host);
+    b"" gives b"".  Data that does not begin with a BGZF member, a malformed member and one the decoder refuses (a corrupt deflate stream,
+    a CRC-32 or ISIZE that is not the trailer's) raise"""
+    L = _ffi.lib()
+    tp = C.POINTER(_ffi.Text)()
+    _ffi.check(L.mm355_bgzf_inflate(None, data, len(data), _ffi.PAF_HOST, C.byref(tp)))
     try:
         return bytes(_ffi.text_view(tp))
     finally:
@@ -1030,18 +1043,21 @@ class Aligner:
         return bgzf_wrap(b"BAM\1" + struct.pack("<I", len(text)) + text + struct.pack("<I", len(refs)) + b"".join(refs), compress=bool(compress))
 
     def map_bam_file(self, reads_path, out_path, cs=False, MD=False, n_threads=None, sub_batch_reads=SUB_BATCH_READS, *, where=_ffi.PAF_AUTO,
-                     softclip=False, hit_only=False, compress=False):
+                     softclip=False, hit_only=False, compress=False, read_on_gpu=False):
         """maps a FASTA / FASTQ file of reads to an uncompressed BAM file (what `samtools view -u` writes; ready for `samtools sort` /
         `index` without a SAM parse): bam_header(), the records of map_bam per sub-batch in input order, BAM_EOF.  The reader, the workers,
         the bound on memory, the ".part" file and its rename, what a failure leaves behind and the returned dict are map_file's; n_lines
         counts records.  A record takes about 1.5 bytes per base with qualities (a SAM line 2) and as much from a FASTA (0xFF per base where
         SAM prints one `*`): the gain is the consumer's, which parses nothing.
         compress=True: a compressed BAM file (what `samtools view -b` writes): bam_header(compress=True), the records of
-        map_bam(compress=True) per sub-batch, BAM_EOF; the returned dict also has n_bytes_out, the size of the file."""
+        map_bam(compress=True) per sub-batch, BAM_EOF; the returned dict also has n_bytes_out, the size of the file.
+        read_on_gpu, and a BAM as the reads file: as for map_file."""
         sam_flags = (_ffi.SAM_SOFTCLIP if softclip else 0) | (_ffi.SAM_HIT_ONLY if hit_only else 0)
-        return self._map_file("bam", reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags, compress=bool(compress))
+        return self._map_file("bam", reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags, compress=bool(compress),
+                              read_on_gpu=bool(read_on_gpu))
 
-    def map_file(self, reads_path, out_path, cs=False, MD=False, n_threads=None, sub_batch_reads=SUB_BATCH_READS, *, where=_ffi.PAF_AUTO, format="paf"):
+    def map_file(self, reads_path, out_path, cs=False, MD=False, n_threads=None, sub_batch_reads=SUB_BATCH_READS, *, where=_ffi.PAF_AUTO, format="paf",
+                 read_on_gpu=False):
         """maps a FASTA / FASTQ file of reads (plain or gzip) to a PAF file, lines in input order -- minimap2's command line from a read set to
         its overlaps or alignments.  A reader thread cuts sub-batches of `sub_batch_reads` reads (and at most SUB_BATCH_BASES bases) with the
         library's streaming reader; up to min(n_threads, 8) workers per GPU (n_threads=None: enable_threading's value, or 1), each with a
@@ -1054,12 +1070,17 @@ class Aligner:
         format (keyword-only): "paf", or "sam": the header of sam_header(), then the lines of map_sam (mm355_map_batch_sam; the reader keeps
         FASTQ qualities, a FASTA read prints `*`; reads without hits write their unmapped record).  A SAM sub-batch's text is about 2.2 x its
         bases (a PAF one's a few hundred bytes per hit), and 2 x workers of them exist at a time.  Any other value: ValueError, before a
-        file is opened."""
+        file is opened.
+        The reads file may also be a BAM (unaligned, as basecallers write it, or aligned): its records are the reads -- secondary and
+        supplementary ones skipped, reverse-strand ones turned back, aux tags dropped (include/mm355.h).
+        read_on_gpu (keyword-only): True opens the reads with mm355_fastx_open_device on the aligner's first device -- a BGZF file (bgzip
+        FASTQ / FASTA, or a BAM) is inflated there, a workgroup per block, and only cut into records on the host.  Any other file (plain
+        text, plain gzip) is opened as without the keyword.  The returned dict then has reader_on_device (bool): which of the two happened."""
         if format not in ("paf", "sam"):
             raise ValueError("`format` must be \"paf\" or \"sam\"")
-        return self._map_file(format, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, 0)
+        return self._map_file(format, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, 0, read_on_gpu=bool(read_on_gpu))
 
-    def _map_file(self, kind, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags, compress=False):
+    def _map_file(self, kind, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags, compress=False, read_on_gpu=False):
         """map_file (kind "paf" / "sam") and map_bam_file ("bam"): reader thread, workers, ordered writer, .part file"""
         sam = kind != "paf"                               # the reader keeps qualities, the call takes them and sam_flags
         flags = self._sam_flags(cs, MD) if sam else self._paf_flags(cs, MD)
@@ -1073,7 +1094,12 @@ class Aligner:
             raise ValueError("`sub_batch_reads` must be at least 1")
         t0 = time.perf_counter()
         fx = C.c_void_p()
-        rc = (L.mm355_fastx_open_qual if sam else L.mm355_fastx_open)(os.fsencode(reads_path), C.byref(fx))
+        rc = _ffi.MM355_EINVAL
+        if read_on_gpu:
+            rc = L.mm355_fastx_open_device(os.fsencode(reads_path), 1 if sam else 0, self._devices[0], C.byref(fx))
+        reader_on_device = rc == 0
+        if rc == _ffi.MM355_EINVAL:               # not asked for, or not a BGZF file: the host reader
+            rc = (L.mm355_fastx_open_qual if sam else L.mm355_fastx_open)(os.fsencode(reads_path), C.byref(fx))
         if rc != 0:
             raise RuntimeError("%s: %s" % (reads_path, L.mm355_strerror(rc).decode()))
         part = os.fspath(out_path) + (b".part" if isinstance(os.fspath(out_path), bytes) else ".part")
@@ -1216,6 +1242,8 @@ class Aligner:
                "seconds": time.perf_counter() - t0, "ms_format": ms_format, "n_on_device": n_dev}
         if compress:
             res["n_bytes_out"] = n_out
+        if read_on_gpu:
+            res["reader_on_device"] = reader_on_device
         return res
 
     def _stage_runner(self):

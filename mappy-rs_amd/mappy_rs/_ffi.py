@@ -122,6 +122,7 @@ EXPORTS = [
     "mm355_sam_format", "mm355_map_batch_sam", "mm355_fastx_open_qual", "mm355_reads_quals",
     "mm355_bam_format", "mm355_map_batch_bam", "mm355_bgzf_wrap",
     "mm355_bam_format_deflate", "mm355_map_batch_bam_deflate", "mm355_bgzf_deflate",
+    "mm355_bgzf_inflate", "mm355_fastx_open_device",
 ]
 
 _LIB = None
@@ -178,6 +179,8 @@ def lib():
     L.mm355_bam_format_deflate.argtypes = L.mm355_sam_format.argtypes[:-1] + [C.c_int, C.POINTER(C.POINTER(Text))]
     L.mm355_map_batch_bam_deflate.argtypes = L.mm355_map_batch_sam.argtypes[:-1] + [C.c_int, C.POINTER(C.POINTER(Text))]
     L.mm355_bgzf_deflate.argtypes = [vp, C.c_char_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.POINTER(Text))]
+    L.mm355_bgzf_inflate.argtypes = [vp, C.c_char_p, C.c_int64, C.c_int, C.POINTER(C.POINTER(Text))]
+    L.mm355_fastx_open_device.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(vp)]
     L.mm355_fastx_open_qual.argtypes = [C.c_char_p, C.POINTER(vp)]
     L.mm355_reads_quals.argtypes = [C.POINTER(Reads)]
     L.mm355_reads_quals.restype = C.POINTER(C.c_char_p)
