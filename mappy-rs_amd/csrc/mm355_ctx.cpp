@@ -112,7 +112,7 @@ void mm355_streams::release()
 	if (!dp_shared) drop_streams(dp_st, 16);
 	hipEvent_t *one[] = { &dp_up_ev, &aux_ev, &aux_ev2, &ev0, &ev1 };
 	for (hipEvent_t *e : one) if (*e) { (void)hipEventDestroy(*e); *e = 0; }
-	for (hipEvent_t *set : { dp_ev, dp_ev0, dp_ev1 }) for (int i = 0; i < 24; ++i) if (set[i]) { (void)hipEventDestroy(set[i]); set[i] = 0; }
+	for (hipEvent_t *set : { dp_ev, dp_ev0, dp_ev1 }) for (int i = 0; i < MM355_DP_GROUPS; ++i) if (set[i]) { (void)hipEventDestroy(set[i]); set[i] = 0; }
 	if (pool_slot < 0) { drop_streams(&aux_st, 1); drop_streams(&st, 1); }
 	else { std::lock_guard<std::mutex> lk(g_streams_mu); g_pools[dev].used &= (uint8_t)~(1u << pool_slot); }   // (the streams stay with the device's pool)
 	for (hipStream_t &s : dp_st) s = 0;

@@ -3,13 +3,7 @@
 #include <stdint.h>
 #include <vector>
 #include "mm355_pipeline.h"
-
-struct DpConst {            // scoring constants after ksw_extd2_sse's (q,e)/(q2,e2) ordering
-	int32_t q, e, q2, e2, qe_preswap;
-	int8_t sc_mch, sc_mis, sc_N;
-	int32_t long_thres, long_diff, valid;
-	int32_t int8_ok;         // no int8 lane of ksw_extd2_sse wraps on a cell of the matrix (mm355_dpdomain.h): the row / band kernels' premise
-};
+#include "mm355_dpplan.h"   // DpConst, mm355_dp_const, the plan of one problem
 
 struct DpJobDev {
 	int32_t qlen, tlen;
@@ -29,7 +23,6 @@ struct DpGather {           // where the code strings of a job come from
 	int32_t rev, pad;
 };
 
-DpConst mm355_dp_const(const mm355_mapopt_t *mo);
 size_t mm355_dp_matrix_bytes(const mm355_mapopt_t *mo, const DpConst &dc, int qlen, int tlen, int w, int flag);   // direction-matrix bytes mm355_dp_run will lay out for one problem
 int mm355_dp_run(mm355_ctx *c, const mm355_mapopt_t *mo, DpJobDev *jobs, size_t n, const uint8_t *d_q, const uint8_t *d_t, HBuf *arena,
                  const mm355_dpres_t **res_out, const uint32_t **cigar_out);   // results live in pinned host buffers (c->h_res, *arena)

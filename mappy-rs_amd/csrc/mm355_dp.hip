@@ -25,12 +25,6 @@
 
 #define WAVE 64
 #define KSW_NEG_INF (-0x40000000)
-#define EZ_SCORE_ONLY  0x01
-#define EZ_RIGHT       0x02
-#define EZ_APPROX_MAX  0x08
-#define EZ_APPROX_DROP 0x10
-#define EZ_EXTZ_ONLY   0x40
-#define EZ_REV_CIGAR   0x80
 
 struct EzState { int32_t max, max_q, max_t, mqe, mqe_t, mte, mte_q, score, zdropped, reach_end; };
 
@@ -431,223 +425,179 @@ __global__ __launch_bounds__(256) void k_read_codes(DevBatch bt, uint8_t *rq)
 }
 
 // ------------------------------------------------------------------ host driver
-DpConst mm355_dp_const(const mm355_mapopt_t *mo)
+// The plan of a problem -- its launch group and everything laid out for it -- is mm355_dpplan.h; its switches come from the environment, once
+// per process
+static const DpKnobs &dp_knobs()
 {
-	DpConst c;
-	int q = mo->q, e = mo->e, q2 = mo->q2, e2 = mo->e2, t;
-	int a = mo->a < 0? -mo->a : mo->a, b = mo->b > 0? -mo->b : mo->b, amb = mo->sc_ambi > 0? -mo->sc_ambi : mo->sc_ambi;
-	c.qe_preswap = (int8_t)q + (int8_t)e;
-	if (q2 + e2 < q + e) t = q, q = q2, q2 = t, t = e, e = e2, e2 = t;
-	c.q = q; c.e = e; c.q2 = q2; c.e2 = e2;
-	c.sc_mch = (int8_t)a; c.sc_mis = (int8_t)b; c.sc_N = amb == 0? (int8_t)(-e2) : (int8_t)amb;
-	c.long_thres = e != e2? (q2 - q) / (e - e2) - 1 : 0;
-	if (q2 + e2 + c.long_thres * e2 > q + e + c.long_thres * e) ++c.long_thres;
-	c.long_diff = c.long_thres * (e - e2) - (q2 - q) - e2;
-	int min_sc = b < amb? b : amb;
-	c.valid = !(-min_sc > 2 * (q + e));
-	c.int8_ok = mm355_dp_int8_domain(mo->a, mo->b, mo->sc_ambi, mo->q, mo->e, mo->q2, mo->e2);
-	return c;
+	static const DpKnobs kn = [] {
+		auto on = [](const char *name) { const char *e = getenv(name); return !(e && atoi(e) == 0); };
+		DpKnobs k;
+		k.use_row = on("MM355_DP_ROW"); k.use_rowl = on("MM355_DP_ROWL"); k.use_regw = on("MM355_DP_REGW"); k.regw8 = on("MM355_DP_REGW8");
+		k.use_band = on("MM355_DP_BAND");
+		if (const char *e = getenv("MM355_DP_BAND_THR")) k.band_thr = atof(e);
+		if (const char *e = getenv("MM355_DP_BAND_THR_HALF")) k.band_thr_half = atof(e);
+		if (const char *e = getenv("MM355_DP_BAND_FORCE")) k.band_force = atoi(e);
+		return k;
+	}();
+	return kn;
 }
 
-// Size classes.  Targets up to 1024 bases run register-resident (k_ksw_reg, 2 * NP cells per lane), split by score
-// tracking mode (KSW_EZ_APPROX_MAX or exact); longer ones keep their per-target state in LDS (12 B per position) or, beyond
-// 12288 positions, in HBM, with eight waves per alignment.  MM355_DP_LEGACY=1 routes everything through the LDS kernel.
-struct DpClass { int cap, kind, np; };   // kind 0: k_ksw_reg, 1: k_ksw_extd2<64> (LDS), 2: k_ksw_extd2<512>
-static const DpClass DP_CLASSES[] = { {128, 0, 1}, {256, 0, 2}, {512, 0, 4}, {1024, 0, 8}, {4096, 2, 0}, {12288, 2, 0}, {0, 2, 0} };
-static const DpClass DP_CLASSES_LEGACY[] = { {256, 1, 0}, {512, 1, 0}, {1024, 1, 0}, {1024, 1, 0}, {4096, 2, 0}, {12288, 2, 0}, {0, 2, 0} };
-#define DP_N_CLASS 7
-#define DP_N_GROUP 23                    // group = class * 2 + exact for the seven classes; 14 / 15 / 16 = k_ksw_row<2> / <4> / <8> (full-band approximate fills), 17 = k_ksw_rowl (the same, targets 1025..8192)
-#define DP_G_ROW2 14
-#define DP_G_ROW4 15
-#define DP_G_ROW8 16
-#define DP_G_ROWL 17
-#define DP_G_BAND1 19                   // k_ksw_band<1 | 2 | 4>: the row sweep on a band of 128 / 256 / 512 diagonals with a sufficiency proof (mm355_dpband.h)
-#define DP_G_BAND2 20
-#define DP_G_BAND4 21
-#define DP_G_BANDH 22                   // k_ksw_band2: two problems per wave, 64 diagonals each
-#define DP_G_REDO 23                    // (not a class: the second, full-matrix run of band problems whose proof failed -- timer / counter slot)
-#define DP_G_REGW 18                    // k_ksw_regw: exact, narrow band (w <= DP_WIN_MAX_W), targets > 1024 -- the register kernel with a moving window
-
-// value range of the row sweep on a qlen x tlen problem (int16 halves; ROW_NEG must stay below every real value, differences of two real
-// values and the shifted prefix terms G + t e must not wrap)
-static bool rowl_range_ok(const DpConst &dc, int qlen, int tlen)
+// bytes of direction matrix mm355_dp_run lays out for one extension problem (the caller cuts a round so that a launch fits its HBM budget)
+size_t mm355_dp_matrix_bytes(const mm355_mapopt_t *mo, const DpConst &dc, int qlen, int tlen, int w_in, int flag)
 {
-	const int tl = (tlen + 127) & ~127;       // the lanes beyond the target compute cells of a wider matrix
-	auto cost = [&](int k) { const int c1 = dc.q + k * dc.e, c2 = dc.q2 + k * dc.e2; return c1 < c2? c1 : c2; };
-	const int emax = dc.e > dc.e2? dc.e : dc.e2;
-	const int hi = dc.sc_mch * (qlen < tl? qlen : tl);
-	int step = dc.q + dc.e > dc.q2 + dc.e2? dc.q + dc.e : dc.q2 + dc.e2;
-	if (-dc.sc_mis > step) step = -dc.sc_mis;
-	if (-dc.sc_N > step) step = -dc.sc_N;
-	const int lo = cost(qlen + 1) + cost(tl + 1) + step + emax + 64;
-	return hi + emax * (tl + 1) <= 32000 && lo <= -ROW_NEG - 64 && hi + lo <= 32000;
-}
-
-template <int NP>
-static void launch_reg(bool exact, unsigned n, hipStream_t st, const DpConst &dc, const DpJobDev *jobs, const int32_t *ids, const uint8_t *d_q, const uint8_t *d_t,
-                       uint8_t *bt, mm355_dpres_t *res, unsigned long long *cells)
-{
-	// MM355_DP_LDS_PAD: bytes of (unused) LDS requested per wave, a cap on the extension waves per CU (160 KB / pad) that keeps wave slots
-	// free for the latency-bound front kernels of the other contexts
-	static const size_t pad = [] { const char *e = getenv("MM355_DP_LDS_PAD"); return (size_t)(e? atoi(e) : 0); }();
-	if (exact) hipLaunchKernelGGL((k_ksw_reg<NP, true>), dim3(n), dim3(64), pad, st, dc, jobs, ids, (int)n, d_q, d_t, bt, res, cells);
-	else hipLaunchKernelGGL((k_ksw_reg<NP, false>), dim3(n), dim3(64), pad, st, dc, jobs, ids, (int)n, d_q, d_t, bt, res, cells);
-}
-
-
-// which full-matrix row-sweep kernel takes a problem: 0 none (the anti-diagonal kernels), 1 k_ksw_row, 2 k_ksw_rowl -- ONE definition for the
-// launch layout (mm355_dp_run) and for the HBM budget of a round (mm355_dp_matrix_bytes)
-static int row_class(const DpConst &dc, int qlen, int tlen, int w_in, int flag)
-{
-	static const bool legacy = [] { const char *e = getenv("MM355_DP_LEGACY"); return e && atoi(e) != 0; }();
-	static const bool use_row = [] { const char *e = getenv("MM355_DP_ROW"); return !legacy && !(e && atoi(e) == 0); }();   // MM355_DP_ROW=0: anti-diagonal kernels only
-	static const bool use_rowl = [] { const char *e = getenv("MM355_DP_ROWL"); return !(e && atoi(e) == 0); }();                           // MM355_DP_ROWL=0: no eight-wave row sweep
-	const int w = w_in < 0? std::max(qlen, tlen) : w_in;
-	// ... only for a regular two-piece cost (after ksw2's ordering: e > e2, or two identical pieces).  Otherwise the boundary row and
-	// column of U:ksw2_extd2_sse.c follow the dearer piece (long_thres <= 1), H(t,q) - H(t-1,q-1) can exceed the match score next to
-	// them, the kernel's clamp `z = min(z, sc_mch)` becomes active and the result is no longer the plain recurrence the row sweep
-	// computes (found by the option fuzzer: scoring=(4,10,3,3,12,3)); those options keep the literal anti-diagonal kernels.
-	const bool regular = dc.e > dc.e2 || (dc.e == dc.e2 && dc.q == dc.q2);
-	// ... and only inside the int8 domain of the SSE kernel (mm355_dpdomain.h): beyond it, e.g. a gap sum (q + e) + (q2 + e2) above 128
-	// or a + q + 2e above 128, its lanes wrap on true cells and its result is no longer the plain recurrence either
-	const bool row_kind = dc.valid && dc.int8_ok && use_row && regular &&(flag & EZ_APPROX_MAX) && !(flag & (EZ_APPROX_DROP | EZ_EXTZ_ONLY | EZ_SCORE_ONLY)) && w >= qlen + tlen;
-	if (!row_kind) return 0;
-	// (the int16 value range is checked per problem: a user scoring such as e2 >= 7 or a large match score would wrap the packed halves)
-	if (tlen <= ROW_MAX_T) return qlen + tlen <= ROW_MAX_QT && rowl_range_ok(dc, qlen, tlen <= 256? 256 : tlen <= 512? 512 : 1024)? 1 : 0;
-	return use_rowl && tlen <= ROWL_MAX_T && qlen <= ROWL_MAX_Q && rowl_range_ok(dc, qlen, tlen)? 2 : 0;
+	return mm355_dp_plan_budget(mm355_dp_plan(dc, dp_knobs(), mo->max_sw_mat, qlen, tlen, w_in, flag));
 }
 
 __global__ void k_dp_patch(DpJobDev *jobs, const int32_t *ids, const DpJobDev *nj, int n) { const int i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) jobs[ids[i]] = nj[i]; }
 
-// ---- band kernels (mm355_dpband.h): which problems take them, with which band
-struct BandPlan { int nsb, dlo, lmin, bw; };   // nsb = 0: the full-matrix kernels; bw = 64 (two problems per wave, nsb = 1), 128, 256, 512
-static int band_ubound(const DpConst &dc, int qlen, int tlen, int d)   // no path through diagonal d (outside [min(0, D0), max(0, D0)]) scores more
+// ---- launch units.  A unit is ONE kernel launch over the launch lists of the groups [g0, g1) (the lists of a round are contiguous by group).
+// Everything a kernel of the round takes besides its own list:
+struct DpLaunchArgs {
+	DpConst dc; const DpJobDev *jobs; const uint8_t *d_q, *d_t; uint8_t *bt; mm355_dpres_t *res;
+	int32_t *d_off; uint32_t *cig; uint64_t *d_S; int32_t *d_H; uint32_t *dense; unsigned long long *d_dense;   // k_ksw_extd2 only
+	int32_t *d_fail;                 // band kernels: [0] = problems whose proof failed, then their ids
+	unsigned long long *d_gcells;    // cells per group [CTR_GROUPS][DP_CTR_SPREAD]
+	size_t regw_seq;                 // LDS bytes of the longest (query, target) pair of k_ksw_regw8 in this round
+	size_t n_band2_right;            // k_ksw_band2 pairs neighbours of its list and both share KSW_EZ_RIGHT: that many at the front of the list have it
+};
+// ids / n: the unit's launch list; cells: the counter slots of its first group
+typedef int (*DpLauncher)(const DpLaunchArgs &a, hipStream_t st, const int32_t *ids, unsigned n, unsigned long long *cells);
+
+typedef void (*DpKernel)(DpConst, const DpJobDev*, const int32_t*, int, const uint8_t*, const uint8_t*, uint8_t*, mm355_dpres_t*, unsigned long long*);
+template <DpKernel K, int NT = 64>     // one wave per problem, or NT threads
+static int launch(const DpLaunchArgs &a, hipStream_t st, const int32_t *ids, unsigned n, unsigned long long *cells)
 {
-	const int D0 = tlen - qlen, g1 = d < 0? -d : d, g2 = D0 - d < 0? d - D0 : D0 - d;
-	auto cost = [&](int g) { if (g <= 0) return 0; const int c1 = dc.q + g * dc.e, c2 = dc.q2 + g * dc.e2; return c1 < c2? c1 : c2; };
-	int a = dc.sc_mch; if (dc.sc_mis > a) a = dc.sc_mis; if (dc.sc_N > a) a = dc.sc_N; if (a < 0) a = 0;
-	int m = (qlen + tlen - g1 - g2) / 2; if (m < 0) m = 0;
-	return a * m - cost(g1) - cost(g2);
+	hipLaunchKernelGGL(K, dim3(n), dim3(NT), 0, st, a.dc, a.jobs, ids, (int)n, a.d_q, a.d_t, a.bt, a.res, cells);
+	return 0;
 }
-static BandPlan band_plan(const DpConst &dc, int qlen, int tlen, int full_sets)
+// The long-target classes: targets <= 4096 (49 KB of LDS state: three alignments per CU) and longer ones (147 KB: one per CU; state in HBM
+// beyond 12288 positions); approx and exact alignments share a launch, and the kernel adds its cells to the job's own group (`4`: the first
+// of these size classes).  A few dozen latency-bound alignments that must not queue behind one another.
+template <int CLS>
+static int launch_lds(const DpLaunchArgs &a, hipStream_t st, const int32_t *ids, unsigned n, unsigned long long *)
 {
-	BandPlan bp; bp.nsb = 0; bp.dlo = 0; bp.lmin = 0; bp.bw = 0;
-	static const bool use_band = [] { const char *e = getenv("MM355_DP_BAND"); return !(e && atoi(e) == 0); }();        // MM355_DP_BAND=0: full-matrix kernels only
-	static const double thr = [] { const char *e = getenv("MM355_DP_BAND_THR"); return e? atof(e) : 0.65; }();          // a band is tried when a score of thr x (all matches) would prove it
-	static const int force = [] { const char *e = getenv("MM355_DP_BAND_FORCE"); return e? atoi(e) : 0; }();            // test hook: this many register sets whenever the geometry allows
-	if (!use_band) return bp;
-	const int D0 = tlen - qlen, lo = D0 < 0? D0 : 0, hi = D0 > 0? D0 : 0, span = hi - lo + 1;
-	const int emax = dc.e > dc.e2? dc.e : dc.e2;
-	auto cost = [&](int g) { const int c1 = dc.q + g * dc.e, c2 = dc.q2 + g * dc.e2; return c1 < c2? c1 : c2; };
-	int a = dc.sc_mch > 0? dc.sc_mch : 0;
-	const int n = qlen < tlen? qlen : tlen;
-	static const double thr_half = [] { const char *e = getenv("MM355_DP_BAND_THR_HALF"); return e? atof(e) : 0.72; }();   // ... for the 64-diagonal band (0 = never)
-	for (int nsb = 0; nsb <= 4; nsb = nsb? nsb * 2 : 1) {   // nsb = 0: half a register set (64 diagonals, k_ksw_band2)
-		const int W = nsb? 128 * nsb : 64;
-		if (force && (nsb? nsb : 64) != force) continue;
-		if (nsb && nsb >= full_sets && !force) break;                   // no narrower than the full matrix
-		if (W < span + 2 * BAND_MIN_MARGIN) continue;
-		// int16 range: real values stay above -(cost(qlen + 1) + cost(tlen + 1)) - ..., the cells left of the border column start at ROW_NEG and
-		// drift by at most a per row for W rows; prefix terms G + d e with |d| <= W + span
-		if (cost(qlen + 1) + cost(tlen + 1) + 256 > 7000 || a * (W + 8) > 4000 || (W + span + 8) * emax > 4000 || a * n + (W + span + 8) * emax > 30000) continue;
-		const int dlo = lo - (W - span) / 2;
-		int u1 = band_ubound(dc, qlen, tlen, dlo - 1), u2 = band_ubound(dc, qlen, tlen, dlo + W);
-		const int lmin = (u1 > u2? u1 : u2) + 1;
-		if (!force && (double)lmin > (nsb? thr : thr_half) * (double)(a * n)) continue;   // not worth a try: only a nearly perfect alignment would prove this band
-		bp.nsb = nsb? nsb : 1; bp.dlo = dlo; bp.lmin = lmin; bp.bw = W;
-		return bp;
-	}
-	return bp;
+	const int cap = DP_CLASS_CAP[CLS];
+	// (per launch, not once per process: the attribute belongs to the function on the CURRENT device, and one process may drive several)
+	(void)hipFuncSetAttribute((const void*)k_ksw_extd2<512>, hipFuncAttributeMaxDynamicSharedMemorySize, DP_CLASS_CAP[DP_N_CLASS - 2] * 12);
+	hipLaunchKernelGGL(k_ksw_extd2<512>, dim3(n), dim3(512), (size_t)cap * 12, st, a.dc, a.jobs, ids, (int)n, a.d_q, a.d_t, a.bt, a.d_off, a.cig, a.d_S, a.d_H, a.res,
+	                   cap, a.d_gcells, a.dense, a.d_dense, 4);
+	return 0;
+}
+// the long narrow-band extensions: thousands of anti-diagonals each -- the longest latency chain of a round.  Eight waves per alignment
+// (mm355_dpmw.h), the sequences of a block in (dynamic) LDS; MM355_DP_REGW8=0: one wave each
+static int launch_regw(const DpLaunchArgs &a, hipStream_t st, const int32_t *ids, unsigned n, unsigned long long *cells)
+{
+	if (!dp_knobs().regw8) return launch<k_ksw_regw>(a, st, ids, n, cells);
+	if (a.regw_seq + 64 > 32768 && hipFuncSetAttribute((const void*)k_ksw_regw8, hipFuncAttributeMaxDynamicSharedMemorySize, MW_SEQ_MAX + 64) != hipSuccess) return MM355_EHIP;
+	hipLaunchKernelGGL(k_ksw_regw8, dim3(n), dim3(MW_THREADS), a.regw_seq + 64, st, a.dc, a.jobs, ids, (int)n, a.d_q, a.d_t, a.bt, a.res, cells);
+	return 0;
+}
+template <int NS>
+static int launch_band(const DpLaunchArgs &a, hipStream_t st, const int32_t *ids, unsigned n, unsigned long long *cells)
+{
+	hipLaunchKernelGGL(k_ksw_band<NS>, dim3(n), dim3(64), 0, st, a.dc, a.jobs, ids, (int)n, a.d_q, a.d_t, a.bt, a.res, cells, a.d_fail);
+	return 0;
+}
+static int launch_band2(const DpLaunchArgs &a, hipStream_t st, const int32_t *ids, unsigned n, unsigned long long *cells)
+{
+	const unsigned nr = (unsigned)a.n_band2_right, nl = n - nr;
+	if (nr) hipLaunchKernelGGL(k_ksw_band2, dim3((nr + 1) / 2), dim3(64), 0, st, a.dc, a.jobs, ids, (int)nr, a.d_q, a.d_t, a.bt, a.res, cells, a.d_fail);
+	if (nl) hipLaunchKernelGGL(k_ksw_band2, dim3((nl + 1) / 2), dim3(64), 0, st, a.dc, a.jobs, ids + nr, (int)nl, a.d_q, a.d_t, a.bt, a.res, cells, a.d_fail);
+	return 0;
+}
+
+// The launch units of a round, in launch order.  This table is the one place that says which stream a kernel runs on, whether it is part of
+// the turn, when the main stream joins it, and (g0) under which group its elapsed time is reported.
+// Streams (created back to back at context creation, so they sit on different hardware queues): 0 approx targets <= 256 (the wide grids),
+// 1 every exact register class, 2 approx 1024, 3 approx 512, 4 .. 7 the eight-wave kernels -- same-stream launches would serialise the classes.
+// Not part of the turn: the eight-wave kernels -- a few dozen latency-bound alignments that leave the GPU almost empty; started BEFORE the turn
+// is taken they run while this context waits for it, and they keep running while the next context's round starts.  Inside it, big problems
+// first; the main stream joins the wide grids (row sweep, bands, approximate register classes) at once, because the turn ends when they are
+// done, and the exact register classes (small latency-bound grids) after the turn, with the eight-wave kernels.
+struct DpUnit { int g0, g1; DpLauncher launch; int stream; bool in_turn, join_at_once; };
+static const DpUnit DP_UNITS[] = {
+	{ DP_G_LDS + 2, DP_G_ROW2,      launch_lds<5>,                       5, false, false },   // the longest sweeps first
+	{ DP_G_LDS,     DP_G_LDS + 2,   launch_lds<4>,                       4, false, false },
+	{ DP_G_REGW,    DP_G_REGW + 1,  launch_regw,                         7, false, false },
+	{ DP_G_ROWL,    DP_G_ROWL + 1,  launch<k_ksw_rowl, 64 * ROWL_WAVES>, 6, false, false },
+	{ DP_G_BANDH,   DP_G_BANDH + 1, launch_band2,                        0, true,  true  },
+	{ DP_G_BAND4,   DP_G_BAND4 + 1, launch_band<4>,                      2, true,  true  },
+	{ DP_G_BAND2,   DP_G_BAND2 + 1, launch_band<2>,                      3, true,  true  },
+	{ DP_G_BAND1,   DP_G_BAND1 + 1, launch_band<1>,                      0, true,  true  },
+	{ DP_G_ROW8,    DP_G_ROW8 + 1,  launch<k_ksw_row<8>>,                2, true,  true  },
+	{ DP_G_ROW4,    DP_G_ROW4 + 1,  launch<k_ksw_row<4>>,                3, true,  true  },
+	{ DP_G_ROW2,    DP_G_ROW2 + 1,  launch<k_ksw_row<2>>,                0, true,  true  },
+	{ DP_G_REG + 7, DP_G_REG + 8,   launch<k_ksw_reg<8, true>>,          1, true,  false },
+	{ DP_G_REG + 6, DP_G_REG + 7,   launch<k_ksw_reg<8, false>>,         2, true,  true  },
+	{ DP_G_REG + 5, DP_G_REG + 6,   launch<k_ksw_reg<4, true>>,          1, true,  false },
+	{ DP_G_REG + 4, DP_G_REG + 5,   launch<k_ksw_reg<4, false>>,         3, true,  true  },
+	{ DP_G_REG + 3, DP_G_REG + 4,   launch<k_ksw_reg<2, true>>,          1, true,  false },
+	{ DP_G_REG + 2, DP_G_REG + 3,   launch<k_ksw_reg<2, false>>,         0, true,  true  },
+	{ DP_G_REG + 1, DP_G_REG + 2,   launch<k_ksw_reg<1, true>>,          1, true,  false },
+	{ DP_G_REG + 0, DP_G_REG + 1,   launch<k_ksw_reg<1, false>>,         0, true,  true  },   // (skipped and empty problems ride in this list)
+};
+// the second, full-matrix run of band problems whose proof failed: by target length, longest rows first
+static const DpLauncher DP_REDO_LAUNCH[4] = { launch<k_ksw_row<8>>, launch<k_ksw_row<4>>, launch<k_ksw_row<2>>, launch<k_ksw_rowl, 64 * ROWL_WAVES> };
+static int dp_redo_class(const DpJobDev &j) { return j.tlen > ROW_MAX_T? 3 : j.tlen <= 256? 2 : j.tlen <= 512? 1 : 0; }
+static_assert(sizeof(((mm355_stats_t*)0)->ms_dp_group) == MM355_DP_GROUPS * sizeof(double) && CTR_GROUPS == MM355_DP_GROUPS, "per-group statistics");
+
+// One extension round saturates the GPU.  Rounds of different contexts take turns (per device): run side by side they would all
+// finish late together and the contexts would march in lock-step -- GPU idle while every host tail runs, hosts idle while every
+// round runs.  Taking turns lets the first finisher start its host tail while the next round has the whole GPU.
+struct Turn {   // counting semaphore: MM355_DP_TURNS rounds at a time per device (default 1, 0 = unlimited)
+	std::mutex m; std::condition_variable cv; int busy = 0;
+	void lock(int cap) { std::unique_lock<std::mutex> lk(m); cv.wait(lk, [&] { return busy < cap; }); ++busy; }
+	void unlock() { { std::lock_guard<std::mutex> lk(m); --busy; } cv.notify_one(); }
+};
+struct TurnGuard { Turn *t = 0; void lock(Turn *x, int cap) { x->lock(cap); t = x; } void unlock() { if (t) { t->unlock(); t = 0; } } ~TurnGuard() { unlock(); } };
+
+// a unit's stream starts after the uploads of the round; its launch sits between the two timer events of its first group
+static int group_begin(mm355_ctx *c, int g, hipStream_t gst)
+{
+	if (c->dp_ev[g] == 0) HIPCHK(hipEventCreateWithFlags(&c->dp_ev[g], hipEventDisableTiming));
+	HIPCHK(hipStreamWaitEvent(gst, c->dp_up_ev, 0));
+	if (c->dp_ev0[g] == 0) HIPCHK(hipEventCreate(&c->dp_ev0[g]));
+	if (c->dp_ev1[g] == 0) HIPCHK(hipEventCreate(&c->dp_ev1[g]));
+	HIPCHK(hipEventRecord(c->dp_ev0[g], gst));
+	return 0;
+}
+static int group_end(mm355_ctx *c, int g, hipStream_t gst, bool join)
+{
+	HIPCHK(hipEventRecord(c->dp_ev1[g], gst));
+	HIPCHK(hipEventRecord(c->dp_ev[g], gst));
+	if (join) HIPCHK(hipStreamWaitEvent(c->st, c->dp_ev[g], 0));
+	return 0;
 }
 
 // runs n jobs whose code strings are already on the device (d_q/d_t).  `jobs` is host memory that stays valid until the call
 // returns (pinned when it comes from the mapping path).  Results: res_out -> c->h_res (pinned, valid until the next call),
-// bytes of direction matrix mm355_dp_run lays out for one extension problem (the caller cuts a round so that a launch fits its HBM budget):
-// the row sweep's tiled matrix (mm355_dprow.h) for the full-band approximate fills it takes, the reference's anti-diagonal layout otherwise
-size_t mm355_dp_matrix_bytes(const mm355_mapopt_t *mo, const DpConst &dc, int qlen, int tlen, int w_in, int flag)
-{
-	if (qlen <= 0 || tlen <= 0) return 0;
-	if (mo->max_sw_mat > 0 && (int64_t)tlen * qlen > mo->max_sw_mat) return 0;
-	const int w = w_in < 0? std::max(qlen, tlen) : w_in;
-	int n_col_ = std::min(qlen, tlen);
-	n_col_ = ((n_col_ < w + 1? n_col_ : w + 1) + 15) / 16 + 1;
-	const int T = (tlen + 15) / 16 * 16;
-	const int rk = row_class(dc, qlen, tlen, w_in, flag);
-	const bool row = rk == 1, rowl = rk == 2;
-	if (row || rowl) {
-		const BandPlan bp = band_plan(dc, qlen, tlen, rowl? 64 : tlen <= 256? 2 : tlen <= 512? 4 : 8);
-		if (bp.nsb) return band_matrix_bytes(qlen, bp.bw) + 64;
-		return row_matrix_bytes(qlen, T) + 64;   // (+ the alignment of its first tile)
-	}
-	return ((size_t)(qlen + tlen - 1) * n_col_ + 1) * 16;
-}
-
 // cigar_out -> dense CIGAR arena in *arena (pinned, owned by the caller's batch).
 int mm355_dp_run(mm355_ctx *c, const mm355_mapopt_t *mo, DpJobDev *jobs, size_t n, const uint8_t *d_q, const uint8_t *d_t, HBuf *arena,
                  const mm355_dpres_t **res_out, const uint32_t **cigar_out)
 {
 	*res_out = 0; *cigar_out = 0;
 	if (n == 0) return 0;
-	DpConst dc = mm355_dp_const(mo);
-	static const bool legacy = [] { const char *e = getenv("MM355_DP_LEGACY"); return e && atoi(e) != 0; }();
-	static const bool use_regw = [] { const char *e = getenv("MM355_DP_REGW"); return !legacy && !(e && atoi(e) == 0); }();               // MM355_DP_REGW=0: no windowed register kernel
-	static const bool regw8 = [] { const char *e = getenv("MM355_DP_REGW8"); return !(e && atoi(e) == 0); }();                             // MM355_DP_REGW8=0: the single-wave kernel of round 2 (same results)
-	size_t regw_seq = 0;                       // LDS bytes of the longest (query, target) pair of the eight-wave kernel in this round
-	const DpClass *classes = legacy? DP_CLASSES_LEGACY : DP_CLASSES;
-	// lay out per-job work areas; group = size class * 2 + exact
-	size_t p_tot = 0, off_tot = 0, cig_tot = 0, st_tot = 0;
+	const DpConst dc = mm355_dp_const(mo);
+	const DpKnobs &kn = dp_knobs();
+	// ---- lay out the per-job work areas from the plan of each job
+	size_t p_tot = 0, cig_tot = 0, st_tot = 0, regw_seq = 0;
 	std::vector<uint8_t> grp(n);
 	size_t n_grp[DP_N_GROUP + 1] = {0};
 	const int LB = 1024;                       // backtrack order: buckets of (qlen + tlen) / 8, longest first (approximate is enough)
 	std::vector<uint32_t> lcnt(LB + 1, 0);
 	for (size_t i = 0; i < n; ++i) {
 		DpJobDev &j = jobs[i];
-		j.skip = (mo->max_sw_mat > 0 && (int64_t)j.tlen * j.qlen > mo->max_sw_mat) || !dc.valid;
-		int w = j.w < 0? std::max(j.qlen, j.tlen) : j.w;
-		int n_col_ = std::min(j.qlen, j.tlen);
-		n_col_ = ((n_col_ < w + 1? n_col_ : w + 1) + 15) / 16 + 1;
-		int T = (j.tlen + 15) / 16 * 16;
-		j.p_off = (int64_t)p_tot; j.off_off = (int64_t)off_tot; j.cig_off = (int64_t)cig_tot; j.st_off = 0;
-		int g = 0;
-		j.pad = 0; j.dlo = 0; j.lmin = 0; j.bw = 0; j.rsv = 0;
-		if (j.qlen > 0 && j.tlen > 0 && !j.skip) {
-			cig_tot += (size_t)j.qlen + j.tlen + 2;
-			// gap fills whose band never binds, without z-drop on the approximate score: the row sweep (mm355_dprow.h; row_class above)
-			const int rk = row_class(dc, j.qlen, j.tlen, j.w, j.flag);
-			const bool row = rk == 1, rowl = rk == 2;
-			if (row || rowl) {
-				const BandPlan bp = band_plan(dc, j.qlen, j.tlen, rowl? 64 : j.tlen <= 256? 2 : j.tlen <= 512? 4 : 8);
-				p_tot = (p_tot + 63) & ~(size_t)63;            // tiles are 64-byte lines
-				j.p_off = (int64_t)p_tot;
-				if (bp.nsb) {                                  // a band of 128 * nsb diagonals with a sufficiency proof (mm355_dpband.h)
-					j.pad = 2; j.dlo = bp.dlo; j.lmin = bp.lmin; j.bw = bp.bw;
-					p_tot += band_matrix_bytes(j.qlen, bp.bw);
-					g = bp.bw == 64? DP_G_BANDH : bp.nsb == 1? DP_G_BAND1 : bp.nsb == 2? DP_G_BAND2 : DP_G_BAND4;
-				} else {
-					j.pad = 1;
-					p_tot += row_matrix_bytes(j.qlen, T);
-					g = rowl? DP_G_ROWL : j.tlen <= 256? DP_G_ROW2 : j.tlen <= 512? DP_G_ROW4 : DP_G_ROW8;
-				}
-			} else {
-				p_tot += ((size_t)(j.qlen + j.tlen - 1) * n_col_ + 1) * 16;
-				int cls = 0;
-				while (cls < DP_N_CLASS - 1 && T > classes[cls].cap) ++cls;
-				if (use_regw && T > 1024 && !(j.flag & EZ_APPROX_MAX) && w <= DP_WIN_MAX_W && (!regw8 || ((j.qlen + 15) & ~15) + T <= MW_SEQ_MAX)) {
-					g = DP_G_REGW;
-					const size_t sb = (size_t)((j.qlen + 15) & ~15) + (size_t)T;
-					if (sb > regw_seq) regw_seq = sb;
-				}
-				else {
-					if (cls == DP_N_CLASS - 1) { j.st_off = (int64_t)st_tot; st_tot += T; }
-					g = cls * 2 + ((j.flag & EZ_APPROX_MAX)? 0 : 1);
-				}
-			}
-		}
-		grp[i] = (uint8_t)g; ++n_grp[g];
+		const DpPlan p = mm355_dp_plan(dc, kn, mo->max_sw_mat, j.qlen, j.tlen, j.w, j.flag);
+		if (p.line) p_tot = (p_tot + 63) & ~(size_t)63;
+		j.skip = p.skip; j.pad = p.pad; j.dlo = p.dlo; j.lmin = p.lmin; j.bw = p.bw; j.rsv = 0;
+		j.p_off = (int64_t)p_tot; j.off_off = 0; j.cig_off = (int64_t)cig_tot; j.st_off = p.st_words? (int64_t)st_tot : 0;
+		p_tot += p.bt_bytes; cig_tot += p.cig_words; st_tot += p.st_words;
+		if (p.regw_lds > regw_seq) regw_seq = p.regw_lds;
+		grp[i] = (uint8_t)p.group; ++n_grp[p.group];
 		int lb = (j.qlen + j.tlen) >> 3; if (lb < 0) lb = 0; if (lb >= LB) lb = LB - 1;
 		++lcnt[LB - 1 - lb];
 	}
-	if (const char *dump = getenv("MM355_DP_DUMP")) {   // diagnostics: (qlen, tlen, w, flag) of every job of this launch group, appended
+	if (const char *dump = getenv("MM355_DP_DUMP")) {   // diagnostics: (qlen, tlen, w, flag) of every job of this round, appended
 		static std::mutex dm; std::lock_guard<std::mutex> lk(dm);
 		if (FILE *fp = fopen(dump, "ab")) { for (size_t i = 0; i < n; ++i) { int32_t v[4] = { jobs[i].qlen, jobs[i].tlen, jobs[i].w, jobs[i].flag }; fwrite(v, 4, 4, fp); } fclose(fp); }
 	}
@@ -669,35 +619,26 @@ int mm355_dp_run(mm355_ctx *c, const mm355_mapopt_t *mo, DpJobDev *jobs, size_t 
 		// launch lists in the same order (most anti-diagonals first): a wave is one alignment, so the longest sweeps of a class start at
 		// t = 0 and the short ones fill in behind them instead of the launch ending on a late-started long one
 		for (size_t k = 0; k < n; ++k) { const int32_t i = h_ord[k]; h_ids[cur[grp[i]]++] = i; }
-		// k_ksw_band2 pairs neighbours of its list and both share KSW_EZ_RIGHT: the list is cut in two by that flag (order kept)
+		// k_ksw_band2's list is cut in two by KSW_EZ_RIGHT (order kept)
 		n_half_right = (size_t)(std::stable_partition(h_ids + grp_off[DP_G_BANDH], h_ids + grp_off[DP_G_BANDH] + n_grp[DP_G_BANDH], [&](int32_t i) { return (jobs[i].flag & EZ_RIGHT) != 0; }) - (h_ids + grp_off[DP_G_BANDH]));
 	}
+	auto unit_jobs = [&](const DpUnit &u) { return grp_off[u.g1] - grp_off[u.g0]; };
 	if (c->dp_jobs.ensure(n * sizeof(DpJobDev)) || c->dp_res.ensure(n * sizeof(mm355_dpres_t)) || c->dp_bt.ensure(p_tot + 64, 4) ||
-	    c->dp_work.ensure((off_tot + 16) * 4 + (2 * n + 32) * 4) || c->dp_cig.ensure((cig_tot + 16) * 4) || c->dp_dense.ensure((cig_tot + 16) * 4) ||
+	    c->dp_work.ensure(16 * 4 + (2 * n + 32) * 4) || c->dp_cig.ensure((cig_tot + 16) * 4) || c->dp_dense.ensure((cig_tot + 16) * 4) ||
 	    c->dp_H.ensure((st_tot + 16) * 12)) return MM355_ENOMEM;
-	// One extension round saturates the GPU.  Rounds of different contexts take turns (per device): run side by side they would all
-	// finish late together and the contexts would march in lock-step -- GPU idle while every host tail runs, hosts idle while every
-	// round runs.  Taking turns lets the first finisher start its host tail while the next round has the whole GPU.
-	struct Turn {   // counting semaphore: MM355_DP_TURNS rounds at a time per device (default 1, 0 = unlimited)
-		std::mutex m; std::condition_variable cv; int busy = 0;
-		void lock(int cap) { std::unique_lock<std::mutex> lk(m); cv.wait(lk, [&] { return busy < cap; }); ++busy; }
-		void unlock() { { std::lock_guard<std::mutex> lk(m); --busy; } cv.notify_one(); }
-	};
 	static std::vector<Turn> dp_turn((size_t)mm355_device_count());   // one per device, indexed by the device id
 	static const int turn_cap = [] { const char *e = getenv("MM355_DP_TURNS"); return e? atoi(e) : 1; }();
 	const bool take_turns = turn_cap > 0;
-	struct TurnGuard { Turn *t = 0; void lock(Turn *x, int cap) { x->lock(cap); t = x; } void unlock() { if (t) { t->unlock(); t = 0; } } ~TurnGuard() { unlock(); } } turn;
-	Turn *my_turn = &dp_turn[c->dev];
+	TurnGuard turn;
+	// ---- upload
 	HIPCHK(hipMemcpyAsync(c->dp_jobs.p, jobs, n * sizeof(DpJobDev), hipMemcpyHostToDevice, c->st));
 	int32_t *d_off = c->dp_work.as<int32_t>();
-	int32_t *d_ids = d_off + off_tot + 16;
+	int32_t *d_ids = d_off + 16;               // (off[] / off_end[] of the reference are recomputed, never stored: d_off stays empty)
 	uint64_t *d_S = c->dp_H.as<uint64_t>();
-	int32_t *d_H = (int32_t*)(d_S + st_tot + 8);
 	unsigned long long *d_cells = c->counters.as<unsigned long long>() + 4, *d_dense = c->counters.as<unsigned long long>() + 5;
-	double t_turn0 = 0;
 	bool redo_timed = false;
 	HIPCHK(hipMemsetAsync(d_dense, 0, 8, c->st));
-	unsigned long long *d_gcells = c->counters.as<unsigned long long>() + CTR_GCELLS_OFF;   // cells per group [CTR_GROUPS][DP_CTR_SPREAD]
+	unsigned long long *d_gcells = c->counters.as<unsigned long long>() + CTR_GCELLS_OFF;
 	HIPCHK(hipMemsetAsync(d_cells, 0, 8, c->st));
 	HIPCHK(hipMemsetAsync(d_gcells, 0, CTR_GCELLS_WORDS * 8, c->st));
 	// band kernels: [0] = problems whose proof failed, then their ids; behind it the launch lists of their second run
@@ -705,155 +646,52 @@ int mm355_dp_run(mm355_ctx *c, const mm355_mapopt_t *mo, DpJobDev *jobs, size_t 
 	if (c->dp_fail.ensure((2 * n_band + 64) * 4 + (n_band + 8) * sizeof(DpJobDev)) || c->h_fail.ensure((2 * n_band + 64) * 4 + (n_band + 8) * sizeof(DpJobDev))) return MM355_ENOMEM;
 	int32_t *d_fail = c->dp_fail.as<int32_t>();
 	if (n_band) HIPCHK(hipMemsetAsync(d_fail, 0, 4, c->st));
-	// every group gets its own HIP stream: the few long alignments of the big classes run concurrently with the thousands of
-	// short ones instead of holding the GPU alone (same-stream launches would serialise the classes)
 	HIPCHK(hipMemcpyAsync(d_ids, h_ids, (2 * n + 8) * 4, hipMemcpyHostToDevice, c->st));   // launch lists + backtrack order (pinned source)
 	if (c->dp_up_ev == 0) HIPCHK(hipEventCreateWithFlags(&c->dp_up_ev, hipEventDisableTiming));
-	HIPCHK(hipEventRecord(c->dp_up_ev, c->st));   // the group streams start after the uploads
-	(void)hipFuncSetAttribute((const void*)k_ksw_extd2<512>, hipFuncAttributeMaxDynamicSharedMemorySize, 12288 * 12);
-	// Streams (created back to back at context creation, so they sit on different hardware queues): 0 approx targets <= 256 (the wide
-	// grids), 1 every exact register class, 2 approx 1024, 3 approx 512, 4 the eight-wave kernel.  The long-target classes (4096 /
-	// 12288 LDS state, HBM state; approx and exact) are ONE launch: a few dozen latency-bound alignments that must not queue behind
-	// one another, nor in front of the register classes on a shared hardware queue (they are not part of the turn).
-	static const bool legacy_groups = [] { const char *e = getenv("MM355_DP_SPLIT_LONG"); return e && atoi(e) != 0; }();
-	const DpJobDev *dj = c->dp_jobs.as<DpJobDev>();
-	mm355_dpres_t *dres = c->dp_res.as<mm355_dpres_t>();
-	auto group_stream = [&](int sidx, hipStream_t *out) -> int { return c->dp_stream(sidx, out); };
-	auto group_begin = [&](int g, hipStream_t gst) -> int {
-		if (c->dp_ev[g] == 0) HIPCHK(hipEventCreateWithFlags(&c->dp_ev[g], hipEventDisableTiming));
-		HIPCHK(hipStreamWaitEvent(gst, c->dp_up_ev, 0));
-		if (c->dp_ev0[g] == 0) HIPCHK(hipEventCreate(&c->dp_ev0[g]));
-		if (c->dp_ev1[g] == 0) HIPCHK(hipEventCreate(&c->dp_ev1[g]));
-		HIPCHK(hipEventRecord(c->dp_ev0[g], gst));
-		return 0;
-	};
-	auto group_end = [&](int g, hipStream_t gst, bool in_turn) -> int {
-		HIPCHK(hipEventRecord(c->dp_ev1[g], gst));
-		HIPCHK(hipEventRecord(c->dp_ev[g], gst));
-		if (in_turn) HIPCHK(hipStreamWaitEvent(c->st, c->dp_ev[g], 0));   // the eight-wave kernels are joined after the turn (below)
-		return 0;
-	};
-	// The long-target classes are two launches: targets <= 4096 (49 KB of LDS state: three alignments per CU) on stream 4, and longer ones
-	// (147 KB: one per CU; state in HBM beyond 12288 positions) on stream 5; approx and exact alignments share a launch.
-	// (MM355_DP_LONG_NT=1024: sixteen waves per alignment -- measured slower, 1019 vs 880 ms/step: the wider barrier costs more than
-	// the saved chunk rounds.)
-	static const bool nt512 = [] { const char *e = getenv("MM355_DP_LONG_NT"); return !(e && atoi(e) == 1024); }();
-	struct LongLaunch { int g0, g1, cap, sidx; };
-	static const LongLaunch long_launch[2] = { { 10, 14, 12288, 5 }, { 8, 10, 4096, 4 } };   // (groups 14, 15 are the row kernels)   // the longest sweeps first
-	bool long_used[2] = { false, false };
-	if (!legacy && !legacy_groups) for (int li = 0; li < 2; ++li) {
-		const LongLaunch &ll = long_launch[li];
-		const size_t nl = grp_off[ll.g1] - grp_off[ll.g0];
-		if (nl == 0) continue;
-		long_used[li] = true;
-		hipStream_t gst; int rc2;
-		if ((rc2 = group_stream(ll.sidx, &gst))) return rc2;
-		if ((rc2 = group_begin(ll.g0, gst))) return rc2;
-		if (nt512)
-			hipLaunchKernelGGL(k_ksw_extd2<512>, dim3((unsigned)nl), dim3(512), (size_t)ll.cap * 12, gst, dc, dj, d_ids + grp_off[ll.g0], (int)nl, d_q, d_t, c->dp_bt.as<uint8_t>(), d_off,
-			                   c->dp_cig.as<uint32_t>(), d_S, d_H, dres, ll.cap, d_gcells, c->dp_dense.as<uint32_t>(), d_dense, 4);
-		else {
-			(void)hipFuncSetAttribute((const void*)k_ksw_extd2<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, 12288 * 12);
-			hipLaunchKernelGGL(k_ksw_extd2<1024>, dim3((unsigned)nl), dim3(1024), (size_t)ll.cap * 12, gst, dc, dj, d_ids + grp_off[ll.g0], (int)nl, d_q, d_t, c->dp_bt.as<uint8_t>(), d_off,
-			                   c->dp_cig.as<uint32_t>(), d_S, d_H, dres, ll.cap, d_gcells, c->dp_dense.as<uint32_t>(), d_dense, 4);
+	HIPCHK(hipEventRecord(c->dp_up_ev, c->st));   // the unit streams start after the uploads
+	DpLaunchArgs la = { dc, c->dp_jobs.as<DpJobDev>(), d_q, d_t, c->dp_bt.as<uint8_t>(), c->dp_res.as<mm355_dpres_t>(), d_off, c->dp_cig.as<uint32_t>(), d_S, (int32_t*)(d_S + st_tot + 8),
+	                    c->dp_dense.as<uint32_t>(), d_dense, d_fail, d_gcells, regw_seq, n_half_right };
+	auto launch_units = [&](bool in_turn) -> int {
+		for (const DpUnit &u : DP_UNITS) {
+			if (u.in_turn != in_turn || unit_jobs(u) == 0) continue;
+			hipStream_t gst; int rc;
+			if ((rc = c->dp_stream(u.stream, &gst)) || (rc = group_begin(c, u.g0, gst))) return rc;
+			if ((rc = u.launch(la, gst, d_ids + grp_off[u.g0], (unsigned)unit_jobs(u), d_gcells + DP_CTR_SPREAD * u.g0))) return rc;
+			if ((rc = group_end(c, u.g0, gst, u.join_at_once))) return rc;
 		}
-		if ((rc2 = group_end(ll.g0, gst, false))) return rc2;
-	}
-	if (n_grp[DP_G_REGW]) {   // the long narrow-band extensions: one wave each, thousands of anti-diagonals -- the longest latency chain of a round
-		hipStream_t gst; int rc2;
-		if ((rc2 = group_stream(7, &gst))) return rc2;
-		if ((rc2 = group_begin(DP_G_REGW, gst))) return rc2;
-		// eight waves per alignment (mm355_dpmw.h), the sequences of a block in (dynamic) LDS
-		// (per launch, not once per process: the attribute belongs to the function on the CURRENT device, and one process may drive several)
-		if (regw8 && regw_seq + 64 > 32768 && hipFuncSetAttribute((const void*)k_ksw_regw8, hipFuncAttributeMaxDynamicSharedMemorySize, MW_SEQ_MAX + 64) != hipSuccess) return MM355_EHIP;
-		if (regw8) hipLaunchKernelGGL(k_ksw_regw8, dim3((unsigned)n_grp[DP_G_REGW]), dim3(MW_THREADS), regw_seq + 64, gst, dc, dj, d_ids + grp_off[DP_G_REGW], (int)n_grp[DP_G_REGW], d_q, d_t,
-		                              c->dp_bt.as<uint8_t>(), dres, d_gcells + DP_CTR_SPREAD * DP_G_REGW);
-		else hipLaunchKernelGGL(k_ksw_regw, dim3((unsigned)n_grp[DP_G_REGW]), dim3(64), 0, gst, dc, dj, d_ids + grp_off[DP_G_REGW], (int)n_grp[DP_G_REGW], d_q, d_t,
-		                        c->dp_bt.as<uint8_t>(), dres, d_gcells + DP_CTR_SPREAD * DP_G_REGW);
-		if ((rc2 = group_end(DP_G_REGW, gst, false))) return rc2;
-	}
-	if (n_grp[DP_G_ROWL]) {   // the eight-wave row sweep of the long full-band fills: a few hundred blocks at most, outside the turn as well
-		hipStream_t gst; int rc2;
-		if ((rc2 = group_stream(6, &gst))) return rc2;
-		if ((rc2 = group_begin(DP_G_ROWL, gst))) return rc2;
-		hipLaunchKernelGGL(k_ksw_rowl, dim3((unsigned)n_grp[DP_G_ROWL]), dim3(64 * ROWL_WAVES), 0, gst, dc, dj, d_ids + grp_off[DP_G_ROWL], (int)n_grp[DP_G_ROWL], d_q, d_t,
-		                   c->dp_bt.as<uint8_t>(), dres, d_gcells + DP_CTR_SPREAD * DP_G_ROWL);
-		if ((rc2 = group_end(DP_G_ROWL, gst, false))) return rc2;
-	}
-	// (the launches above -- the long-target kernels -- are not part of the turn: a few dozen latency-bound alignments that leave the GPU
-	// almost empty; started BEFORE the turn is taken they run while this context waits for it)
+		return 0;
+	};
+	// ---- the units outside the turn
+	if (int rc = launch_units(false)) return rc;
 	// everything this round depends on (code-string gather, descriptor uploads) is finished BEFORE the turn is taken: the turn then holds
 	// nothing but extension kernels
-	if (take_turns) { HIPCHK(mm355_wait_stream(c->st)); turn.lock(my_turn, turn_cap); }
-	t_turn0 = mm355_now_ms();
+	if (take_turns) { HIPCHK(mm355_wait_stream(c->st)); turn.lock(&dp_turn[c->dev], turn_cap); }
+	const double t_turn0 = mm355_now_ms();
 	{
 		EvTimer2 tm(c, &c->stats.ms_dp);
-		for (int g = DP_N_GROUP - 1; g >= 0; --g) {   // big problems first
-			if (n_grp[g] == 0 || g == DP_G_ROWL || g == DP_G_REGW) continue;
-			if (g >= DP_G_ROW2) {   // the row sweep of the full-band approximate fills: the wide throughput grids of a round
-				hipStream_t gst; int rc2;
-				if ((rc2 = group_stream(g == DP_G_ROW2 || g == DP_G_BAND1 || g == DP_G_BANDH? 0 : g == DP_G_ROW4 || g == DP_G_BAND2? 3 : 2, &gst))) return rc2;
-				if ((rc2 = group_begin(g, gst))) return rc2;
-				if (g == DP_G_BANDH) {
-					const size_t nr = n_half_right, nl = n_grp[g] - nr;
-					if (nr) hipLaunchKernelGGL(k_ksw_band2, dim3((unsigned)((nr + 1) / 2)), dim3(64), 0, gst, dc, dj, d_ids + grp_off[g], (int)nr, d_q, d_t, c->dp_bt.as<uint8_t>(), dres, d_gcells + DP_CTR_SPREAD * g, d_fail);
-					if (nl) hipLaunchKernelGGL(k_ksw_band2, dim3((unsigned)((nl + 1) / 2)), dim3(64), 0, gst, dc, dj, d_ids + grp_off[g] + nr, (int)nl, d_q, d_t, c->dp_bt.as<uint8_t>(), dres, d_gcells + DP_CTR_SPREAD * g, d_fail);
-				}
-				else if (g == DP_G_BAND1) hipLaunchKernelGGL(k_ksw_band<1>, dim3((unsigned)n_grp[g]), dim3(64), 0, gst, dc, dj, d_ids + grp_off[g], (int)n_grp[g], d_q, d_t, c->dp_bt.as<uint8_t>(), dres, d_gcells + DP_CTR_SPREAD * g, d_fail);
-				else if (g == DP_G_BAND2) hipLaunchKernelGGL(k_ksw_band<2>, dim3((unsigned)n_grp[g]), dim3(64), 0, gst, dc, dj, d_ids + grp_off[g], (int)n_grp[g], d_q, d_t, c->dp_bt.as<uint8_t>(), dres, d_gcells + DP_CTR_SPREAD * g, d_fail);
-				else if (g == DP_G_BAND4) hipLaunchKernelGGL(k_ksw_band<4>, dim3((unsigned)n_grp[g]), dim3(64), 0, gst, dc, dj, d_ids + grp_off[g], (int)n_grp[g], d_q, d_t, c->dp_bt.as<uint8_t>(), dres, d_gcells + DP_CTR_SPREAD * g, d_fail);
-				else if (g == DP_G_ROW2) hipLaunchKernelGGL(k_ksw_row<2>, dim3((unsigned)n_grp[g]), dim3(64), 0, gst, dc, dj, d_ids + grp_off[g], (int)n_grp[g], d_q, d_t, c->dp_bt.as<uint8_t>(), dres, d_gcells + DP_CTR_SPREAD * g);
-				else if (g == DP_G_ROW4) hipLaunchKernelGGL(k_ksw_row<4>, dim3((unsigned)n_grp[g]), dim3(64), 0, gst, dc, dj, d_ids + grp_off[g], (int)n_grp[g], d_q, d_t, c->dp_bt.as<uint8_t>(), dres, d_gcells + DP_CTR_SPREAD * g);
-				else hipLaunchKernelGGL(k_ksw_row<8>, dim3((unsigned)n_grp[g]), dim3(64), 0, gst, dc, dj, d_ids + grp_off[g], (int)n_grp[g], d_q, d_t, c->dp_bt.as<uint8_t>(), dres, d_gcells + DP_CTR_SPREAD * g);
-				if ((rc2 = group_end(g, gst, true))) return rc2;
-				continue;
-			}
-			const DpClass &k = classes[g >> 1];
-			if (k.kind == 2 && !legacy && !legacy_groups) continue;   // launched above
-			const int sidx = k.kind != 0? 4 + (g - 8) : (g & 1)? 1 : g >= 6? 2 : g >= 4? 3 : 0;
-			hipStream_t gst; int rc2;
-			if ((rc2 = group_stream(sidx, &gst))) return rc2;
-			if ((rc2 = group_begin(g, gst))) return rc2;
-			unsigned long long *gc = d_gcells + DP_CTR_SPREAD * g;
-			const unsigned nj = (unsigned)n_grp[g];
-			const int32_t *gid = d_ids + grp_off[g];
-			if (k.kind == 0) {
-				const bool ex = g & 1;
-				if (k.np == 1) launch_reg<1>(ex, nj, gst, dc, dj, gid, d_q, d_t, c->dp_bt.as<uint8_t>(), dres, gc);
-				else if (k.np == 2) launch_reg<2>(ex, nj, gst, dc, dj, gid, d_q, d_t, c->dp_bt.as<uint8_t>(), dres, gc);
-				else if (k.np == 4) launch_reg<4>(ex, nj, gst, dc, dj, gid, d_q, d_t, c->dp_bt.as<uint8_t>(), dres, gc);
-				else launch_reg<8>(ex, nj, gst, dc, dj, gid, d_q, d_t, c->dp_bt.as<uint8_t>(), dres, gc);
-			} else if (k.kind == 1)
-				hipLaunchKernelGGL(k_ksw_extd2<64>, dim3(nj), dim3(64), (size_t)k.cap * 12, gst, dc, dj, gid, (int)nj, d_q, d_t, c->dp_bt.as<uint8_t>(), d_off,
-				                   c->dp_cig.as<uint32_t>(), d_S, d_H, dres, k.cap, gc, c->dp_dense.as<uint32_t>(), d_dense, -1);
-			else
-				hipLaunchKernelGGL(k_ksw_extd2<512>, dim3(nj), dim3(512), (size_t)k.cap * 12, gst, dc, dj, gid, (int)nj, d_q, d_t, c->dp_bt.as<uint8_t>(), d_off,
-				                   c->dp_cig.as<uint32_t>(), d_S, d_H, dres, k.cap, gc, c->dp_dense.as<uint32_t>(), d_dense, -1);
-			if ((rc2 = group_end(g, gst, k.kind == 0 && !(g & 1)))) return rc2;   // in the turn: the approximate register classes; the exact ones are small latency-bound grids
-		}
+		// ---- the turn
+		if (int rc = launch_units(true)) return rc;
 		// band kernels whose proof failed (a divergent stretch, a long indel: the optimal path may leave the band): the same problems again, on
 		// the full-matrix row sweep, inside the same turn; their direction matrices go to a buffer of their own
-		bool rowl_redo = false;
 		if (n_band) {
 			int32_t *h_fail = (int32_t*)c->h_fail.p;
-			HIPCHK(hipMemcpyAsync(h_fail, d_fail, (1 + n_band) * 4, hipMemcpyDeviceToHost, c->st));   // (c->st has joined every band group: group_end)
+			HIPCHK(hipMemcpyAsync(h_fail, d_fail, (1 + n_band) * 4, hipMemcpyDeviceToHost, c->st));   // (c->st has joined every band unit: group_end)
 			HIPCHK(mm355_wait_stream(c->st));
 			const size_t n_fail = (size_t)h_fail[0];
 			c->stats.n_dp_band += (int64_t)n_band; c->stats.n_dp_band_redo += (int64_t)n_fail;
 			if (n_fail) {
 				std::sort(h_fail + 1, h_fail + 1 + n_fail);                  // (the device appended them in no particular order)
-				int32_t *h_rid = h_fail + 1 + n_band;                        // launch lists of the second run: row<8>, row<4>, row<2>, rowl
+				int32_t *h_rid = h_fail + 1 + n_band;                        // launch lists of the second run, by redo class
 				DpJobDev *h_rj = (DpJobDev*)((char*)c->h_fail.p + (2 * n_band + 64) * 4);
 				size_t p2 = 0, cnt[4] = {0, 0, 0, 0}, pos[4];
-				auto cls_of = [&](const DpJobDev &j) { return j.tlen > ROW_MAX_T? 3 : j.tlen <= 256? 2 : j.tlen <= 512? 1 : 0; };
-				for (size_t k = 0; k < n_fail; ++k) ++cnt[cls_of(jobs[h_fail[1 + k]])];
+				for (size_t k = 0; k < n_fail; ++k) ++cnt[dp_redo_class(jobs[h_fail[1 + k]])];
 				pos[0] = 0; pos[1] = cnt[0]; pos[2] = pos[1] + cnt[1]; pos[3] = pos[2] + cnt[2];
 				for (size_t k = 0; k < n_fail; ++k) {
 					DpJobDev &j = jobs[h_fail[1 + k]];
 					j.pad = 1 | 4; j.p_off = (int64_t)p2; j.bw = 0;
 					p2 += (row_matrix_bytes(j.qlen, (j.tlen + 15) / 16 * 16) + 63) & ~(size_t)63;
 					h_rj[k] = j;
-					h_rid[pos[cls_of(j)]++] = h_fail[1 + k];
+					h_rid[pos[dp_redo_class(j)]++] = h_fail[1 + k];
 				}
 				if (c->dp_bt2.ensure(p2 + 64, 4)) return MM355_ENOMEM;
 				int32_t *d_rid = d_fail + 1 + n_band; DpJobDev *d_rj = (DpJobDev*)((char*)c->dp_fail.p + (2 * n_band + 64) * 4);
@@ -865,43 +703,34 @@ int mm355_dp_run(mm355_ctx *c, const mm355_mapopt_t *mo, DpJobDev *jobs, size_t 
 				if (c->dp_ev0[g] == 0) HIPCHK(hipEventCreate(&c->dp_ev0[g]));
 				if (c->dp_ev1[g] == 0) HIPCHK(hipEventCreate(&c->dp_ev1[g]));
 				HIPCHK(hipEventRecord(c->dp_ev0[g], c->st));
-				unsigned long long *gc = d_gcells + DP_CTR_SPREAD * g;
-				size_t o0 = 0;
-				if (cnt[0]) hipLaunchKernelGGL(k_ksw_row<8>, dim3((unsigned)cnt[0]), dim3(64), 0, c->st, dc, dj, d_rid + o0, (int)cnt[0], d_q, d_t, c->dp_bt2.as<uint8_t>(), dres, gc);
-				o0 += cnt[0];
-				if (cnt[1]) hipLaunchKernelGGL(k_ksw_row<4>, dim3((unsigned)cnt[1]), dim3(64), 0, c->st, dc, dj, d_rid + o0, (int)cnt[1], d_q, d_t, c->dp_bt2.as<uint8_t>(), dres, gc);
-				o0 += cnt[1];
-				if (cnt[2]) hipLaunchKernelGGL(k_ksw_row<2>, dim3((unsigned)cnt[2]), dim3(64), 0, c->st, dc, dj, d_rid + o0, (int)cnt[2], d_q, d_t, c->dp_bt2.as<uint8_t>(), dres, gc);
-				o0 += cnt[2];
-				if (cnt[3]) { hipLaunchKernelGGL(k_ksw_rowl, dim3((unsigned)cnt[3]), dim3(64 * ROWL_WAVES), 0, c->st, dc, dj, d_rid + o0, (int)cnt[3], d_q, d_t, c->dp_bt2.as<uint8_t>(), dres, gc); rowl_redo = true; }
+				DpLaunchArgs la2 = la; la2.bt = c->dp_bt2.as<uint8_t>();
+				for (int k = 0; k < 4; ++k) {
+					if (cnt[k]) (void)DP_REDO_LAUNCH[k](la2, c->st, d_rid, (unsigned)cnt[k], d_gcells + DP_CTR_SPREAD * g);
+					d_rid += cnt[k];
+				}
 				HIPCHK(hipEventRecord(c->dp_ev1[g], c->st));
 				redo_timed = true;
 			}
 		}
-		(void)rowl_redo;
 		// the turn ends when the extension kernels are done: the backtrack below is a latency-bound pointer walk and, like the result
 		// copies, overlaps the next context's round
-		// (only the wide register-kernel grids count: the few long alignments of the eight-wave classes are latency chains that
-		// leave the GPU almost empty; they keep running while the next context's round starts)
 		if (take_turns) { const double tl1 = mm355_now_ms(); HIPCHK(mm355_wait_stream(c->st)); turn.unlock(); const double tl2 = mm355_now_ms(); mm355_trace_add(c, "dpk", t_turn0, tl2); mm355_trace_add(c, "dpk_launch", t_turn0, tl1); }
-		if (n_grp[DP_G_ROWL]) HIPCHK(hipStreamWaitEvent(c->st, c->dp_ev[DP_G_ROWL], 0));
-		if (n_grp[DP_G_REGW]) HIPCHK(hipStreamWaitEvent(c->st, c->dp_ev[DP_G_REGW], 0));
-		if (!legacy && !legacy_groups) { for (int li = 0; li < 2; ++li) if (long_used[li]) HIPCHK(hipStreamWaitEvent(c->st, c->dp_ev[long_launch[li].g0], 0)); }
-		else { for (int g = 0; g < 2 * DP_N_CLASS; ++g) if (n_grp[g] && classes[g >> 1].kind != 0) HIPCHK(hipStreamWaitEvent(c->st, c->dp_ev[g], 0)); }
-		for (int g = 1; g < 8; g += 2) if (n_grp[g] && classes[g >> 1].kind == 0) HIPCHK(hipStreamWaitEvent(c->st, c->dp_ev[g], 0));   // the exact register classes
-		// backtrack: all jobs, longest first so that the lanes of a wave walk paths of similar length
+		// ---- the units the main stream has not joined yet
+		for (const DpUnit &u : DP_UNITS) if (!u.join_at_once && unit_jobs(u)) HIPCHK(hipStreamWaitEvent(c->st, c->dp_ev[u.g0], 0));
+		// ---- backtrack: all jobs, longest first so that the lanes of a wave walk paths of similar length
 		KtScope ks_bt(c, KT_DP_BACKTRACK, c->st);
 		hipLaunchKernelGGL(k_ksw_backtrack, dim3((unsigned)((n + WAVE - 1) / WAVE)), dim3(WAVE), 0, c->st, c->dp_jobs.as<DpJobDev>(), d_ids + n + 8, (int)n,
 		                   c->dp_bt.as<uint8_t>(), c->dp_bt2.as<uint8_t>(), c->dp_cig.as<uint32_t>(), c->dp_res.as<mm355_dpres_t>(), c->dp_dense.as<uint32_t>(), d_dense);
 	}
 	HIPCHK(hipGetLastError());
+	// ---- copy back
 	if (c->h_res.ensure(n * sizeof(mm355_dpres_t) + 64 + CTR_GCELLS_WORDS * 8)) return MM355_ENOMEM;
 	unsigned long long *ctr = (unsigned long long*)((char*)c->h_res.p + n * sizeof(mm355_dpres_t));   // pinned landing zone of the counters
 	HIPCHK(hipMemcpyAsync(ctr, d_cells, 16, hipMemcpyDeviceToHost, c->st));
 	HIPCHK(hipMemcpyAsync(ctr + 2, d_gcells, CTR_GCELLS_WORDS * 8, hipMemcpyDeviceToHost, c->st));
 	HIPCHK(hipMemcpyAsync(c->h_res.p, c->dp_res.p, n * sizeof(mm355_dpres_t), hipMemcpyDeviceToHost, c->st));
 	HIPCHK(mm355_wait_stream(c->st));
-	if (const char *dump = getenv("MM355_DP_DUMP_BT")) {   // diagnostics: the direction matrices of this launch group, raw
+	if (const char *dump = getenv("MM355_DP_DUMP_BT")) {   // diagnostics: the direction matrices of this round, raw
 		std::vector<uint8_t> hb(p_tot + 64);
 		if (hipMemcpy(hb.data(), c->dp_bt.p, p_tot, hipMemcpyDeviceToHost) == hipSuccess) if (FILE *fp = fopen(dump, "wb")) { fwrite(hb.data(), 1, p_tot, fp); fclose(fp); }
 	}
@@ -909,29 +738,25 @@ int mm355_dp_run(mm355_ctx *c, const mm355_mapopt_t *mo, DpJobDev *jobs, size_t 
 	if (arena->ensure((n_dense + 16) * 4)) return MM355_ENOMEM;
 	if (n_dense) HIPCHK(hipMemcpyAsync(arena->p, c->dp_dense.p, n_dense * 4, hipMemcpyDeviceToHost, c->st));
 	HIPCHK(mm355_wait_stream(c->st));
-	{
-		int64_t tot = 0;
-		const bool merged_long = !legacy && getenv("MM355_DP_SPLIT_LONG") == 0;
-		for (int g = 0; g < DP_N_GROUP; ++g) {
-			// the merged long-target launches are timed as groups 8 (targets <= 4096) and 10 (longer)
-			const bool timed_here = merged_long && g >= 8 && g < 14? ((g == 8 && grp_off[10] > grp_off[8]) || (g == 10 && grp_off[14] > grp_off[10])) : n_grp[g] != 0;
-			float ms = 0.f;
-			if (timed_here && hipEventElapsedTime(&ms, c->dp_ev0[g], c->dp_ev1[g]) == hipSuccess) c->stats.ms_dp_group[g] += ms;
+	// ---- statistics: a unit's elapsed time under its first group, cells and launches under each group of its list
+	auto group_cells = [&](int g) { int64_t gc = 0; for (int k = 0; k < DP_CTR_SPREAD; ++k) gc += (int64_t)ctr[2 + DP_CTR_SPREAD * g + k]; return gc; };
+	auto group_ms = [&](int g) { float ms = 0.f; if (hipEventElapsedTime(&ms, c->dp_ev0[g], c->dp_ev1[g]) == hipSuccess) c->stats.ms_dp_group[g] += ms; };
+	int64_t tot = 0;
+	for (const DpUnit &u : DP_UNITS) {
+		if (unit_jobs(u) == 0) continue;
+		group_ms(u.g0);
+		for (int g = u.g0; g < u.g1; ++g) {
 			if (n_grp[g] == 0) continue;
-			int64_t gc = 0;
-			for (int k = 0; k < DP_CTR_SPREAD; ++k) gc += (int64_t)ctr[2 + DP_CTR_SPREAD * g + k];
+			const int64_t gc = group_cells(g);
 			c->stats.dp_cells_group[g] += gc; ++c->stats.n_launch_group[g];
 			tot += gc;
 		}
-		if (redo_timed) {   // the second run of the band problems whose proof failed (its cells are counted again: they were computed twice)
-			float ms = 0.f;
-			if (hipEventElapsedTime(&ms, c->dp_ev0[DP_G_REDO], c->dp_ev1[DP_G_REDO]) == hipSuccess) c->stats.ms_dp_group[DP_G_REDO] += ms;
-			int64_t gc = 0;
-			for (int k = 0; k < DP_CTR_SPREAD; ++k) gc += (int64_t)ctr[2 + DP_CTR_SPREAD * DP_G_REDO + k];
-			c->stats.dp_cells_group[DP_G_REDO] += gc; ++c->stats.n_launch_group[DP_G_REDO];
-		}
-		c->stats.dp_cells += tot; c->stats.n_dp_jobs += (int64_t)n; ++c->stats.n_launch_dp;
 	}
+	if (redo_timed) {   // the second run of the band problems whose proof failed (its cells are counted again: they were computed twice)
+		group_ms(DP_G_REDO);
+		c->stats.dp_cells_group[DP_G_REDO] += group_cells(DP_G_REDO); ++c->stats.n_launch_group[DP_G_REDO];
+	}
+	c->stats.dp_cells += tot; c->stats.n_dp_jobs += (int64_t)n; ++c->stats.n_launch_dp;
 	*res_out = (const mm355_dpres_t*)c->h_res.p; *cigar_out = (const uint32_t*)arena->p;
 	return 0;
 }

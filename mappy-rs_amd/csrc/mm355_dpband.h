@@ -31,10 +31,7 @@
 // reproduces H(-1, q) = boundary(q) by itself (a vertical gap from the corner).  Cells beyond the target only feed cells beyond the target.
 // Direction bytes: the tiles of the row sweep (4 rows x 16 cells = 64 B) over a W-byte row: byte (q, t) at row_cell_off(q, t - q - dlo, W).
 #pragma once
-
-#define BAND_MIN_MARGIN 8
-
-__host__ __device__ __forceinline__ size_t band_matrix_bytes(int qlen, int W) { return (size_t)((qlen + ROW_TILE_ROWS - 1) & ~(ROW_TILE_ROWS - 1)) * (size_t)W + 64; }
+#include "mm355_dpplan.h"   // BAND_MIN_MARGIN, band_matrix_bytes
 
 // wave_shl:1 with a carry word for lane 63, then the 16-bit funnel: { cur.hi, next.lo } = the cells one diagonal up
 __device__ __forceinline__ uint32_t band_shl(uint32_t cur, uint32_t carry)

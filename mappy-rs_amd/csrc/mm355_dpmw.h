@@ -21,9 +21,9 @@
 //     mailbox and leave one or two anti-diagonals late (the direction bytes they wrote past the end are never read: the backtrack starts at
 //     the bookkeeper's maximum).
 #pragma once
+#include "mm355_dpplan.h"   // MW_SEQ_MAX: query + target bytes staged in LDS (padded to 16 each); longer problems keep the other kernels
 
 #define MW_WAVES 8
-#define MW_SEQ_MAX 98304             // query + target bytes staged in LDS (padded to 16 each); longer problems keep the other kernels
 // The two sequences live in LDS for the whole sweep: a global load inside the loop -- even one behind a branch that is taken once in 64
 // anti-diagonals -- makes the compiler wait for vmcnt(0) at the join, i.e. for the direction bytes of the previous anti-diagonal to be
 // acknowledged by the L2: a memory round trip on every step of the dependency chain.

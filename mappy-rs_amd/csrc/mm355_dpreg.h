@@ -19,6 +19,7 @@
 // The direction code is the argmax position among (s, a, b, a2, b2) -- first maximum for left-aligned gaps, last maximum
 // with KSW_EZ_RIGHT -- computed without compares: n_i = min_u16(zmax - v_i, 1) is 0 exactly where v_i attains the maximum.
 #pragma once
+#include "mm355_dpplan.h"   // DP_WIN_MAX_W
 
 // The packed operations are emitted as written: left to itself the optimiser turns min_u16(x, 1) and the multiplications by
 // 0/1 flags back into per-half compares and selects (SDWA v_cmp + v_cndmask + v_perm), several instructions per half.
@@ -517,7 +518,7 @@ __global__ __launch_bounds__(64) void k_ksw_reg(DpConst dc, const DpJobDev *jobs
 
 // Targets of any length whose band is narrow (w <= DP_WIN_MAX_W: the extensions of a read's ends, w = 751 with the ONT preset): the same
 // sweep with the eight blocks as a WINDOW of 1024 target positions that follows the band (dp_rebase).  Exact score tracking only.
-#define DP_WIN_MAX_W 832                // live positions per anti-diagonal: st - 1 - base < 128, en + 16 (score spill) <= st + 15 + w + 31 -> < 1024
+static_assert(DP_WIN_MAX_W == 832, "mm355_dpplan.h");   // live positions per anti-diagonal: st - 1 - base < 128, en + 16 (score spill) <= st + 15 + w + 31 -> < 1024
 __global__ __launch_bounds__(64) void k_ksw_regw(DpConst dc, const DpJobDev *jobs, const int32_t *job_ids, int n_jobs,
                                                   const uint8_t *qbase, const uint8_t *tbase, uint8_t *pbase, mm355_dpres_t *res, unsigned long long *cells_ctr)
 {

@@ -28,14 +28,9 @@
 // descriptor names the layout (DpJobDev::pad = 1) and k_ksw_backtrack reads it that way.  ez: only `score` is defined for these problems
 // (max = 0, max_t = max_q = -1, not z-dropped), as in the approximate full-band path of k_ksw_reg.
 #pragma once
+#include "mm355_dpplan.h"   // ROW_NEG, ROW_TILE_ROWS, ROW_MAX_T, ROW_MAX_QT, ROWL_MAX_T, ROWL_MAX_Q, row_matrix_bytes
 
-#define ROW_NEG (-16384)
-#define ROW_TILE_ROWS 4
-// bytes of the tiled direction matrix of a qlen x tlen problem (T = tlen rounded up to 16; the matrix starts on a 64-byte boundary)
-__host__ __device__ __forceinline__ size_t row_matrix_bytes(int qlen, int T) { return (size_t)((qlen + ROW_TILE_ROWS - 1) & ~(ROW_TILE_ROWS - 1)) * ((size_t)T + 16) + 64; }
 __host__ __device__ __forceinline__ size_t row_cell_off(int q, int t, int tstride) { return (size_t)(q >> 2) * (size_t)(4 * tstride) + (size_t)(t >> 1) * 8 + (size_t)((q & 3) * 2 + (t & 1)); }
-#define ROW_MAX_T 1024              // eight register sets
-#define ROW_MAX_QT 6000             // qlen + tlen: keeps every value inside int16
 
 __device__ __forceinline__ uint32_t pk8w(int v) { const uint32_t h = (uint32_t)(uint16_t)(int16_t)v; return h | h << 16; }   // plain int16 in both halves
 __device__ __forceinline__ uint32_t pk_sign16(uint32_t a) { uint32_t r; asm("v_pk_ashrrev_i16 %0, 15, %1 op_sel_hi:[0,1]" : "=v"(r) : "v"(a)); return r; }   // 0xffff where the half is negative
@@ -242,8 +237,7 @@ __global__ __launch_bounds__(64) void k_ksw_row(DpConst dc, const DpJobDev *jobs
 #define ROWL_PANEL (128 * ROWL_NS)
 #define ROWL_WAVES 8
 #define ROWL_MAX_PANELS 16           // targets beyond 4096: wave w takes panels w and w + 8 one after the other (the fills of ~5000 x 5000 between
-#define ROWL_MAX_T (ROWL_PANEL * ROWL_MAX_PANELS)   // anchors a max_gap apart were the last single-block jobs of the eight-wave LDS kernel, 41 ms each)
-#define ROWL_MAX_Q 5120
+static_assert(ROWL_MAX_T == ROWL_PANEL * ROWL_MAX_PANELS, "mm355_dpplan.h");   // anchors a max_gap apart were the last single-block jobs of the eight-wave LDS kernel, 41 ms each)
 
 template <bool RIGHT>
 __device__ __forceinline__ void rowl_panel(const DpConst &dc, const RowK &K, const DpJobDev &jb, const uint8_t *query, const uint8_t *target, uint8_t *p, const int tstride,

@@ -7,6 +7,7 @@
 #include "mm355_host.h"
 #include "mm355_dev.h"
 #include "mm355_timers.h"
+#include "mm355_dpplan.h"   // MM355_DP_GROUPS
 
 // Device and pinned buffers own their memory: move-only, freed by the destructor (release() frees early, e.g. before a larger allocation)
 struct DBuf {
@@ -72,7 +73,7 @@ struct ResidentBatch { HostBatch hb; DBuf seq, roff, rlen, order, ck_read, ck_st
 //   CTR_HITS_OFF     minimizers k_seed_lookup found in the index, CTR_HITS_WORDS slots
 #define CTR_HEAD_WORDS   64
 #define CTR_SPREAD       16
-#define CTR_GROUPS       24
+#define CTR_GROUPS       MM355_DP_GROUPS
 #define CTR_GCELLS_OFF   CTR_HEAD_WORDS
 #define CTR_GCELLS_WORDS (CTR_GROUPS * CTR_SPREAD)
 #define CTR_PAIRS_OFF    (CTR_GCELLS_OFF + CTR_GCELLS_WORDS)
@@ -96,7 +97,7 @@ struct mm355_streams {
 	int pool_slot = -1; bool dp_shared = false;
 	int prio_low = 0, prio_high = 0; bool use_prio = false; int ord = 0;   // ord: creation ordinal of the context
 	hipEvent_t aux_ev = 0, aux_ev2 = 0, ev0 = 0, ev1 = 0, dp_up_ev = 0;
-	hipEvent_t dp_ev[24] = {}, dp_ev0[24] = {}, dp_ev1[24] = {};
+	hipEvent_t dp_ev[MM355_DP_GROUPS] = {}, dp_ev0[MM355_DP_GROUPS] = {}, dp_ev1[MM355_DP_GROUPS] = {};   // per launch group: done, and the timer pair
 	mm355_streams() = default;
 	mm355_streams(const mm355_streams&) = delete; mm355_streams &operator=(const mm355_streams&) = delete;
 	~mm355_streams() { release(); }
