@@ -5,7 +5,9 @@
 // minimap2 2.26 units whose observable behaviour is reproduced (reference call site: mm_map at
 // /root/reference/src/lib.rs:482 and :587):
 //   U:lchain.c::mg_lchain_rmq (+U:krmq.h), mg_chain_backtrack, compact_a      -> rechain_rmq()
-//   U:hit.c::mm_gen_regs .. mm_set_mapq, U:esterr.c::mm_est_err               -> regs_*()
+//   U:hit.c::mm_split_reg, mm_filter_regs, mm_hit_sort, mm_squeeze_a          -> split_reg(), filter_regs(), hit_sort(), squeeze_a()
+//     (the rest of the region logic -- mm_gen_regs, mm_set_parent, mm_select_sub, mm_set_mapq, U:esterr.c::mm_est_err ... -- is not typed
+//     here: mm355_regs.h states it once for the device and for this file, which instantiates it for Reg; mm_set_inv_mapq is in mm355_glue.h)
 //   U:align.c::mm_align_skeleton / mm_align1 / mm_test_zdrop / mm_update_extra / mm_align1_inv -> align_*()
 //   U:format.c::mm_gen_cs / mm_gen_MD                                          -> gen_cs() / gen_md()
 #include <stdlib.h>
@@ -24,8 +26,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#define PARENT_UNSET   (-1)
-#define PARENT_TMP_PRI (-2)
 #define EZ_RIGHT       0x02
 #define EZ_APPROX_MAX  0x08
 #define EZ_EXTZ_ONLY   0x40
@@ -436,79 +436,17 @@ static void rechain_rmq(int max_dist, int max_dist_inner, int bw, int max_chn_sk
 }
 
 // ================================================================== regions (U:hit.c, U:esterr.c)
-static inline uint32_t wang32(uint32_t key)
-{
-	key += ~(key << 15); key ^= (key >> 10); key += (key << 3); key ^= (key >> 6); key += ~(key << 11); key ^= (key >> 16);
-	return key;
-}
-static inline uint64_t hash64u(uint64_t key)
-{
-	key = (~key + (key << 21)); key = key ^ key >> 24; key = ((key + (key << 3)) + (key << 8)); key = key ^ key >> 14;
-	key = ((key + (key << 2)) + (key << 4)); key = key ^ key >> 28; key = (key + (key << 31));
-	return key;
-}
-
-static void reg_fuzzy_len(Reg *r, const mm128 *a)
-{
-	r->mlen = r->blen = 0;
-	if (r->cnt <= 0) return;
-	r->mlen = r->blen = (int32_t)(a[r->as].y >> 32 & 0xff);
-	for (int i = r->as + 1; i < r->as + r->cnt; ++i) {
-		int span = (int)(a[i].y >> 32 & 0xff);
-		int tl = (int32_t)a[i].x - (int32_t)a[i-1].x;
-		int ql = (int32_t)a[i].y - (int32_t)a[i-1].y;
-		r->blen += tl > ql? tl : ql;
-		r->mlen += tl > span && ql > span? span : tl < ql? tl : ql;
+// gen_regs, set_coor, set_parent, select_sub / sync_regs / set_sam_pri, est_err, filter_strand_retained and set_mapq are mm355_regs.h's,
+// instantiated for Reg with the host's libm (Mm355Libm).  Here: their scratch, and the steps only the CIGAR path has.
+struct RegsScratch {   // (kept per host thread) at least n entries each
+	std::vector<mm128> z; std::vector<uint64_t> cov; std::vector<int32_t> w, tmp; std::vector<uint32_t> mapq;
+	Mm355RegsScratch of(int n)
+	{
+		if ((int)z.size() < n) { z.resize(n); cov.resize(n); w.resize(n); tmp.resize(n); mapq.resize(n); }
+		return Mm355RegsScratch{ 0, z.data(), cov.data(), w.data(), tmp.data() };
 	}
-}
-
-static void reg_set_coor(Reg *r, int32_t qlen, const mm128 *a)
-{
-	int32_t k = r->as, q_span = (int32_t)(a[k].y >> 32 & 0xff);
-	r->rev = (uint32_t)(a[k].x >> 63);
-	r->rid = (int32_t)(a[k].x << 1 >> 33);
-	r->rs = (int32_t)a[k].x + 1 > q_span? (int32_t)a[k].x + 1 - q_span : 0;
-	r->re = (int32_t)a[k + r->cnt - 1].x + 1;
-	if (!r->rev) {
-		r->qs = (int32_t)a[k].y + 1 - q_span;
-		r->qe = (int32_t)a[k + r->cnt - 1].y + 1;
-	} else {
-		r->qs = qlen - ((int32_t)a[k + r->cnt - 1].y + 1);
-		r->qe = qlen - ((int32_t)a[k].y + 1 - q_span);
-	}
-	reg_fuzzy_len(r, a);
-}
-
-static void gen_regs(uint32_t hash, int qlen, ReadState &rs)
-{
-	const int n_u = (int)rs.u.size();
-	const mm128 *a = rs.a.data();
-	rs.regs.clear();
-	if (n_u == 0) return;
-	std::vector<mm128> z(n_u);
-	int k = 0;
-	for (int i = 0; i < n_u; ++i) {
-		uint32_t h = (uint32_t)hash64u((hash64u(a[k].x) + hash64u(a[k].y)) ^ hash);
-		z[i].x = rs.u[i] ^ h;
-		z[i].y = (uint64_t)k << 32 | (uint32_t)(int32_t)rs.u[i];
-		k += (int32_t)rs.u[i];
-	}
-	mm_radix_sort(z.data(), z.data() + n_u, mm_key_x());
-	for (int i = 0; i < n_u >> 1; ++i) std::swap(z[i], z[n_u - 1 - i]);
-	rs.regs.resize(n_u);
-	for (int i = 0; i < n_u; ++i) {
-		Reg *ri = &rs.regs[i];
-		*ri = Reg();
-		ri->id = i;
-		ri->parent = PARENT_UNSET;
-		ri->score = ri->score0 = (int32_t)(z[i].x >> 32);
-		ri->hash = (uint32_t)z[i].x;
-		ri->cnt = (int32_t)z[i].y;
-		ri->as = (int32_t)(z[i].y >> 32);
-		ri->div = -1.0f;
-		reg_set_coor(ri, qlen, a);
-	}
-}
+};
+static thread_local RegsScratch t_regs;
 
 static void split_reg(Reg *r, Reg *r2, int n, int qlen, const mm128 *a)
 {
@@ -522,131 +460,12 @@ static void split_reg(Reg *r, Reg *r2, int n, int qlen, const mm128 *a)
 	r2->cnt = r->cnt - n;
 	r2->score = (int32_t)(r->score * ((float)r2->cnt / r->cnt) + .499);
 	r2->as = r->as + n;
-	if (r->parent == r->id) r2->parent = PARENT_TMP_PRI;
-	reg_set_coor(r2, qlen, a);
+	if (r->parent == r->id) r2->parent = MM355_PARENT_TMP_PRI;
+	mm355r_set_coor(r2, qlen, a);
 	r->cnt -= r2->cnt;
 	r->score -= r2->score;
-	reg_set_coor(r, qlen, a);
+	mm355r_set_coor(r, qlen, a);
 	r->split |= 1, r2->split |= 2;
-}
-
-static void set_parent(float mask_level, int mask_len, int n, Reg *r, int sub_diff, int hard_mask_level)
-{
-	if (n <= 0) return;
-	for (int i = 0; i < n; ++i) r[i].id = i;
-	std::vector<uint64_t> cov(n);
-	std::vector<int> w(n);
-	int k = 1, j;
-	w[0] = 0, r[0].parent = 0;
-	for (int i = 1; i < n; ++i) {
-		Reg *ri = &r[i];
-		int si = ri->qs, ei = ri->qe, n_cov = 0, uncov_len = 0;
-		if (hard_mask_level) goto skip_uncov;
-		for (j = 0; j < k; ++j) {
-			Reg *rp = &r[w[j]];
-			int sj = rp->qs, ej = rp->qe;
-			if (ej <= si || sj >= ei) continue;
-			if (sj < si) sj = si;
-			if (ej > ei) ej = ei;
-			cov[n_cov++] = (uint64_t)sj << 32 | (uint32_t)ej;
-		}
-		if (n_cov == 0) {
-			goto set_parent_test;
-		} else {
-			int x = si;
-			mm_radix_sort(cov.data(), cov.data() + n_cov, mm_key_u64());
-			for (int jj = 0; jj < n_cov; ++jj) {
-				if ((int)(cov[jj] >> 32) > x) uncov_len += (int)(cov[jj] >> 32) - x;
-				x = (int32_t)cov[jj] > x? (int32_t)cov[jj] : x;
-			}
-			if (ei > x) uncov_len += ei - x;
-		}
-skip_uncov:
-		for (j = 0; j < k; ++j) {
-			Reg *rp = &r[w[j]];
-			int sj = rp->qs, ej = rp->qe, min, max, ol;
-			if (ej <= si || sj >= ei) continue;
-			min = ej - sj < ei - si? ej - sj : ei - si;
-			max = ej - sj > ei - si? ej - sj : ei - si;
-			ol = si < sj? (ei < sj? 0 : ei < ej? ei - sj : ej - sj) : (ej < si? 0 : ej < ei? ej - si : ei - si);
-			if ((float)ol / min - (float)uncov_len / max > mask_level && uncov_len <= mask_len) {
-				int cnt_sub = 0, sci = ri->score;
-				ri->parent = rp->parent;
-				rp->subsc = rp->subsc > sci? rp->subsc : sci;
-				if (ri->cnt >= rp->cnt) cnt_sub = 1;
-				if (rp->p && ri->p && (rp->rid != ri->rid || rp->rs != ri->rs || rp->re != ri->re || ol != min)) {
-					sci = ri->p->dp_max;
-					rp->p->dp_max2 = rp->p->dp_max2 > sci? rp->p->dp_max2 : sci;
-					if (rp->p->dp_max - ri->p->dp_max <= sub_diff) cnt_sub = 1;
-				}
-				if (cnt_sub) ++rp->n_sub;
-				break;
-			}
-		}
-set_parent_test:
-		if (j == k) w[k++] = i, ri->parent = i, ri->n_sub = 0;
-	}
-}
-
-static int set_sam_pri(int n, Reg *r)
-{
-	int n_pri = 0;
-	for (int i = 0; i < n; ++i)
-		if (r[i].id == r[i].parent) { ++n_pri; r[i].sam_pri = (n_pri == 1); }
-		else r[i].sam_pri = 0;
-	return n_pri;
-}
-
-static void sync_regs(int n_regs, Reg *regs)
-{
-	int max_id = -1;
-	if (n_regs <= 0) return;
-	for (int i = 0; i < n_regs; ++i) max_id = max_id > regs[i].id? max_id : regs[i].id;
-	int n_tmp = max_id + 1;
-	std::vector<int> tmp(n_tmp > 0? n_tmp : 1, -1);
-	for (int i = 0; i < n_regs; ++i) if (regs[i].id >= 0) tmp[regs[i].id] = i;
-	for (int i = 0; i < n_regs; ++i) {
-		Reg *r = &regs[i];
-		r->id = i;
-		if (r->parent == PARENT_TMP_PRI) r->parent = i;
-		else if (r->parent >= 0 && r->parent < n_tmp && tmp[r->parent] >= 0) r->parent = tmp[r->parent];
-		else r->parent = PARENT_UNSET;
-	}
-	set_sam_pri(n_regs, regs);
-}
-
-static void select_sub(float pri_ratio, int min_diff, int best_n, int check_strand, int min_strand_sc, int *n_, Reg *r)
-{
-	if (pri_ratio > 0.0f && *n_ > 0) {
-		int k = 0, n = *n_, n_2nd = 0;
-		for (int i = 0; i < n; ++i) {
-			int p = r[i].parent;
-			if (p == i || r[i].inv) {
-				r[k++] = r[i];
-			} else if ((r[i].score >= r[p].score * pri_ratio || r[i].score + min_diff >= r[p].score) && n_2nd < best_n) {
-				if (!(r[i].qs == r[p].qs && r[i].qe == r[p].qe && r[i].rid == r[p].rid && r[i].rs == r[p].rs && r[i].re == r[p].re))
-					r[k++] = r[i], ++n_2nd;
-				else if (r[i].p) delete r[i].p;
-			} else if (check_strand && n_2nd < best_n && r[i].score > min_strand_sc && r[p].rev != r[i].rev) {
-				r[i].strand_retained = 1;
-				r[k++] = r[i], ++n_2nd;
-			} else if (r[i].p) delete r[i].p;
-		}
-		if (k != n) sync_regs(k, r);
-		*n_ = k;
-	}
-}
-
-static int filter_strand_retained(int n_regs, Reg *r)
-{
-	int k = 0;
-	for (int i = 0; i < n_regs; ++i) {
-		int p = r[i].parent;
-		if (!r[i].strand_retained || r[i].div < r[p].div * 5.0f || r[i].div < 0.01f) {
-			if (k < i) r[k++] = r[i]; else ++k;
-		}
-	}
-	return k;
 }
 
 static void filter_regs(const mm355_mapopt_t *opt, int qlen, int *n_regs, Reg *regs)
@@ -700,106 +519,6 @@ static int squeeze_a(int n_regs, Reg *regs, mm128 *a)
 	return as;
 }
 
-static void set_inv_mapq(int n_regs, Reg *regs)
-{
-	int i, n_aux = 0;
-	if (n_regs < 3) return;
-	for (i = 0; i < n_regs; ++i) if (regs[i].inv) break;
-	if (i == n_regs) return;
-	std::vector<mm128> aux(n_regs);
-	for (i = 0; i < n_regs; ++i)
-		if (regs[i].parent == i || regs[i].parent < 0)
-			aux[n_aux].y = (uint64_t)i, aux[n_aux++].x = (uint64_t)(uint32_t)regs[i].rid << 32 | (uint32_t)regs[i].rs;
-	mm_radix_sort(aux.data(), aux.data() + n_aux, mm_key_x());
-	for (i = 1; i < n_aux - 1; ++i) {
-		Reg *inv = &regs[aux[i].y];
-		if (inv->inv) {
-			Reg *l = &regs[aux[i-1].y], *r = &regs[aux[i+1].y];
-			inv->mapq = l->mapq < r->mapq? l->mapq : r->mapq;
-		}
-	}
-}
-
-static void set_mapq(int n_regs, Reg *regs, int min_chain_sc, int match_sc, int rep_len)
-{
-	static const float q_coef = 40.0f;
-	int64_t sum_sc = 0;
-	float uniq_ratio;
-	if (n_regs == 0) return;
-	for (int i = 0; i < n_regs; ++i) if (regs[i].parent == regs[i].id) sum_sc += regs[i].score;
-	uniq_ratio = (float)sum_sc / (sum_sc + rep_len);
-	for (int i = 0; i < n_regs; ++i) {
-		Reg *r = &regs[i];
-		if (r->inv) {
-			r->mapq = 0;
-		} else if (r->parent == r->id) {
-			int mapq, subsc;
-			float pen_s1 = (r->score > 100? 1.0f : 0.01f * r->score) * uniq_ratio;
-			float pen_cm = r->cnt > 10? 1.0f : 0.1f * r->cnt;
-			pen_cm = pen_s1 < pen_cm? pen_s1 : pen_cm;
-			subsc = r->subsc > min_chain_sc? r->subsc : min_chain_sc;
-			if (r->p && r->p->dp_max2 > 0 && r->p->dp_max > 0) {
-				float identity = (float)r->mlen / r->blen;
-				float x = (float)r->p->dp_max2 * subsc / r->p->dp_max / r->score0;
-				mapq = (int)(identity * pen_cm * q_coef * (1.0f - x * x) * logf((float)r->p->dp_max / match_sc));
-				int mapq_alt = (int)(6.02f * identity * identity * (r->p->dp_max - r->p->dp_max2) / match_sc + .499f);
-				mapq = mapq < mapq_alt? mapq : mapq_alt;
-			} else {
-				float x = (float)subsc / r->score0;
-				if (r->p) {
-					float identity = (float)r->mlen / r->blen;
-					mapq = (int)(identity * pen_cm * q_coef * (1.0f - x) * logf((float)r->p->dp_max / match_sc));
-				} else mapq = (int)(pen_cm * q_coef * (1.0f - x) * logf(r->score));
-			}
-			mapq -= (int)(4.343f * logf(r->n_sub + 1) + .499f);
-			mapq = mapq > 0? mapq : 0;
-			r->mapq = mapq < 60? mapq : 60;
-			if (r->p && r->p->dp_max > r->p->dp_max2 && r->mapq == 0) r->mapq = 1;
-		} else r->mapq = 0;
-	}
-	set_inv_mapq(n_regs, regs);
-}
-
-static inline int32_t get_for_qpos(int32_t qlen, const mm128 *a)
-{
-	int32_t x = (int32_t)a->y, q_span = (int32_t)(a->y >> 32 & 0xff);
-	if (a->x >> 63) x = qlen - 1 - (x + 1 - q_span);
-	return x;
-}
-
-static void est_err(const mm355_index *mi, int qlen, int n_regs, Reg *regs, const mm128 *a, int32_t n, const uint64_t *mini_pos)
-{
-	uint64_t sum_k = 0;
-	if (n == 0) return;
-	for (int i = 0; i < n; ++i) sum_k += mini_pos[i] >> 32 & 0xff;
-	float avg_k = (float)sum_k / n;
-	for (int i = 0; i < n_regs; ++i) {
-		Reg *r = &regs[i];
-		int32_t st, en, j, k, n_match, n_tot, l_ref;
-		r->div = -1.0f;
-		if (r->cnt == 0) continue;
-		{   // get_mini_idx
-			int32_t x = get_for_qpos(qlen, r->rev? &a[r->as + r->cnt - 1] : &a[r->as]), L = 0, R = n - 1;
-			st = -1;
-			while (L <= R) {
-				int32_t m = (int32_t)(((uint64_t)L + R) >> 1), y = (int32_t)mini_pos[m];
-				if (y < x) L = m + 1; else if (y > x) R = m - 1; else { st = m; break; }
-			}
-		}
-		en = st;
-		if (st < 0) continue;
-		l_ref = (int32_t)mi->seq_len[r->rid];
-		for (k = 1, j = st + 1, n_match = 1; j < n && k < r->cnt; ++j) {
-			int32_t x = get_for_qpos(qlen, r->rev? &a[r->as + r->cnt - 1 - k] : &a[r->as + k]);
-			if (x == (int32_t)mini_pos[j]) ++k, en = j, ++n_match;
-		}
-		n_tot = en - st + 1;
-		if (r->qs > avg_k && r->rs > avg_k) ++n_tot;
-		if (qlen - r->qs > avg_k && l_ref - r->re > avg_k) ++n_tot;
-		r->div = n_match >= n_tot? 0.0f : (float)(1.0 - pow((double)n_match / n_tot, 1.0 / avg_k));
-	}
-}
-
 // ================================================================== stage 0 (MM_F_RMQ presets only: asm5/asm10/asm20)
 // U:map.c::mm_map_frag with MM_F_RMQ: the *primary* chainer is mg_lchain_rmq over all sorted anchors of the read (not
 // mg_lchain_dp).  Its AVL-tree walk is strictly sequential per read (tree shape decides ties), so it stays in this
@@ -815,9 +534,6 @@ void mm355_glue_chain_rmq(const mm355_index *mi, const mm355_mapopt_t *opt, Read
 void mm355_glue_regions(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, int rmq_state)
 {
 	const int qlen = rs.qlen;
-	uint32_t hash = rs.name_hash;   // X31(qname); 0 without a name (the L2 crate passes null)
-	hash ^= wang32((uint32_t)qlen) + wang32((uint32_t)opt->seed);
-	hash = wang32(hash);
 	const float pen_gap = (float)(opt->chain_gap_scale * 0.01 * mi->k), pen_skip = (float)(opt->chain_skip_scale * 0.01 * mi->k);
 	int n_regs0 = (int)rs.u.size();
 	{ ProfScope pf(PF_PRE_RMQ);
@@ -839,25 +555,18 @@ void mm355_glue_regions(const mm355_index *mi, const mm355_mapopt_t *opt, ReadSt
 		}
 	}
 	}
-	int n;
-	{ ProfScope pf(PF_PRE_REGS);
-	gen_regs(hash, qlen, rs);
-	n = (int)rs.regs.size();
-	if (!(opt->flag & MMF_ALL_CHAINS) && n > 0) {
-		set_parent(opt->mask_level, opt->mask_len, n, rs.regs.data(), opt->a * 2 + opt->b, (int)(opt->flag & MMF_HARD_MLEVEL));
-		select_sub(opt->pri_ratio, mi->k * 2, opt->best_n, 1, (int)(opt->max_gap * 0.8), &n, rs.regs.data());
-	}
-	}
-	{ ProfScope pf(PF_PRE_ESTERR);
-	est_err(mi, qlen, n, rs.regs.data(), rs.a.data(), (int32_t)rs.mini_pos.size(), rs.mini_pos.data());
-	}
-	n = filter_strand_retained(n, rs.regs.data());
-	rs.regs.resize(n);
+	ProfScope pf(PF_PRE_REGS);   // gen_regs .. est_err
+	const int n_u = (int)rs.u.size();
+	rs.regs.resize(n_u);
+	if (n_u == 0) return;
+	rs.regs.resize(mm355r_regions(mm355_regs_opt(opt, mi->k), mi->seq_len.data(), qlen, n_u, rs.u.data(), rs.a.data(), (int32_t)rs.mini_pos.size(),
+	                              rs.mini_pos.data(), rs.name_hash, t_regs.of(n_u), rs.regs.data()));   // name_hash: X31(qname); 0 without a name
 }
 
 void mm355_glue_pre_align(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, int rmq_state)
 {
 	mm355_glue_regions(mi, opt, rs, rmq_state);
+	rs.regs.resize(mm355r_filter_strand_retained((int)rs.regs.size(), rs.regs.data(), true));
 	const int qlen = rs.qlen, n = (int)rs.regs.size();
 	ProfScope pfc(PF_PRE_CODES);
 	// U:align.c::mm_align_skeleton prologue: query codes and anchor squeeze
@@ -898,7 +607,7 @@ static double tsc_per_us()
 }
 void mm355_prof_dump(int64_t n_reads)   // call while no worker is inside a section
 {
-	static const char *nm[PF_N] = { "pre:copy", "pre:rmq", "pre:regs", "pre:est_err", "pre:codes", "pre:squeeze", "task_prepare", "getseq", "test_zdrop", "add_cigar",
+	static const char *nm[PF_N] = { "pre:copy", "pre:rmq", "pre:regs", "pre:codes", "pre:squeeze", "task_prepare", "getseq", "test_zdrop", "add_cigar",
 	                                "update_extra", "task_run(total)", "align_step(total)", "finish", "dp:distribute", "dp:gather_build", "assemble", "x1:newExtra+getseq", "x2:fix_cigar", "x3:extra_loop", "x4:cs_md", "x5" };
 	if (!g_prof_on) return;
 	const double f = tsc_per_us(), nr = (double)(n_reads > 0? n_reads : 1);
@@ -1582,8 +1291,8 @@ static int align1_inv(const mm355_index *mi, const mm355_mapopt_t *opt, int read
 	*pending = false;
 	*r_inv = Reg();
 	if (!(r1->split & 1) || !(r2->split & 2)) return 0;
-	if (r1->id != r1->parent && r1->parent != PARENT_TMP_PRI) return 0;
-	if (r2->id != r2->parent && r2->parent != PARENT_TMP_PRI) return 0;
+	if (r1->id != r1->parent && r1->parent != MM355_PARENT_TMP_PRI) return 0;
+	if (r2->id != r2->parent && r2->parent != MM355_PARENT_TMP_PRI) return 0;
 	if (r1->rid != r2->rid || r1->rev != r2->rev) return 0;
 	ql = r1->rev? r1->qs - r2->qe : r2->qs - r1->qe;
 	tl = r2->rs - r1->re;
@@ -1616,7 +1325,7 @@ static int align1_inv(const mm355_index *mi, const mm355_mapopt_t *opt, int read
 	append_cigar(r_inv, ez.cigar, ez.n_cigar);
 	r_inv->p->dp_score = ez.max;
 	r_inv->id = -1;
-	r_inv->parent = PARENT_UNSET;
+	r_inv->parent = MM355_PARENT_UNSET;
 	r_inv->inv = 1;
 	r_inv->rev = !r1->rev;
 	r_inv->rid = r1->rid;
@@ -1777,12 +1486,16 @@ void mm355_glue_finish(const mm355_index *mi, const mm355_mapopt_t *opt, ReadSta
 	Reg *regs = rs.regs.data();
 	filter_regs(opt, rs.qlen, &n, regs);
 	hit_sort(&n, regs);
+	const Mm355RegsScratch s = t_regs.of(n);
+	uint32_t *mapq = t_regs.mapq.data();
 	if (!(opt->flag & MMF_ALL_CHAINS)) {
-		set_parent(opt->mask_level, opt->mask_len, n, regs, opt->a * 2 + opt->b, (int)(opt->flag & MMF_HARD_MLEVEL));
-		select_sub(opt->pri_ratio, mi->k * 2, opt->best_n, 0, (int)(opt->max_gap * 0.8), &n, regs);
-		set_sam_pri(n, regs);
+		mm355r_set_parent(opt->mask_level, opt->mask_len, n, regs, (int)(opt->flag & MMF_HARD_MLEVEL), s.cov, s.w, opt->a * 2 + opt->b);
+		n = mm355r_select_sub(opt->pri_ratio, mi->k * 2, opt->best_n, (int)(opt->max_gap * 0.8), n, regs, s.tmp, 0);
+		mm355r_set_sam_pri(n, regs);
 	}
-	set_mapq(n, regs, opt->min_chain_score, opt->a, rs.rep_len);
+	mm355r_set_mapq(n, regs, opt->min_chain_score, opt->a, rs.rep_len, Mm355Libm(), mapq);
+	for (int i = 0; i < n; ++i) regs[i].mapq = mapq[i];
+	mm355_set_inv_mapq(n, regs);
 	rs.regs.resize(n);
 	std::vector<uint8_t> q, t;
 	for (int i = 0; i < n; ++i) {
@@ -1813,19 +1526,16 @@ void mm355_glue_finish(const mm355_index *mi, const mm355_mapopt_t *opt, ReadSta
 // device's region stage (mm355_regs.h) does not take.
 void mm355_glue_chain_finish(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, std::vector<mm355_hit_t> &hits, std::vector<mm355_tags_t> *tags)
 {
-	const int n = (int)rs.regs.size();
-	set_mapq(n, rs.regs.data(), opt->min_chain_score, opt->a, rs.rep_len);
-	for (int i = 0; i < n; ++i) {
-		const Reg *r = &rs.regs[i];
-		mm355_hit_t h;
-		mm355r_hit(r, r->mapq, mi->seq_len.data(), &h);
-		hits.push_back(h);
-		if (tags) {
-			mm355_tags_t g;
-			mm355r_tags(r, rs.rep_len, &g);
-			tags->push_back(g);
-		}
-	}
+	const int n0 = (int)rs.regs.size();
+	const size_t h0 = hits.size(), t0 = tags? tags->size() : 0;
+	hits.resize(h0 + n0);
+	if (tags) tags->resize(t0 + n0);
+	t_regs.of(n0);
+	const int n = mm355r_finish(mm355_regs_opt(opt, mi->k), mi->seq_len.data(), rs.rep_len, n0, rs.regs.data(), Mm355Libm(), t_regs.mapq.data(),
+	                            hits.data() + h0, tags? tags->data() + t0 : 0);
+	rs.regs.resize(n);
+	hits.resize(h0 + n);
+	if (tags) tags->resize(t0 + n);
 }
 
 // ---- regions whose mm_update_extra walk / cs / MD were left to the device

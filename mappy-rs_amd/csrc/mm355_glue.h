@@ -23,16 +23,47 @@ struct Extra {
 
 struct ExtraLoc { int32_t strand, q_st, rid, t_st; };   // start of a region's query / target strings
 
-struct Reg {                // U:minimap.h::mm_reg1_t
+struct Reg {                // U:minimap.h::mm_reg1_t; the region type of the host's instantiation of mm355_regs.h (same field names as Mm355Reg)
 	int32_t id = 0, cnt = 0, rid = 0, score = 0;
 	int32_t qs = 0, qe = 0, rs = 0, re = 0;
 	int32_t parent = 0, subsc = 0, as = 0, mlen = 0, blen = 0, n_sub = 0, score0 = 0;
 	uint32_t mapq = 0, split = 0, rev = 0, inv = 0, sam_pri = 0, seg_split = 0, split_inv = 0, is_alt = 0, strand_retained = 0;
 	uint32_t hash = 0;
 	float div = -1.0f;
+	uint32_t div_unsure = 0;   // est_err's mark (mm355_regs.h); the host's pow decides, so nothing here reads it
 	Extra *p = 0;
 	int task = -1;          // alignment task bound to this region (-1: none yet)
 };
+
+// what extension adds to a region, as mm355_regs.h reaches it
+inline Extra *mm355r_extra(const Reg *r) { return r->p; }
+inline uint32_t mm355r_inv(const Reg *r) { return r->inv; }
+inline void mm355r_drop(Reg *r) { delete r->p; }
+// the host's sorts stay U:ksort.h's radix sorts (see mm355r_sort_for in mm355_regs.h)
+inline void mm355r_sort_for(const Reg*, mm128 *v, int n) { mm_radix_sort(v, v + n, mm_key_x()); }
+inline void mm355r_sort_for(const Reg*, uint64_t *v, int n) { mm_radix_sort(v, v + n, mm_key_u64()); }
+
+// U:hit.c::mm_set_inv_mapq, the close of mm_set_mapq after mm355r_set_mapq (here, not in mm355_glue.cpp, so that
+// tests/host_harness/regs_finish_host.cpp runs the product's)
+inline void mm355_set_inv_mapq(int n_regs, Reg *regs)
+{
+	int i, n_aux = 0;
+	if (n_regs < 3) return;
+	for (i = 0; i < n_regs; ++i) if (regs[i].inv) break;
+	if (i == n_regs) return;
+	std::vector<mm128> aux(n_regs);
+	for (i = 0; i < n_regs; ++i)
+		if (regs[i].parent == i || regs[i].parent < 0)
+			aux[n_aux].y = (uint64_t)i, aux[n_aux++].x = (uint64_t)(uint32_t)regs[i].rid << 32 | (uint32_t)regs[i].rs;
+	mm_radix_sort(aux.data(), aux.data() + n_aux, mm_key_x());
+	for (i = 1; i < n_aux - 1; ++i) {
+		Reg *inv = &regs[aux[i].y];
+		if (inv->inv) {
+			Reg *l = &regs[aux[i-1].y], *r = &regs[aux[i+1].y];
+			inv->mapq = l->mapq < r->mapq? l->mapq : r->mapq;
+		}
+	}
+}
 
 struct EzRes {              // U:ksw2.h::ksw_extz_t as returned by the DP kernel
 	int32_t max = 0, zdropped = 0, max_q = -1, max_t = -1, mqe = 0, mqe_t = -1, mte = 0, mte_q = -1, score = 0, reach_end = 0;
@@ -91,9 +122,10 @@ void mm355_glue_chain_rmq(const mm355_index *mi, const mm355_mapopt_t *opt, Read
 // here; MM355_RMQ_HOST: rs.a holds the chained anchors already sorted by x, mg_lchain_rmq runs here; -1: the stage did not run, the
 // rescue test, the sort and mg_lchain_rmq all run here (MM355_RMQ_ON_HOST=1)
 void mm355_glue_pre_align(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, int rmq_state);
-// its first half alone: re-chain (if triggered), gen_regs, set_parent + select_sub, est_err, filter_strand_retained -> rs.regs
+// its first half alone: re-chain (if triggered), gen_regs, set_parent + select_sub, est_err -> rs.regs (filter_strand_retained is the
+// caller's next step: mm355_glue_pre_align's, or mm355_glue_chain_finish's through mm355r_finish)
 void mm355_glue_regions(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, int rmq_state);
-// chain-only (no MM_F_CIGAR), after mm355_glue_regions: MAPQ from the chains and the hit records, in the order of rs.regs
+// chain-only (no MM_F_CIGAR), after mm355_glue_regions: filter_strand_retained, MAPQ from the chains and the hit records, in the order of rs.regs
 // (tags != 0: one mm355_tags_t per record as well, MM355_OUT_TAGS)
 void mm355_glue_chain_finish(const mm355_index *mi, const mm355_mapopt_t *opt, ReadState &rs, std::vector<mm355_hit_t> &hits, std::vector<mm355_tags_t> *tags = 0);
 // stage 2: advance the skeleton of one read as far as cached DP results allow; appends missing DP problems to `reqs`.

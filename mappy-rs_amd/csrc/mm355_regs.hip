@@ -102,10 +102,7 @@ int mm355_map_chain_only(mm355_ctx *c, const mm355_mapopt_t *mo, const std::vect
 			HIPCHK(hipMemcpy(c->logt.p, t.data(), t.size() * 4, hipMemcpyHostToDevice));
 			c->logt_ok = true;
 		}
-		Mm355RegsOpt o;
-		memset(&o, 0, sizeof(o));
-		o.flag = mo->flag; o.mask_level = mo->mask_level; o.pri_ratio = mo->pri_ratio; o.mask_len = mo->mask_len; o.best_n = mo->best_n;
-		o.min_diff = mi->k * 2; o.min_strand_sc = (int)(mo->max_gap * 0.8); o.min_chain_score = mo->min_chain_score; o.seed = mo->seed;
+		const Mm355RegsOpt o = mm355_regs_opt(mo, mi->k);
 		HIPCHK(hipMemcpyAsync(c->regs_in.p, rr, (size_t)n_reads * sizeof(RegsRead), hipMemcpyHostToDevice, c->st));
 		mm355_kt(c, KT_REGS, 0, c->st);
 #define K_REGS_ACTUALS (int)n_reads, c->regs_in.as<RegsRead>(), c->aoff.as<int64_t>(), c->roff.as<int64_t>(), c->u.as<uint64_t>(), c->a.as<mm128>(),    \
