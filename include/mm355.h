@@ -273,8 +273,9 @@ int mm355_map_batch_sam(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_re
  *          byte, high nibble first, a final odd base padded with 0; code = index in "=ACMGRSVTWYHKDBN" in either case, every other byte (U
  *          and u among them) 15.  On the reverse strand the byte is complemented first, as the line's is: U -> A -> 1
  *   QUAL   l_seq bytes: the quality byte minus 33 mod 256, last byte first on the reverse strand; 0xFF each for a read without quality
- *   tags   in the SAM line's order: NM ms AS nn tp cm s1 [s2] de [zd] [SA] [cs] [MD] rl [CG].  An i tag takes htslib's smallest type: C up to
- *          255, S up to 65535, else I; c down to -128, s down to -32768, else i.  tp is A.  de is f: the float32 of the double N / 10000.0, N
+ *   tags   in the SAM line's order: NM ms AS nn tp cm s1 [s2] de [zd] [SA] [cs] [MD] rl [CG], copied tags (mm355_bam_format_aux) between rl
+ *          and CG.  An i tag takes htslib's smallest type: C up to 255, S up to 65535, else I; c down to -128, s down to -32768, else i.
+ *          tp is A.  de is f: the float32 of the double N / 10000.0, N
  *          the integer behind the line's %.4f digits (0 for the printed "0", the sign kept) -- (float)strtod(text) without the text.  SA, cs
  *          and MD are Z with a NUL, SA's text the SAM line's
  * The unmapped record: refID -1, pos -1, mapq 0, bin 4680, flag 4, no CIGAR, SEQ and QUAL as given, rl.
@@ -319,6 +320,38 @@ int mm355_map_batch_bam_deflate(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int6
                                 const char *const *names, const char *const *quals, int flags, int sam_flags, int where, int level, mm355_text_t **out);
 int mm355_bgzf_deflate(mm355_ctx_t *ctx, const void *data, int64_t n, int where, int level, mm355_text_t **out);
 
+/* --- copied aux tags: the calls above with the tags a read brought along (MM / ML of a basecaller's BAM, RG, qs, ...), which the record
+ * carries through.  aux == NULL: the calls above, byte for byte (they are these with aux == NULL; aux_len and aux_mod are not read).
+ * Otherwise per read: aux[i] points to aux_len[i] bytes of BAM aux tags in the two groups mm355_bam_aux_split makes, the second -- the tags
+ * that index the bases of the read as sequenced, MM ML MN Mm Ml -- beginning at aux_mod[i]; aux[i] == NULL or aux_len[i] == 0: none.
+ * The rule, field by field behind the record's own tags: ... rl [copied tags] [CG], so CG stays the record's last, and
+ *   aux[i][0 .. aux_len[i])   on a record whose SEQ is the whole read: a row with FLAG & 0x900 == 0, every row under MM355_SAM_SOFTCLIP, and
+ *                             the unmapped record
+ *   aux[i][0 .. aux_mod[i])   on every other record: a hard-clipped supplementary (its SEQ is a slice: MM / ML would count bases that are
+ *                             not there) and a secondary with SEQ `*`
+ * The bytes are copied as given (mm355_bam.hip: a third bulk run of k_bam_bulk, 16-byte pieces from shifted source dwords; on the host a
+ * memcpy): their well-formedness is mm355_bam_aux_split's job -- the reader always runs it, the Python surface runs it on a caller's bytes.
+ * A record must not hold a tag twice, which is why the split drops the tags the writer emits itself.  The SAM specification gives tag order
+ * no meaning.  SAM and PAF text do not print copied tags: mm355_sam_format and mm355_paf_format have no such argument (a follow-up, as
+ * bgzip-compressed text is).  `level` as for the _deflate calls.
+ * MM355_EINVAL, before anything is allocated or launched, besides what mm355_bam_format refuses: aux != NULL with aux_len or aux_mod NULL;
+ * a negative aux_len[i]; aux[i] == NULL with aux_len[i] > 0; aux_mod[i] outside [0, aux_len[i]]; a record that would be longer than
+ * 2^32 + 3 bytes (block_size has 32 bits). */
+int mm355_bam_format_aux(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, const mm355_hits_t *hits, const char *const *qnames, const char *const *seqs,
+                         const int32_t *qlens, const char *const *quals, const int32_t *rep_len, const uint8_t *const *aux, const int32_t *aux_len,
+                         const int32_t *aux_mod, int sam_flags, int where, int level, mm355_text_t **out);
+int mm355_map_batch_bam_aux(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
+                            const char *const *names, const char *const *quals, const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod,
+                            int flags, int sam_flags, int where, int level, mm355_text_t **out);
+/* One bounded walk over a BAM aux block of n bytes (mm355_bamaux.h) and the split the calls above take.  A tag is two name bytes, a type
+ * and a value: A c C one byte, s S two, i I f four, d eight, Z H up to a NUL inside the block, B a subtype out of cCsSiIf, a uint32 count
+ * and count x size bytes inside the block (the product in 64 bits).  `keep` is "*" for every tag or two-letter names back to back
+ * ("MMMLMN").  `out` (n bytes) receives the kept tags in two groups, each in input order: first every kept tag but MM ML MN Mm Ml, then,
+ * from *mod_off, those; *n_out: the bytes written.  Always dropped, because the writer emits them itself: NM ms AS nn tp cm s1 s2 de dv
+ * zd SA cs MD rl CG.  The block is untrusted input.  MM355_EINVAL: an unknown type or subtype, a value or NUL past the end, a trailing
+ * partial tag, n < 0, a `keep` that is NULL, empty or of odd length (but "*"). */
+int mm355_bam_aux_split(const uint8_t *aux, int32_t n, const char *keep, uint8_t *out, int32_t *n_out, int32_t *mod_off);
+
 /* --- BGZF input: the inverse of mm355_bgzf_deflate.  `data` is n bytes of BGZF members (what mm355_bgzf_wrap / _deflate, bgzip or any BAM
  * writer produced): gzip members with the BC extra subfield (other subfields may stand in front of it; MTIME, XFL and OS are ignored), cdata of
  * at most 64 KB holding any RFC 1951 stream -- several deflate blocks, stored, fixed and dynamic ones, run symbols 16 - 18, codes of 15 bits,
@@ -358,7 +391,7 @@ void mm355_fastx_close(mm355_fastx_t *fx);
  * handle -- unaligned BAM as basecallers write it, or an aligned one.  The header is skipped; a record with flag & 0x900 (secondary,
  * supplementary) is skipped as `samtools fastq` skips it; the name is read_name, the bases come from the nibbles ("=ACMGRSVTWYHKDBN"), the
  * quality is qual + 33 (first byte 0xff: none); a record with flag 0x10 is reverse-complemented and its quality reversed, back to the read
- * as sequenced.  Aux tags are dropped.  MM355_EIO: block_size below 32, l_read_name 0, name + CIGAR + SEQ + QUAL beyond block_size, or a
+ * as sequenced.  Aux tags are dropped unless mm355_fastx_keep_aux asks for them.  MM355_EIO: block_size below 32, l_read_name 0, name + CIGAR + SEQ + QUAL beyond block_size, or a
  * stream that ends inside the header or a record.  The index builders do not read BAM: a BAM is no reference.
  * mm355_fastx_open_device: the same reader over a BGZF file (bgzip FASTQ / FASTA, BAM) whose members GPU `device` inflates
  * (k_bgzf_inflate).  The file is read in pieces of 32 MB of compressed bytes (MM355_INFLATE_PIECE=<bytes> overrides it; a piece always
@@ -368,6 +401,21 @@ void mm355_fastx_close(mm355_fastx_t *fx);
  * mm355_fastx_open.  MM355_EIO: unreadable.  MM355_ENODEV / ENOMEM / EHIP.  A malformed or refused member surfaces as MM355_EIO from
  * mm355_fastx_next when the reader gets there.  MM355_INFLATE_TIMES=1: a line per piece on stderr. */
 int mm355_fastx_open_device(const char *path, int keep_qual, int device, mm355_fastx_t **out);
+/* Aux tags of a BAM reads file.  mm355_fastx_keep_aux: `tags` as mm355_bam_aux_split's `keep`, or NULL for none (the default); it must come
+ * before the first mm355_fastx_next -- after it, and for a malformed `tags`, MM355_EINVAL.  On a stream that turns out not to be a BAM it has
+ * no effect.  The reader then reads a record's aux block (in chunks, never allocating by a length the stream has not delivered) instead of
+ * skipping it and runs it through mm355_bam_aux_split; a malformed block is MM355_EIO like every other malformed record.  A record with flag
+ * 0x10 keeps its aux verbatim: MM / ML are defined on the read as sequenced, which is what the reader restores.  Either byte source
+ * (mm355_fastx_open*, mm355_fastx_open_device) serves it.
+ * mm355_reads_aux: the blocks of a sub-batch, parallel to seqs[] -- aux[i] has (*aux_len)[i] bytes, its second group from (*aux_mod)[i], as
+ * mm355_bam_format_aux takes them; NULL (and NULL lengths) when nothing is kept or the stream is no BAM.  The reads own them.
+ * mm355_fastx_bam_rg: the @RG lines of the BAM's header text, verbatim and newline-terminated, *len their bytes (an RG:Z tag without its
+ * header line is no valid file: the writer of the output header needs them); NULL and 0 for a stream that is no BAM or a header without
+ * @RG.  It may be called before the first mm355_fastx_next and reads the header then; once records have been read it answers only if
+ * mm355_fastx_keep_aux was set (a reader that keeps nothing skips the header text as before).  The handle owns the string. */
+int mm355_fastx_keep_aux(mm355_fastx_t *fx, const char *tags);
+const uint8_t *const *mm355_reads_aux(const mm355_reads_t *r, const int32_t **aux_len, const int32_t **aux_mod);
+const char *mm355_fastx_bam_rg(mm355_fastx_t *fx, int64_t *len);
 
 /* --- per-stage entry points (same kernels as mm355_map_batch; used by the parity tests and
  * by bench.py to time one kernel with HIP events).  Outputs are caller-allocated host buffers. --- */

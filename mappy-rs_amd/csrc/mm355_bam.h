@@ -5,10 +5,11 @@
 //
 // A sink has binary primitives: ch(c) / u8(v) one byte, u16(v) and u32(v) little-endian, bytes(p, n) a run that exists in memory (names,
 // cs, MD), cigar(w, n) n packed CIGAR words as they are (len<<4 | op is BAM's own word), seq4(p, n, rev) n bases packed two per byte,
-// qual(p, n, rev) n quality bytes minus 33, fill(n) n bytes of 0xFF.  SEQ and QUAL are the bulk of a record: the device sinks only note
-// them down, and a kernel of its own packs them (mm355_bam.hip::k_bam_bulk).
+// qual(p, n, rev) n quality bytes minus 33, fill(n) n bytes of 0xFF, aux(p, n) n bytes of copied aux tags as they are.  SEQ, QUAL and the
+// copied tags are the bulk of a record: the device sinks only note them down, and a kernel of its own writes them (mm355_bam.hip::k_bam_bulk).
 #pragma once
 #include <zlib.h>
+#include <algorithm>
 #include "mm355_sam.h"
 
 // ---- BGZF with stored deflate blocks: the stream is cut every BGZF_PAYLOAD bytes (htslib's block payload); a block is the 18-byte gzip
@@ -165,6 +166,7 @@ template <typename S> MM_HD void bam_emit_record(S &s, const SamLine &L, int64_t
 		s.seq4(R.seq, R.qlen, false);
 		if (R.qual) s.qual(R.qual, R.qlen, false); else s.fill(R.qlen);
 		bam_tag_i(s, 'r', 'l', R.rep_len);
+		if (R.aux_len > 0) s.aux(R.aux, R.aux_len);
 		return;
 	}
 	const mm355_hit_t &h = R.rows[L.row]; const mm355_tags_t &t = R.tags[L.row];
@@ -208,6 +210,9 @@ template <typename S> MM_HD void bam_emit_record(S &s, const SamLine &L, int64_t
 	if (h.cs_len >= 0) bam_tag_z(s, 'c', 's', R.str + h.cs_off, h.cs_len);
 	if (h.md_len >= 0) bam_tag_z(s, 'M', 'D', R.str + h.md_off, h.md_len);
 	bam_tag_i(s, 'r', 'l', t.rep_len);
+	// the read's copied tags: all of them where SEQ is the whole read, otherwise those that do not index its bases (CG stays last)
+	const int32_t n_aux = (flag & 0x900) == 0 || soft? R.aux_len : R.aux_mod;
+	if (n_aux > 0) s.aux(R.aux, n_aux);
 	if (lng) {
 		s.ch('C'); s.ch('G'); s.ch('B'); s.ch('I'); s.u32((uint32_t)n_words);
 		if (clip5) s.u32(clip5 << 4 | clip_op);
@@ -228,6 +233,7 @@ struct BamCountSink {
 	MM_HD void seq4(const char *, int64_t l, bool) { n += (l + 1) / 2; }
 	MM_HD void qual(const char *, int64_t l, bool) { n += l; }
 	MM_HD void fill(int64_t l) { n += l; }
+	MM_HD void aux(const uint8_t *, int64_t l) { n += l; }
 };
 struct BamWriteSink {
 	unsigned char *p; int64_t n = 0;
@@ -248,6 +254,7 @@ struct BamWriteSink {
 	}
 	MM_HD void qual(const char *b, int64_t l, bool rev) { for (int64_t i = 0; i < l; ++i) p[n++] = (unsigned char)((unsigned char)(rev? b[l - 1 - i] : b[i]) - 33); }
 	MM_HD void fill(int64_t l) { for (int64_t i = 0; i < l; ++i) p[n++] = 0xff; }
+	MM_HD void aux(const uint8_t *b, int64_t l) { memcpy(p + n, b, (size_t)l); n += l; }
 };
 
 // ------------------------------------------------------------------ host side
@@ -293,10 +300,10 @@ inline void mm355_bgzf_frame_host(const char *data, int64_t n, char *out)
 // ---- the format as the shared writers see it (the host walk of mm355_sam.h; the device record writer, mm355_recdev.h)
 struct BamFmt {
 	typedef SamLine Line; typedef BamCountSink HostCount; typedef BamWriteSink HostWrite;
-	enum { RUNS = 5 };                                                 // runs of a record the wave copies: qname, the CIGAR words, cs, MD, the CG words
+	enum { RUNS = 5, TILE_RUNS = 3 };                                  // runs of a record the wave copies: qname, the CIGAR words, cs, MD, the CG words; runs in tiles: SEQ, QUAL, copied tags
 	static constexpr bool WAVE_CIGAR = false, TILED = true, FRAMED = true;   // the CIGAR is a run of words; SEQ and QUAL go in tiles; the result is the stream in BGZF blocks
-	// the fixed part of a record is 36 bytes, and block_size is 32 bits; records the upload takes (the tile table has two runs per record)
-	static constexpr int64_t MIN_RECORD = 36, MAX_RECORD = (int64_t)UINT32_MAX + 4, MAX_LINES = INT32_MAX / 2;
+	// the fixed part of a record is 36 bytes, and block_size is 32 bits; records the upload takes (the tile table has TILE_RUNS runs per record)
+	static constexpr int64_t MIN_RECORD = 36, MAX_RECORD = (int64_t)UINT32_MAX + 4, MAX_LINES = INT32_MAX / TILE_RUNS;
 	static MM_HD int64_t word_term(uint32_t w) { return bam_ref_len(w); }   // summed over a row's CIGAR words: the reference length (the bin needs it)
 	template <typename S> static MM_HD void emit(S &s, const SamLine &L, int64_t reflen, uint32_t block_size) { bam_emit_record(s, L, reflen, block_size); }
 	static int64_t n_lines(const mm355_hits_t *H, const int32_t *qlens, int sam_flags, int64_t i) { return mm355_sam_n_lines(H, qlens, sam_flags, i); }
@@ -307,9 +314,49 @@ struct BamFmt {
 
 // line_off counts in the unframed stream of records
 inline int mm355_bam_format_host(const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens, const char *const *quals,
-                                 const int32_t *rep_len, const PafNames &pn, int sam_flags, mm355_text_t **out)
+                                 const int32_t *rep_len, const PafNames &pn, int sam_flags, mm355_text_t **out, const RecAux &ax = RecAux())
 {
-	return mm355_rec_format_host<BamFmt>(H, qnames, seqs, qlens, quals, rep_len, pn, sam_flags, out);
+	return mm355_rec_format_host<BamFmt>(H, qnames, seqs, qlens, quals, rep_len, pn, sam_flags, out, ax);
+}
+
+// the same with copied aux tags, and what they add: a negative length, aux[i] == NULL with a positive length, aux_mod outside [0, aux_len],
+// and a record that would pass MAX_RECORD with them.  A sum of the read's lengths that is above any of its records decides for every
+// read a file will ever hold; only a read whose sum passes the limit is counted record by record (the counting sink reads lengths, never
+// a byte of a read or a tag), so the formatter's own counting pass is not run twice
+inline int mm355_bam_check_aux(const mm355_hits_t *H, const PafNames &pn, bool has_cigar, const char *const *qnames, const char *const *seqs, const int32_t *qlens,
+                               const int32_t *rep_len, int sam_flags, const RecAux &ax)
+{
+	if (int rc = mm355_bam_check(H, pn.n_seq, has_cigar, qnames, seqs, qlens, rep_len, sam_flags)) return rc;
+	if (ax.aux == 0) return 0;
+	if (ax.len == 0 || ax.mod == 0) return MM355_EINVAL;
+	bool any = false;
+	for (int64_t i = 0; i < H->n_reads; ++i) {
+		if (ax.len[i] < 0 || (ax.len[i] > 0 && ax.aux[i] == 0) || ax.mod[i] < 0 || ax.mod[i] > ax.len[i]) return MM355_EINVAL;
+		any = any || ax.len[i] > 0;
+	}
+	if (!any) return 0;
+	int64_t name_max = 0;
+	for (uint32_t k = 0; k < pn.n_seq; ++k) name_max = std::max<int64_t>(name_max, (int64_t)pn.names[k].size());
+	for (int64_t i = 0; i < H->n_reads; ++i) {
+		const int64_t nl = ax.len[i] > 0? mm355_sam_n_lines(H, qlens, sam_flags, i) : 0;
+		if (nl == 0) continue;
+		// above every record of the read: the fixed part, name and scalar tags (1024), SEQ and QUAL, the tags, and per row its words
+		// (twice: CG), its strings and its SA entry (a name and less than 128 bytes of numbers and letters)
+		int64_t bound = 1024 + 2 * (int64_t)qlens[i] + ax.len[i];
+		for (int64_t k = H->hit_off[i]; k < H->hit_off[i + 1]; ++k) {
+			const mm355_hit_t &h = H->hits[k];
+			bound += 8 * ((int64_t)h.n_cigar + 2) + (h.cs_len > 0? h.cs_len : 0) + (h.md_len > 0? h.md_len : 0) + name_max + 128;
+		}
+		if (bound <= BamFmt::MAX_RECORD) continue;
+		const SamNames nm(pn);
+		const SamRead R = mm355_sam_read_of(H, i, qnames, seqs, qlens, 0, rep_len, nm, sam_flags, ax);
+		for (int64_t j = 0; j < nl; ++j) {
+			BamCountSink cs;
+			bam_emit_record(cs, SamLine{ &R, R.n_rows? (int32_t)j : -1 }, 0, 0);   // (the reference length decides the bin, not the size)
+			if (cs.n > BamFmt::MAX_RECORD) return MM355_EINVAL;
+		}
+	}
+	return 0;
 }
 
 // mm355_bgzf_wrap on the host

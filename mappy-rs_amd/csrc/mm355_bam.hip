@@ -6,7 +6,9 @@
 //                 the destination.  SEQ: 32 bases from nine aligned source dwords shifted into place (reversed: mirrored, which swaps the
 //                 nibbles' order with the bytes'), each through the 256-entry code table in LDS (the reversed table is the code of the
 //                 complement, so U and u need no special case), two codes per byte.  QUAL: 16 bytes minus 33, mirrored on the reverse
-//                 strand; no quality: 0xFF.  The ragged head and tail of a tile, and the padded last byte of an odd SEQ, are byte stores.
+//                 strand; no quality: 0xFF.  Copied aux tags (mode 5): 16 bytes as they lie, from five aligned source dwords shifted into
+//                 place -- the blocks lie back to back in the upload and records start anywhere, so source and destination are misaligned
+//                 against each other in every way.  The ragged head and tail of a tile, and the padded last byte of an odd SEQ, are byte stores.
 // and the records, written into an unframed buffer, are framed by a pass of their own (one more read and write of the stream in HBM):
 //   k_bgzf_frame  one workgroup per BGZF block of the unframed stream: header, payload (aligned 16-byte stores from shifted source dwords),
 //                 CRC-32 by lanes with fixed-length chunks read 16 bytes at a time and a table in LDS (mm355_bam.h: bgzf_lane_crc, the combine
@@ -24,8 +26,8 @@
 #define BAM_TILE 4096         // output bytes of one k_bam_bulk block: 256 threads x 16 bytes
 
 MM_HD int64_t bam_tiles(int64_t n) { return (n + BAM_TILE - 1) / BAM_TILE; }
-// a SEQ / QUAL run of a record: len bases or bytes.  mode 0 / 1: bases packed two per byte, forwards / last base first and complemented;
-// 2 / 3: quality bytes minus 33, forwards / last byte first; 4: len bytes of 0xFF
+// a SEQ / QUAL / aux run of a record: len bases or bytes.  mode 0 / 1: bases packed two per byte, forwards / last base first and complemented;
+// 2 / 3: quality bytes minus 33, forwards / last byte first; 4: len bytes of 0xFF; 5: len bytes copied as they are (aux tags)
 MM_HD int64_t bam_bulk_bytes(const RecTileRun &r) { return r.mode < 2? ((int64_t)r.len + 1) / 2 : r.len; }
 MM_HD int64_t bam_run_tiles(const RecTileRun &r) { return bam_tiles(bam_bulk_bytes(r)); }
 
@@ -45,12 +47,12 @@ __global__ __launch_bounds__(256) void k_bam_bulk(const RecTileRun *bulk, const 
 	code[0][threadIdx.x] = bam_code((unsigned char)threadIdx.x);
 	code[1][threadIdx.x] = bam_code(sam_comp((unsigned char)threadIdx.x));
 	int64_t t;
-	const RecTileRun r = rec_tile_run(bulk, tile_off, n_lines, blockIdx.x, bam_run_tiles, &t);
+	const RecTileRun r = rec_tile_run<BamFmt::TILE_RUNS>(bulk, tile_off, n_lines, blockIdx.x, bam_run_tiles, &t);
 	__syncthreads();
 	const int64_t nb = bam_bulk_bytes(r), n = r.len;
 	const int64_t o0 = t * BAM_TILE, o1 = o0 + BAM_TILE < nb? o0 + BAM_TILE : nb;   // this tile: bytes [o0, o1) of the run
 	if (t < 0 || o0 >= o1) return;
-	const bool rev = (r.mode & 1) != 0;
+	const bool rev = r.mode < 4 && (r.mode & 1) != 0;
 	const unsigned char *cd = code[rev? 1 : 0];
 	const unsigned char *src = (const unsigned char*)r.src;
 	char *dst = text + r.dst;
@@ -61,6 +63,7 @@ __global__ __launch_bounds__(256) void k_bam_bulk(const RecTileRun *bulk, const 
 		if (c >= d0 && c + 16 <= d1 && (r.mode >= 2 || 2 * (oc + 16) <= n)) {
 			uint32_t v[4];
 			if (r.mode == 4) v[0] = v[1] = v[2] = v[3] = 0xffffffffu;
+			else if (r.mode == 5) sam_load16(r.src, oc, v);
 			else if (r.mode >= 2) {
 				sam_load16(r.src, rev? n - 16 - oc : oc, v);
 				if (rev) sam_mirror16(v);
@@ -83,6 +86,7 @@ __global__ __launch_bounds__(256) void k_bam_bulk(const RecTileRun *bulk, const 
 				const int64_t o = (int64_t)(a - (uintptr_t)dst);
 				unsigned char x;
 				if (r.mode == 4) x = 0xff;
+				else if (r.mode == 5) x = src[o];
 				else if (r.mode >= 2) x = (unsigned char)(src[rev? n - 1 - o : o] - 33);
 				else {
 					const int64_t i = 2 * o;
@@ -281,15 +285,17 @@ static bool bam_times_on() { const char *te = getenv("MM355_BAM_TIMES"); return 
 
 // BamFmt as the device writes it
 struct BamDevFmt : BamFmt {
+	typedef RecDev Dev;
 	struct Count : BamCountSink {
 		int64_t tiles = 0;
 		__device__ explicit Count(int64_t) {}
 		__device__ void seq4(const char *, int64_t l, bool) { n += (l + 1) / 2; tiles += bam_tiles((l + 1) / 2); }
 		__device__ void qual(const char *, int64_t l, bool) { n += l; tiles += bam_tiles(l); }
 		__device__ void fill(int64_t l) { n += l; tiles += bam_tiles(l); }
+		__device__ void aux(const uint8_t *, int64_t l) { n += l; tiles += bam_tiles(l); }
 	};
-	struct Write : RecWrite<RUNS> {
-		using RecWrite<RUNS>::RecWrite;
+	struct Write : RecWrite<RUNS, TILE_RUNS> {
+		using RecWrite<RUNS, TILE_RUNS>::RecWrite;
 		__device__ void u8(uint32_t v) { p[n++] = (char)v; }
 		__device__ void u16(uint32_t v) { u8(v & 0xff); u8(v >> 8 & 0xff); }
 		__device__ void u32(uint32_t v) { u16(v & 0xffff); u16(v >> 16); }
@@ -297,18 +303,30 @@ struct BamDevFmt : BamFmt {
 		__device__ void seq4(const char *b, int64_t l, bool rev) { note(b, l, rev? 1 : 0); n += (l + 1) / 2; }
 		__device__ void qual(const char *b, int64_t l, bool rev) { note(b, l, rev? 3 : 2); n += l; }
 		__device__ void fill(int64_t l) { note(0, l, 4); n += l; }
+		__device__ void aux(const uint8_t *b, int64_t l) { note((const char*)b, l, 5); n += l; }
 	};
-	// MM355_BAM_TIMES=1 (tools/bam_bench.py): one line on stderr with the framing kernel's time between two events
+	// MM355_BAM_TIMES=1 (tools/bam_bench.py, tools/aux_bench.py): one line on stderr with the framing kernel's time between two events and, at its end, k_bam_bulk's
 	static constexpr const char *TIMES_ENV = "MM355_BAM_TIMES";
-	static int bulk(mm355_ctx *c, const RecCall &k, const RecTileRun *runs, const int64_t *tile_off)
+	static int bulk(mm355_ctx *c, RecCall &k, const RecTileRun *runs, const int64_t *tile_off)
 	{
+		// timed: a pair of events of the call's own around the kernel (the framing step uses the context's two); finish() reads and frees them
+		const bool timed = k.times && hipEventCreate(&k.bulk_ev[0]) == hipSuccess && hipEventCreate(&k.bulk_ev[1]) == hipSuccess;
+		if (timed) (void)hipEventRecord(k.bulk_ev[0], c->st);
 		if (k.n_tiles > 0) {
 			hipLaunchKernelGGL(k_bam_bulk, dim3((unsigned)k.n_tiles), dim3(256), 0, c->st, runs, tile_off, k.n_lines, (char*)c->rec_text.p);
 			HIPCHK(hipGetLastError());
 		}
+		if (timed) (void)hipEventRecord(k.bulk_ev[1], c->st);
 		return 0;
 	}
 	static int finish(mm355_ctx *c, RecCall &k, const int64_t *d_lo, mm355_text_t **out)
+	{
+		double b_us = 0;
+		const int rc = finish_1(c, k, d_lo, out, &b_us);
+		for (hipEvent_t &e : k.bulk_ev) if (e) { (void)hipEventDestroy(e); e = 0; }
+		return rc;
+	}
+	static int finish_1(mm355_ctx *c, RecCall &k, const int64_t *d_lo, mm355_text_t **out, double *b_us)
 	{
 		double k_us = 0, d_us = 0;
 		int64_t n_out = bgzf_size(k.n_text), n_stored = 0;
@@ -319,14 +337,18 @@ struct BamDevFmt : BamFmt {
 		hipError_t e = hipMemcpyAsync(T->line_off, d_lo, (size_t)(k.n_reads + 1) * 8, hipMemcpyDeviceToHost, c->st);
 		int rc = e != hipSuccess? MM355_EHIP : c->bgzf_level? bam_blocks_back(c, n_out, T->text) : bam_frame_device(c, k.n_text, T->text, k.times, &k_us);
 		if (rc) { fprintf(stderr, "[mm355] error %d in the BAM writer (%s)\n", rc, hipGetErrorString(e)); mm355_free_text_host(T); return rc; }
+		if (k.times && k.bulk_ev[1]) { float ms = 0; (void)hipEventElapsedTime(&ms, k.bulk_ev[0], k.bulk_ev[1]); *b_us = (double)ms * 1e3; }   // (the stream has been waited for)
 		if (k.times && c->bgzf_level) bam_deflate_times("records", k.n_text, n_out, n_stored, d_us, true);
 		else if (k.times)
-			fprintf(stderr, "[mm355] bam_times records %lld stream_bytes %lld blocks %lld tiles %lld pack_ms %.3f k_bgzf_frame_us %.1f total_ms %.3f\n", (long long)k.n_lines,
-			        (long long)k.n_text, (long long)bgzf_blocks(k.n_text), (long long)k.n_tiles, k.t_packed - k.t_begin, k_us, mm355_now_ms() - k.t_begin);
+			fprintf(stderr, "[mm355] bam_times records %lld stream_bytes %lld blocks %lld tiles %lld pack_ms %.3f k_bgzf_frame_us %.1f total_ms %.3f k_bam_bulk_us %.1f\n", (long long)k.n_lines,
+			        (long long)k.n_text, (long long)bgzf_blocks(k.n_text), (long long)k.n_tiles, k.t_packed - k.t_begin, k_us, mm355_now_ms() - k.t_begin, *b_us);
 		*out = T;
 		return 0;
 	}
 };
+
+// BamDevFmt for a call with copied tags: the kernels' argument carries them
+struct BamAuxDevFmt : BamDevFmt { typedef RecDevAux Dev; };
 
 // MM355_PAF_AUTO for BAM: the device formatter from this many hits on.  Measured with tools/bam_bench.py (profiles/bam_file.json, format_sweep:
 // ms_format of the two formatters on the hits of 16 .. 9216 reads, map-ont with cs, reads of N50 8 kb with qualities): the host is ahead at 16
@@ -339,47 +361,65 @@ struct BamDeflateFmt : BamFmt {
 	static int64_t frame_host(const char *raw, int64_t n, char *out) { return mm355_bgzf_deflate_host(raw, n, out); }
 };
 
-extern "C" int mm355_bam_format_deflate(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs,
-                                        const int32_t *qlens, const char *const *quals, const int32_t *rep_len, int sam_flags, int where, int level, mm355_text_t **out)
+extern "C" int mm355_bam_format_aux(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs,
+                                    const int32_t *qlens, const char *const *quals, const int32_t *rep_len, const uint8_t *const *aux, const int32_t *aux_len,
+                                    const int32_t *aux_mod, int sam_flags, int where, int level, mm355_text_t **out)
 {
 	if (out == 0) return MM355_EINVAL;
 	*out = 0;
 	if (c == 0 || mo == 0 || H == 0 || where < MM355_PAF_AUTO || where > MM355_PAF_DEVICE || level < 0 || level > 1) return MM355_EINVAL;
 	if (c->mi == 0) return MM355_ENOIDX;
-	if (int rc = mm355_bam_check(H, c->mi->n_seq, (mo->flag & MMF_CIGAR) != 0, qnames, seqs, qlens, rep_len, sam_flags)) return rc;
 	const PafNames nm = { c->mi->names.data(), c->mi->n_seq };
+	RecAux ax;
+	if (aux) { ax.aux = aux; ax.len = aux_len; ax.mod = aux_mod; }
+	if (int rc = mm355_bam_check_aux(H, nm, (mo->flag & MMF_CIGAR) != 0, qnames, seqs, qlens, rep_len, sam_flags, ax)) return rc;
 	c->bgzf_level = level;
 	return rec_format_where(where, H->n_hits, "MM355_BAM_MIN_HITS", MM355_BAM_MIN_HITS_DEFAULT,
-	                        [&] { return level? mm355_rec_format_host<BamDeflateFmt>(H, qnames, seqs, qlens, quals, rep_len, nm, sam_flags, out)
-	                                          : mm355_bam_format_host(H, qnames, seqs, qlens, quals, rep_len, nm, sam_flags, out); },
-	                        [&] { return rec_format_device<BamDevFmt>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out); }, out);
+	                        [&] { return level? mm355_rec_format_host<BamDeflateFmt>(H, qnames, seqs, qlens, quals, rep_len, nm, sam_flags, out, ax)
+	                                          : mm355_bam_format_host(H, qnames, seqs, qlens, quals, rep_len, nm, sam_flags, out, ax); },
+	                        [&] { return ax.aux? rec_format_device<BamAuxDevFmt>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out, ax)
+	                                           : rec_format_device<BamDevFmt>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out); }, out);
+}
+
+extern "C" int mm355_bam_format_deflate(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs,
+                                        const int32_t *qlens, const char *const *quals, const int32_t *rep_len, int sam_flags, int where, int level, mm355_text_t **out)
+{
+	return mm355_bam_format_aux(c, mo, H, qnames, seqs, qlens, quals, rep_len, 0, 0, 0, sam_flags, where, level, out);
 }
 
 extern "C" int mm355_bam_format(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs,
                                 const int32_t *qlens, const char *const *quals, const int32_t *rep_len, int sam_flags, int where, mm355_text_t **out)
 {
-	return mm355_bam_format_deflate(c, mo, H, qnames, seqs, qlens, quals, rep_len, sam_flags, where, 0, out);
+	return mm355_bam_format_aux(c, mo, H, qnames, seqs, qlens, quals, rep_len, 0, 0, 0, sam_flags, where, 0, out);
 }
 
-static int mm355_bam_format_1(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens,
-                              const char *const *quals, const int32_t *rep_len, int sam_flags, int where, mm355_text_t **out)
+// rec_map_batch with the tags the format call takes besides
+extern "C" int mm355_map_batch_bam_aux(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
+                                       const char *const *names, const char *const *quals, const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod,
+                                       int flags, int sam_flags, int where, int level, mm355_text_t **out)
 {
-	return mm355_bam_format_deflate(c, mo, H, qnames, seqs, qlens, quals, rep_len, sam_flags, where, 1, out);
+	if (out == 0) return MM355_EINVAL;
+	*out = 0;
+	if (level < 0 || level > 1 || (aux && (aux_len == 0 || aux_mod == 0))) return MM355_EINVAL;   // (before anything is mapped)
+	if (mo && !(mo->flag & MMF_CIGAR)) return MM355_EINVAL;
+	mm355_hits_t *H = 0; const int32_t *rep_len = 0;
+	int rc = mm355_map_batch_rl(c, mo, n_reads, seqs, lens, names, flags | MM355_OUT_TAGS, &H, &rep_len);
+	if (rc) return rc;
+	rc = mm355_bam_format_aux(c, mo, H, names, seqs, lens, quals, rep_len, aux, aux_len, aux_mod, sam_flags, where, level, out);
+	mm355_free_hits(H);
+	return rc;
 }
 
 extern "C" int mm355_map_batch_bam_deflate(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
                                            const char *const *names, const char *const *quals, int flags, int sam_flags, int where, int level, mm355_text_t **out)
 {
-	if (out == 0) return MM355_EINVAL;
-	*out = 0;
-	if (level < 0 || level > 1) return MM355_EINVAL;           // (before anything is mapped)
-	return rec_map_batch(level? mm355_bam_format_1 : mm355_bam_format, c, mo, n_reads, seqs, lens, names, quals, flags, sam_flags, where, out);
+	return mm355_map_batch_bam_aux(c, mo, n_reads, seqs, lens, names, quals, 0, 0, 0, flags, sam_flags, where, level, out);
 }
 
 extern "C" int mm355_map_batch_bam(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
                                    const char *const *names, const char *const *quals, int flags, int sam_flags, int where, mm355_text_t **out)
 {
-	return mm355_map_batch_bam_deflate(c, mo, n_reads, seqs, lens, names, quals, flags, sam_flags, where, 0, out);
+	return mm355_map_batch_bam_aux(c, mo, n_reads, seqs, lens, names, quals, 0, 0, 0, flags, sam_flags, where, 0, out);
 }
 
 extern "C" int mm355_bgzf_deflate(mm355_ctx_t *c, const void *data, int64_t n, int where, int level, mm355_text_t **out)

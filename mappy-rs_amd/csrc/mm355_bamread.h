@@ -4,7 +4,9 @@
 //   the BAM loop a stream that begins "BAM\1" is a BAM file (unaligned, as basecallers write it, or aligned): the header is skipped, and every
 //                record but the secondary and supplementary ones (flag & 0x900, as `samtools fastq`) gives a read -- the name, the bases from
 //                the nibbles, the quality + 33 (first byte 0xff: none), a record with flag 0x10 turned back to the read as sequenced.  Aux
-//                tags are dropped.
+//                tags are dropped, or (mm355_fastx_keep_aux) read in chunks and filtered by mm355_bamaux.h::bam_aux_split; a 0x10 record keeps
+//                its aux verbatim: MM / ML are defined on the read as sequenced, which is what the reader restores.  The @RG lines of the
+//                header text are kept for the writer of the output header.
 // The loop parses untrusted input: it takes a record's fields only as far as block_size allows, never allocates by a length the stream has
 // not delivered, and answers MM355_EIO for a block_size below 32, an l_read_name of 0, fields that exceed block_size and a stream that ends
 // inside the header or a record.  Plain C++ (tests/host_harness/inflate_host.cpp builds it with g++ alone).
@@ -12,6 +14,7 @@
 #include <stdint.h>
 #include <string>
 #include "mm355_sam.h"
+#include "mm355_bamaux.h"
 
 struct ByteSource {
 	virtual ~ByteSource() {}
@@ -24,12 +27,44 @@ template <typename R> static inline int bam_need(R &r, void *dst, size_t n) { re
 
 static inline uint32_t bam_le32(const unsigned char *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 
-// the header, magic included: l_text, text, n_ref, per reference l_name, name, l_ref
-template <typename R> static inline int bam_read_header(R &r)
+// the @RG lines of a header text that arrives in pieces: a line is kept from its first byte on while it can still begin "@RG\t", the text
+// ends at its first NUL, and a last line without a newline gets one
+struct BamRgFilter {
+	std::string *rg; std::string line; bool live = true, done = false;
+	explicit BamRgFilter(std::string *rg_) : rg(rg_) {}
+	void end_line() { if (live && line.size() >= 4) { *rg += line; *rg += '\n'; } line.clear(); live = true; }
+	void feed(const unsigned char *p, size_t n)
+	{
+		for (size_t i = 0; i < n && !done; ++i) {
+			if (p[i] == 0) { done = true; break; }
+			if (p[i] == '\n') { end_line(); continue; }
+			if (!live) continue;
+			if (line.size() < 4 && (char)p[i] != "@RG\t"[line.size()]) { live = false; line.clear(); continue; }
+			line += (char)p[i];
+		}
+	}
+	void finish() { if (!line.empty()) end_line(); }
+};
+
+// the header, magic included: l_text, text, n_ref, per reference l_name, name, l_ref.  rg != 0: the text's @RG lines are appended to it
+template <typename R> static inline int bam_read_header(R &r, std::string *rg)
 {
 	unsigned char w[8];
 	if (bam_need(r, w, 8) || memcmp(w, "BAM\1", 4) != 0) return MM355_EIO;
-	if (bam_le32(w + 4) > (uint32_t)INT32_MAX || bam_need(r, 0, bam_le32(w + 4)) || bam_need(r, w, 4)) return MM355_EIO;
+	if (bam_le32(w + 4) > (uint32_t)INT32_MAX) return MM355_EIO;
+	if (rg == 0) { if (bam_need(r, 0, bam_le32(w + 4))) return MM355_EIO; }
+	else {
+		BamRgFilter flt(rg);
+		unsigned char chunk[4096];
+		for (uint64_t left = bam_le32(w + 4); left > 0; ) {    // (in chunks: what is kept has been delivered)
+			const size_t k = left < sizeof(chunk)? (size_t)left : sizeof(chunk);
+			if (bam_need(r, chunk, k)) return MM355_EIO;
+			flt.feed(chunk, k);
+			left -= k;
+		}
+		flt.finish();
+	}
+	if (bam_need(r, w, 4)) return MM355_EIO;
 	const uint32_t n_ref = bam_le32(w);
 	if (n_ref > (uint32_t)INT32_MAX) return MM355_EIO;
 	for (uint32_t i = 0; i < n_ref; ++i) {
@@ -37,6 +72,7 @@ template <typename R> static inline int bam_read_header(R &r)
 	}
 	return 0;
 }
+template <typename R> static inline int bam_read_header(R &r) { return bam_read_header(r, (std::string*)0); }
 
 MM_HD char bam_base(uint32_t code)
 {
@@ -46,8 +82,11 @@ MM_HD char bam_base(uint32_t code)
 	}
 }
 
-// The next read: 1, the name set, the bases APPENDED to seq, qual set (*has_qual: the record has one); 0 at the end of the stream; MM355_EIO
-template <typename R> static inline int bam_read_record(R &r, std::string &name, std::string &seq, std::string &qual, bool *has_qual)
+// The next read: 1, the name set, the bases APPENDED to seq, qual set (*has_qual: the record has one); 0 at the end of the stream; MM355_EIO.
+// keep != 0 (a string bam_aux_keep_ok accepts): the record's aux block through bam_aux_split into aux, *aux_mod the offset of its second
+// group; a malformed block is MM355_EIO like every other malformed record
+template <typename R> static inline int bam_read_record(R &r, std::string &name, std::string &seq, std::string &qual, bool *has_qual, const char *keep, std::string &aux,
+                                                        int32_t *aux_mod)
 {
 	for (;;) {
 		unsigned char f[36];
@@ -85,7 +124,22 @@ template <typename R> static inline int bam_read_record(R &r, std::string &name,
 			if (*has_qual) for (uint64_t i = 0; i < k; ++i) qual.push_back((char)(chunk[i] + 33));
 			done += k;
 		}
-		if (bam_need(r, 0, (size_t)(block_size - 32 - fields))) return MM355_EIO;
+		const uint64_t n_aux = block_size - 32 - fields;
+		if (keep == 0) { if (bam_need(r, 0, (size_t)n_aux)) return MM355_EIO; }
+		else {
+			if (n_aux > (uint64_t)INT32_MAX) return MM355_EIO;
+			std::string raw;
+			for (uint64_t done = 0; done < n_aux; ) {          // (in chunks, as the bases)
+				const uint64_t k = n_aux - done < sizeof(chunk)? n_aux - done : sizeof(chunk);
+				if (bam_need(r, chunk, (size_t)k)) return MM355_EIO;
+				raw.append((const char*)chunk, (size_t)k);
+				done += k;
+			}
+			aux.resize(raw.size());
+			int32_t n_out = 0;
+			if (bam_aux_split((const uint8_t*)raw.data(), (int32_t)raw.size(), keep, (uint8_t*)&aux[0], &n_out, aux_mod)) return MM355_EIO;
+			aux.resize((size_t)n_out);
+		}
 		if (rev) {
 			for (size_t i = start, j = seq.size(); i < j; ) {
 				--j;
@@ -97,6 +151,12 @@ template <typename R> static inline int bam_read_record(R &r, std::string &name,
 		}
 		return 1;
 	}
+}
+
+template <typename R> static inline int bam_read_record(R &r, std::string &name, std::string &seq, std::string &qual, bool *has_qual)
+{
+	std::string aux; int32_t mod = 0;
+	return bam_read_record(r, name, seq, qual, has_qual, (const char*)0, aux, &mod);
 }
 
 // a streaming reader of read sets (mm355_fastx_t) over a source it takes over: mm355_fastx_next, mm355_fastx_close as for mm355_fastx_open

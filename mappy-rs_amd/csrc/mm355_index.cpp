@@ -308,6 +308,9 @@ struct mm355_fastx {
 	std::string held_name, held_seq; bool held = false; int err = 0;
 	// mm355_fastx_open_qual: the quality of the record fastx_record has just returned (has_qual: a FASTQ record with a '+' line), and the held record's
 	bool keep_qual = false, has_qual = false, held_has_qual = false; std::string qual, held_qual;
+	// mm355_fastx_keep_aux: the tags to keep from a BAM's records (empty: none), the aux of the record reads_record has just returned as
+	// bam_aux_split left it, and the held record's; started: mm355_fastx_next has been called.  rg: the @RG lines of a BAM's header text
+	std::string keep_aux, aux, held_aux, rg; int32_t aux_mod = 0, held_aux_mod = 0; bool started = false;
 	~mm355_fastx() { delete src; }
 };
 
@@ -396,7 +399,9 @@ struct FastxTake {
 };
 
 // fastx_record for the streaming reader: a stream that begins "BAM\1" gives its records as reads (fx->qual, fx->has_qual: the record's quality)
-static int reads_record(mm355_fastx *fx, std::string &name, std::string &seq)
+// the stream's first bytes looked at and, for a BAM, its header read: 0, or MM355_EIO (fx->is_bam says which loop reads the records)
+// (want_rg: the header text goes through the @RG filter; otherwise it is skipped as before)
+static int reads_begin(mm355_fastx *fx, bool want_rg)
 {
 	if (!fx->sniffed) {
 		fx->sniffed = true;
@@ -408,13 +413,20 @@ static int reads_record(mm355_fastx *fx, std::string &name, std::string &seq)
 		}
 		fx->is_bam = fx->end >= 4 && memcmp(fx->buf.data(), "BAM\1", 4) == 0;
 	}
-	if (!fx->is_bam) return fastx_record(fx, name, seq);
-	FastxTake t = { fx };
-	if (!fx->header_done) {
-		if (bam_read_header(t)) return MM355_EIO;
+	if (fx->is_bam && !fx->header_done) {
+		FastxTake t = { fx };
+		if (bam_read_header(t, want_rg? &fx->rg : (std::string*)0)) return MM355_EIO;
 		fx->header_done = true;
 	}
-	return bam_read_record(t, name, seq, fx->qual, &fx->has_qual);
+	return 0;
+}
+
+static int reads_record(mm355_fastx *fx, std::string &name, std::string &seq)
+{
+	if (reads_begin(fx, !fx->keep_aux.empty())) return MM355_EIO;
+	if (!fx->is_bam) return fastx_record(fx, name, seq);
+	FastxTake t = { fx };
+	return bam_read_record(t, name, seq, fx->qual, &fx->has_qual, fx->keep_aux.empty()? (const char*)0 : fx->keep_aux.c_str(), fx->aux, &fx->aux_mod);
 }
 
 static bool parse_fastx(const char *path, std::vector<std::string> &names, std::vector<std::string> &seqs)
@@ -455,6 +467,28 @@ extern "C" int mm355_fastx_open_qual(const char *path, mm355_fastx_t **out)
 
 extern "C" void mm355_fastx_close(mm355_fastx_t *fx) { delete fx; }
 
+extern "C" int mm355_fastx_keep_aux(mm355_fastx_t *fx, const char *tags)
+{
+	if (fx == 0 || fx->started || (tags && !bam_aux_keep_ok(tags))) return MM355_EINVAL;
+	fx->keep_aux = tags? tags : "";
+	return 0;
+}
+
+extern "C" const char *mm355_fastx_bam_rg(mm355_fastx_t *fx, int64_t *len)
+{
+	if (len) *len = 0;
+	if (fx == 0 || fx->err) return 0;
+	if (reads_begin(fx, true)) { fx->err = MM355_EIO; return 0; }    // (mm355_fastx_next reports it)
+	if (!fx->is_bam || fx->rg.empty()) return 0;
+	if (len) *len = (int64_t)fx->rg.size();
+	return fx->rg.c_str();
+}
+
+extern "C" int mm355_bam_aux_split(const uint8_t *aux, int32_t n, const char *keep, uint8_t *out, int32_t *n_out, int32_t *mod_off)
+{
+	return bam_aux_split(aux, n, keep, out, n_out, mod_off);
+}
+
 // a sub-batch of reads and everything its pointers point to (mm355_reads_t is its first member: mm355_reads_free gets the box back)
 struct ReadsBox {
 	mm355_reads_t r;
@@ -463,32 +497,47 @@ struct ReadsBox {
 	std::vector<const char*> sp, np; std::vector<int32_t> ln;
 	// a reader that keeps quality: the strings back to back, qual_at[i] < 0 for a record without one (FASTA, or a length other than the sequence's)
 	bool keep_qual = false; std::string qual_bytes; std::vector<int64_t> qual_at; std::vector<const char*> qp;
+	// a BAM reader that keeps aux: the filtered blocks back to back, every read has one (of length 0 where nothing was kept)
+	bool keep_aux = false; std::string aux_bytes; std::vector<size_t> aux_at; std::vector<int32_t> aux_len, aux_mod; std::vector<const uint8_t*> ap;
 };
 
 extern "C" void mm355_reads_free(mm355_reads_t *r) { delete (ReadsBox*)r; }
 extern "C" const char *const *mm355_reads_quals(const mm355_reads_t *r) { const ReadsBox *B = (const ReadsBox*)r; return B && B->keep_qual? B->qp.data() : 0; }
 
+extern "C" const uint8_t *const *mm355_reads_aux(const mm355_reads_t *r, const int32_t **aux_len, const int32_t **aux_mod)
+{
+	const ReadsBox *B = (const ReadsBox*)r;
+	const bool on = B && B->keep_aux;
+	if (aux_len) *aux_len = on? B->aux_len.data() : 0;
+	if (aux_mod) *aux_mod = on? B->aux_mod.data() : 0;
+	return on? B->ap.data() : 0;
+}
+
 extern "C" int mm355_fastx_next(mm355_fastx_t *fx, int64_t max_reads, int64_t max_bases, mm355_reads_t **out)
 {
 	*out = 0;
 	if (fx == 0 || max_reads < 1 || max_bases < 1) return MM355_EINVAL;
+	fx->started = true;
 	if (fx->err) return fx->err;
 	ReadsBox *B = new ReadsBox();
 	B->keep_qual = fx->keep_qual;
-	std::string name, qual; bool has_qual = false;
+	std::string name, qual, aux; bool has_qual = false; int32_t aux_mod = 0;
 	while ((int64_t)B->ln.size() < max_reads) {
 		const size_t at = B->seq_bytes.size();
-		if (fx->held) { name.swap(fx->held_name); B->seq_bytes += fx->held_seq; fx->held_seq.clear(); fx->held = false; qual.swap(fx->held_qual); has_qual = fx->held_has_qual; }
+		if (fx->held) { name.swap(fx->held_name); B->seq_bytes += fx->held_seq; fx->held_seq.clear(); fx->held = false; qual.swap(fx->held_qual); has_qual = fx->held_has_qual;
+			aux.swap(fx->held_aux); aux_mod = fx->held_aux_mod; }
 		else {
 			const int rc = reads_record(fx, name, B->seq_bytes);      // (the bases land behind the sub-batch's other reads)
 			if (rc == 0) break;
 			if (rc < 0) { fx->err = rc; break; }
 			if (B->seq_bytes.size() - at >= (size_t)1 << 31) { fx->err = MM355_EINVAL; break; }
 			if (fx->keep_qual) { qual.swap(fx->qual); has_qual = fx->has_qual; }
+			if (!fx->keep_aux.empty() && fx->is_bam) { aux.swap(fx->aux); aux_mod = fx->aux_mod; }
 		}
 		if (!B->ln.empty() && (int64_t)B->seq_bytes.size() > max_bases) {   // over the base limit and not the first: it opens the next sub-batch
 			fx->held_name.swap(name); fx->held_seq.assign(B->seq_bytes, at, std::string::npos); fx->held = true;
 			fx->held_qual.swap(qual); fx->held_has_qual = has_qual;
+			fx->held_aux.swap(aux); fx->held_aux_mod = aux_mod;
 			B->seq_bytes.resize(at);
 			break;
 		}
@@ -500,10 +549,16 @@ extern "C" int mm355_fastx_next(mm355_fastx_t *fx, int64_t max_reads, int64_t ma
 			B->qual_at.push_back(ok? (int64_t)B->qual_bytes.size() : -1);
 			if (ok) B->qual_bytes += qual;
 		}
+		if (!fx->keep_aux.empty() && fx->is_bam) {
+			B->keep_aux = true;
+			B->aux_at.push_back(B->aux_bytes.size()); B->aux_len.push_back((int32_t)aux.size()); B->aux_mod.push_back(aux_mod);
+			B->aux_bytes += aux;
+		}
 	}
 	if (fx->err || B->ln.empty()) { delete B; return fx->err; }
 	for (size_t i = 0; i < B->ln.size(); ++i) { B->sp.push_back(B->seq_bytes.data() + B->seq_at[i]); B->np.push_back(B->name_bytes.data() + B->name_at[i]); }
 	for (size_t i = 0; i < B->qual_at.size(); ++i) B->qp.push_back(B->qual_at[i] < 0? (const char*)0 : B->qual_bytes.data() + B->qual_at[i]);
+	for (size_t i = 0; i < B->aux_at.size(); ++i) B->ap.push_back((const uint8_t*)B->aux_bytes.data() + B->aux_at[i]);
 	B->r.n = (int64_t)B->ln.size(); B->r.seqs = B->sp.data(); B->r.lens = B->ln.data(); B->r.names = B->np.data();
 	*out = &B->r;
 	return 0;

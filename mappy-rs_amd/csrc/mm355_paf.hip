@@ -6,6 +6,7 @@
 
 // PafFmt as the device writes it
 struct PafDevFmt : PafFmt {
+	typedef RecDev Dev;
 	typedef RecCount Count;
 	typedef RecWrite<RUNS> Write;
 	static constexpr const char *TIMES_ENV = 0;

@@ -18,7 +18,8 @@
 //   k_rec_fields  lane 0 runs the emitter with the writing sink: single bytes go straight to the text; runs that exist in memory already
 //                 (names, cs, MD, BAM's CIGAR words) are noted down with their place in the record and copied by the whole wave,
 //                 lane-strided (a full table falls back to lane 0: the table never decides what is written); the text formats' CIGAR is
-//                 written by the wave in tiles of 64 operations; SEQ and QUAL are only noted down, in a table of two runs per record.
+//                 written by the wave in tiles of 64 operations; SEQ and QUAL (BAM: and the copied aux tags) are only noted down, in a
+//                 table of F::TILE_RUNS runs per record.
 //   bulk          the format's own kernel over that table (k_sam_copy, k_bam_bulk): work item = (record, field, tile of output bytes), one
 //                 block each, so a 200-kb read is 49 blocks and not one wave.
 //   last step     the text formats copy the text back; BAM frames the stream first (k_bgzf_frame).
@@ -26,6 +27,7 @@
 #pragma once
 #include <stdio.h>
 #include <algorithm>
+#include <type_traits>
 #include <rocprim/device/device_scan.hpp>
 #include "mm355_pipeline.h"
 #include "mm355_wave.h"
@@ -40,6 +42,11 @@ struct RecDev {
 	const char *tn; const int64_t *tn_off;                            // contig names
 	const int32_t *l_read; const int64_t *l_first;                    // read of a record; first record of a read (n_reads + 1)
 	int64_t n_lines; int sam_flags, has_cigar;
+};
+
+// the same with the copied aux tags of a call that has some (BamAuxDevFmt): a format's kernels take F::Dev, so only that format's argument grows
+struct RecDevAux : RecDev {
+	const int64_t *aux_off; const int32_t *aux_len, *aux_mod;         // per read: its tags in bytes[]
 };
 
 __device__ __forceinline__ int32_t rec_row_of(const RecDev &D, int64_t l, int32_t r) { return D.hit_off[r + 1] > D.hit_off[r]? (int32_t)(l - D.l_first[r]) : -1; }
@@ -61,12 +68,18 @@ __device__ __forceinline__ void rec_line_dev(const RecDev &D, int64_t, int32_t r
 	R.seq = D.bytes + D.seq_off[r]; R.qual = D.qual_off[r] >= 0? D.bytes + D.qual_off[r] : 0;
 	R.tn = D.tn; R.tn_off = D.tn_off; R.cigar = D.cigar; R.str = D.str;
 	R.rep_len = D.rep_len[r]; R.sam_flags = D.sam_flags;
+	R.aux = 0; R.aux_len = R.aux_mod = 0;
 	L.R = &R; L.row = row;
+}
+__device__ __forceinline__ void rec_line_dev(const RecDevAux &D, int64_t l, int32_t r, int32_t row, SamRead &R, SamLine &L)
+{
+	rec_line_dev((const RecDev&)D, l, r, row, R, L);
+	R.aux = (const uint8_t*)D.bytes + D.aux_off[r]; R.aux_len = D.aux_len[r]; R.aux_mod = D.aux_mod[r];
 }
 
 // a run the wave copies after lane 0 has laid the record out: len bytes (the text formats' CIGAR: words) from src to byte `at` of the record
 struct RecRun { const void *src; int64_t at, len; };
-// a SEQ / QUAL run of a record, which the format's bulk kernel writes in tiles: len bytes or bases from src to byte `dst` of the text; mode
+// a SEQ / QUAL / aux run of a record, which the format's bulk kernel writes in tiles: len bytes or bases from src to byte `dst` of the text; mode
 // is the bulk kernel's to read
 struct RecTileRun { const char *src; int64_t dst; int32_t len, mode; };
 
@@ -78,8 +91,9 @@ struct RecCount {
 	__device__ void bytes(const char *, int64_t l) { n += l; }
 	__device__ void cigar(const uint32_t *, int64_t) { n += aux; }            // (text: the wave has added up the widths)
 };
-// RUNS entries of runs[] are the table; a text format has one more behind them, for the CIGAR.  at0: where the record begins in the text
-template <int RUNS> struct RecWrite {
+// RUNS entries of runs[] are the table; a text format has one more behind them, for the CIGAR.  at0: where the record begins in the text.
+// TILE_RUNS entries of tile[] are the record's bulk runs
+template <int RUNS, int TILE_RUNS = 2> struct RecWrite {
 	char *p; int64_t n = 0, aux, at0; RecRun *runs; RecTileRun *tile; int n_runs = 0, n_tile = 0;
 	__device__ RecWrite(char *p_, int64_t aux_, int64_t at0_, RecRun *runs_, RecTileRun *tile_) : p(p_), aux(aux_), at0(at0_), runs(runs_), tile(tile_) {}
 	__device__ void ch(char c) { p[n++] = c; }
@@ -89,7 +103,7 @@ template <int RUNS> struct RecWrite {
 		else for (int64_t i = 0; i < l; ++i) p[n++] = b[i];
 	}
 	__device__ void cigar(const uint32_t *w, int64_t k) { runs[RUNS] = RecRun{ w, n, k }; n += aux; }   // (text: the wave writes it)
-	__device__ void note(const char *b, int64_t l, int mode) { if (n_tile < 2) tile[n_tile++] = RecTileRun{ b, at0 + n, (int32_t)l, mode }; }   // (a record has SEQ and QUAL, no third run)
+	__device__ void note(const char *b, int64_t l, int mode) { if (n_tile < TILE_RUNS) tile[n_tile++] = RecTileRun{ b, at0 + n, (int32_t)l, mode }; }   // (a record has no more bulk runs than its format says)
 };
 
 // the text of nc CIGAR words, written by a whole wave in tiles of 64 operations: a prefix sum of the operations' widths, every lane its own
@@ -112,7 +126,7 @@ __device__ __forceinline__ void rec_wave_cigar(char *dst, const uint32_t *w, int
 }
 
 // ---- the kernels of the shared stages: a wave per record, four records per block
-template <typename F> __global__ __launch_bounds__(256) void k_rec_len(RecDev D, int64_t *len, int64_t *aux, int64_t *ntile)
+template <typename F> __global__ __launch_bounds__(256) void k_rec_len(typename F::Dev D, int64_t *len, int64_t *aux, int64_t *ntile)
 {
 	const int lane = threadIdx.x & 63;
 	const int64_t l = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -141,7 +155,7 @@ static __global__ void k_rec_line_off(const int64_t *off, const int64_t *l_first
 	if (i <= n_reads) line_off[i] = off[l_first[i]];
 }
 
-template <typename F> __global__ __launch_bounds__(256) void k_rec_fields(RecDev D, const int64_t *off, const int64_t *aux, char *text, RecTileRun *tile)
+template <typename F> __global__ __launch_bounds__(256) void k_rec_fields(typename F::Dev D, const int64_t *off, const int64_t *aux, char *text, RecTileRun *tile)
 {
 	__shared__ RecRun runs[4][F::RUNS + (F::WAVE_CIGAR? 1 : 0)];   // per wave; a text format's last one is the CIGAR
 	__shared__ int n_runs[4];
@@ -154,8 +168,12 @@ template <typename F> __global__ __launch_bounds__(256) void k_rec_fields(RecDev
 		SamRead R; typename F::Line L;
 		rec_line_dev(D, l, r, rec_row_of(D, l, r), R, L);
 		if constexpr (F::WAVE_CIGAR) runs[wv][F::RUNS] = RecRun{ 0, 0, 0 };
-		if constexpr (F::TILED) tile[2 * l] = tile[2 * l + 1] = RecTileRun{ 0, 0, 0, 0 };
-		typename F::Write s(rec, aux[l], off[l], runs[wv], F::TILED? tile + 2 * l : 0);
+		RecTileRun *mine = 0;
+		if constexpr (F::TILED) {
+			mine = tile + F::TILE_RUNS * l;
+			for (int k = 0; k < F::TILE_RUNS; ++k) mine[k] = RecTileRun{ 0, 0, 0, 0 };
+		}
+		typename F::Write s(rec, aux[l], off[l], runs[wv], mine);
 		F::emit(s, L, aux[l], (uint32_t)(off[l + 1] - off[l] - 4));
 		n_runs[wv] = s.n_runs;
 	}
@@ -171,14 +189,14 @@ template <typename F> __global__ __launch_bounds__(256) void k_rec_fields(RecDev
 }
 
 // the head of a bulk kernel: the run that block b of the tile grid works on and, in *t, which of the run's tiles it has.  tiles(run): how
-// many tiles the format cuts a run into
-template <typename Tiles> __device__ __forceinline__ RecTileRun rec_tile_run(const RecTileRun *runs, const int64_t *tile_off, int64_t n_lines, int64_t b, Tiles tiles, int64_t *t)
+// many tiles the format cuts a run into; NR: the runs of a record (F::TILE_RUNS)
+template <int NR, typename Tiles> __device__ __forceinline__ RecTileRun rec_tile_run(const RecTileRun *runs, const int64_t *tile_off, int64_t n_lines, int64_t b, Tiles tiles, int64_t *t)
 {
 	int64_t lo = 0, hi = n_lines;              // the last record whose first tile is <= b (records without tiles in front of it share that number)
 	while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (tile_off[mid] <= b) lo = mid; else hi = mid; }
 	*t = b - tile_off[lo];
-	RecTileRun r = runs[2 * lo];
-	if (*t >= tiles(r)) { *t -= tiles(r); r = runs[2 * lo + 1]; }
+	RecTileRun r = runs[NR * lo];
+	for (int k = 1; k < NR && *t >= tiles(r); ++k) { *t -= tiles(r); r = runs[NR * lo + k]; }
 	return r;
 }
 
@@ -220,18 +238,19 @@ static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 // A format without SEQ and QUAL carries no read bytes: seqs, quals and rep_len are not read, and D's pointers to them are null.
 // *t_packed: the host clock when the packing was done (MM355_SAM_TIMES).
 template <typename F> static int rec_upload(mm355_ctx *c, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens,
-                                            const char *const *quals, const int32_t *rep_len, int sam_flags, bool has_cigar, RecDev *Dp, double *t_packed)
+                                            const char *const *quals, const int32_t *rep_len, const RecAux &ax, int sam_flags, bool has_cigar, typename F::Dev *Dp, double *t_packed)
 {
-	RecDev &D = *Dp;
+	typename F::Dev &D = *Dp;
 	const int64_t nh = H->n_hits, nr = H->n_reads;
 	std::vector<int64_t> n_line((size_t)nr), qn_len((size_t)nr);
 	int64_t nl = 0, qn_tot = 0, by_tot = 0;
+	const bool with_aux = std::is_same<typename F::Dev, RecDevAux>::value && ax.aux != 0;   // (the caller picks that format for a call with tags)
 	for (int64_t i = 0; i < nr; ++i) {
 		n_line[i] = F::n_lines(H, qlens, sam_flags, i);
 		nl += n_line[i];
 		qn_len[i] = n_line[i] == 0? 0 : qnames && qnames[i]? paf_qname_len(qnames[i]) : 1;   // (a read without records prints nothing)
 		qn_tot += qn_len[i];
-		if constexpr (F::TILED) if (n_line[i]) by_tot += (int64_t)qlens[i] * (quals && quals[i]? 2 : 1);
+		if constexpr (F::TILED) if (n_line[i]) by_tot += (int64_t)qlens[i] * (quals && quals[i]? 2 : 1) + (with_aux && ax.aux[i] && ax.len[i] > 0? ax.len[i] : 0);
 	}
 	D.n_lines = nl; D.sam_flags = sam_flags; D.has_cigar = has_cigar;
 	*t_packed = mm355_now_ms();
@@ -243,16 +262,18 @@ template <typename F> static int rec_upload(mm355_ctx *c, const mm355_hits_t *H,
 	// (a chain-only batch has no CIGAR words and no strings: H->cigar and H->str are not touched)
 	const size_t nc = has_cigar && H->n_cigar > 0? (size_t)H->n_cigar : 0, ns = has_cigar && H->n_str > 0? (size_t)H->n_str : 0;
 	const size_t per_read4 = F::TILED? up256((size_t)nr * 4) : 0, per_read8 = F::TILED? up256((size_t)nr * 8) : 0;   // rep_len; seq_off, qual_off
+	const size_t aux4 = with_aux? per_read4 : 0, aux8 = with_aux? per_read8 : 0;                                     // aux_len, aux_mod; aux_off: only a call with aux has them
 	// one device buffer; one pinned staging buffer for the parts made here (the tables, the names, the reads and qualities back to back)
 	const size_t o_hits = 0, o_tags = o_hits + up256((size_t)nh * sizeof(mm355_hit_t) + 8), o_cig = o_tags + up256((size_t)nh * sizeof(mm355_tags_t) + 8),
 	             o_str = o_cig + up256(nc * 4 + 4), o_qlen = o_str + up256(ns + 4), o_hoff = o_qlen + up256((size_t)nr * 4), o_made = o_hoff + up256((size_t)(nr + 1) * 8);
 	const size_t m_lread = 0, m_lfirst = m_lread + up256((size_t)nl * 4), m_rep = m_lfirst + up256((size_t)(nr + 1) * 8), m_qoff = m_rep + per_read4,
-	             m_soff = m_qoff + up256((size_t)(nr + 1) * 8), m_uoff = m_soff + per_read8, m_qn = m_uoff + per_read8,
+	             m_soff = m_qoff + up256((size_t)(nr + 1) * 8), m_uoff = m_soff + per_read8, m_aoff = m_uoff + per_read8, m_alen = m_aoff + aux8, m_amod = m_alen + aux4, m_qn = m_amod + aux4,
 	             m_by = m_qn + up256((size_t)qn_tot + 4), m_end = m_by + up256((size_t)by_tot + 64);   // (64: the copy kernels read whole dwords around a span)
 	if (c->rec_in.ensure(o_made + m_end) || c->h_rec_in.ensure(m_end) || c->h_rec_out.ensure(64, 1 << 20)) return MM355_ENOMEM;
 	char *hm = (char*)c->h_rec_in.p, *din = (char*)c->rec_in.p;
 	int32_t *l_read = (int32_t*)(hm + m_lread), *rl = (int32_t*)(hm + m_rep);
 	int64_t *l_first = (int64_t*)(hm + m_lfirst), *qoff = (int64_t*)(hm + m_qoff), *soff = (int64_t*)(hm + m_soff), *uoff = (int64_t*)(hm + m_uoff);
+	int64_t *aoff = (int64_t*)(hm + m_aoff); int32_t *alen = (int32_t*)(hm + m_alen), *amod = (int32_t*)(hm + m_amod);
 	char *qn = hm + m_qn, *by = hm + m_by;
 	int64_t at = 0, bat = 0, lat = 0;
 	for (int64_t i = 0; i < nr; ++i) {
@@ -267,6 +288,11 @@ template <typename F> static int rec_upload(mm355_ctx *c, const mm355_hits_t *H,
 			if (n_line[i]) {
 				soff[i] = bat; memcpy(by + bat, seqs[i], (size_t)qlens[i]); bat += qlens[i];
 				if (quals && quals[i]) { uoff[i] = bat; memcpy(by + bat, quals[i], (size_t)qlens[i]); bat += qlens[i]; }
+			}
+			if (aux8) {
+				const bool has = n_line[i] && ax.aux[i] && ax.len[i] > 0;
+				aoff[i] = bat; alen[i] = has? ax.len[i] : 0; amod[i] = has? ax.mod[i] : 0;
+				if (has) { memcpy(by + bat, ax.aux[i], (size_t)ax.len[i]); bat += ax.len[i]; }
 			}
 		}
 	}
@@ -288,6 +314,10 @@ template <typename F> static int rec_upload(mm355_ctx *c, const mm355_hits_t *H,
 	D.hit_off = (const int64_t*)(din + o_hoff); D.qlen = (const int32_t*)(din + o_qlen); D.rep_len = F::TILED? (const int32_t*)(made + m_rep) : 0;
 	D.qn_off = (const int64_t*)(made + m_qoff); D.qn = made + m_qn;
 	D.seq_off = F::TILED? (const int64_t*)(made + m_soff) : 0; D.qual_off = F::TILED? (const int64_t*)(made + m_uoff) : 0; D.bytes = F::TILED? made + m_by : 0;
+	if constexpr (std::is_same<typename F::Dev, RecDevAux>::value) {
+		if (!with_aux) return MM355_EINVAL;
+		D.aux_off = (const int64_t*)(made + m_aoff); D.aux_len = (const int32_t*)(made + m_alen); D.aux_mod = (const int32_t*)(made + m_amod);
+	}
 	D.tn = d_tn; D.tn_off = d_tn_off;
 	D.l_read = (const int32_t*)(made + m_lread); D.l_first = (const int64_t*)(made + m_lfirst);
 	return 0;
@@ -305,19 +335,19 @@ static int rec_text_empty(int64_t nr, mm355_text_t **out)
 
 // what a call's format-specific steps are told: the records, the bytes of the unframed text in c->rec_text, the tiles, the host clock at the
 // call's begin and after the packing; times: the format's *_TIMES variable is set
-struct RecCall { int64_t n_reads, n_lines, n_text, n_tiles; double t_begin, t_packed, t_copy; bool times; };
+struct RecCall { int64_t n_reads, n_lines, n_text, n_tiles; double t_begin, t_packed, t_copy; bool times; hipEvent_t bulk_ev[2] = { 0, 0 }; };   // bulk_ev: a format's own, around its bulk kernel
 
 // The driver.  F is the format's device half: its traits struct plus Count and Write (the device sinks), TIMES_ENV (the variable that
 // asks for a line of timings on stderr, or null), bulk() (with tiles: launches the bulk kernel on the run table) and finish() (the last
 // step: the result record from the text in c->rec_text and line_off[] on the device).
 template <typename F> static int rec_format_device(mm355_ctx *c, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens,
-                                                   const char *const *quals, const int32_t *rep_len, int sam_flags, bool has_cigar, mm355_text_t **out)
+                                                   const char *const *quals, const int32_t *rep_len, int sam_flags, bool has_cigar, mm355_text_t **out, const RecAux &ax = RecAux())
 {
 	RecCall k; k.n_reads = H->n_reads; k.n_tiles = 0;
 	const char *te = F::TIMES_ENV? getenv(F::TIMES_ENV) : 0; k.times = te && *te && *te != '0';   // (read per call)
 	k.t_begin = mm355_now_ms();
-	RecDev D;
-	if (int rc = rec_upload<F>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, has_cigar, &D, &k.t_packed)) return rc;
+	typename F::Dev D;
+	if (int rc = rec_upload<F>(c, H, qnames, seqs, qlens, quals, rep_len, ax, sam_flags, has_cigar, &D, &k.t_packed)) return rc;
 	const int64_t nr = k.n_reads, nl = k.n_lines = D.n_lines;
 	if (nl == 0) return rec_text_empty(nr, out);   // nothing to launch
 	hipStream_t st = c->st;
@@ -325,9 +355,11 @@ template <typename F> static int rec_format_device(mm355_ctx *c, const mm355_hit
 	// space; a format without tiles has neither their counts nor the runs
 	size_t tb = 0;
 	(void)rocprim::exclusive_scan(nullptr, tb, (int64_t*)0, (int64_t*)0, (int64_t)0, (size_t)nl + 1, rocprim::plus<int64_t>(), st);
+	size_t tile_runs = 0;                              // (a format without tiles says nothing about their runs)
+	if constexpr (F::TILED) tile_runs = F::TILE_RUNS;
 	const size_t w1 = up256((size_t)(nl + 1) * 8), wt = F::TILED? w1 : 0;
 	const size_t w_len = 0, w_off = w_len + w1, w_nt = w_off + w1, w_to = w_nt + wt, w_aux = w_to + wt, w_lo = w_aux + w1, w_run = w_lo + up256((size_t)(nr + 1) * 8),
-	             w_tmp = w_run + (F::TILED? up256((size_t)nl * 2 * sizeof(RecTileRun)) : 0);
+	             w_tmp = w_run + up256((size_t)nl * tile_runs * sizeof(RecTileRun));
 	if (c->rec_work.ensure(w_tmp + tb + 256)) return MM355_ENOMEM;
 	char *dw = (char*)c->rec_work.p;
 	int64_t *d_len = (int64_t*)(dw + w_len), *d_off = (int64_t*)(dw + w_off), *d_nt = (int64_t*)(dw + w_nt), *d_to = (int64_t*)(dw + w_to),

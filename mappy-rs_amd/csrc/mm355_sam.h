@@ -35,7 +35,11 @@ struct SamRead {
 	const char *tn; const int64_t *tn_off;
 	const uint32_t *cigar; const char *str;                              // the batch's CIGAR words and string arena
 	int32_t rep_len; int sam_flags;                                      // rep_len: of an unmapped read (a row's comes from its tags row)
+	const uint8_t *aux; int32_t aux_len, aux_mod;                        // copied aux tags (BAM records only; the text formats do not print them): [0, aux_mod) on
+	                                                                     // every record, [aux_mod, aux_len) on records that hold the whole read; none: 0, 0, 0
 };
+// the copied aux tags of a batch, per read: aux == 0: none; aux[i] == 0: read i has none
+struct RecAux { const uint8_t *const *aux = 0; const int32_t *len = 0, *mod = 0; };
 struct SamLine { const SamRead *R; int32_t row; };                       // row < 0: the unmapped record
 
 MM_HD uint32_t sam_flag_of(const mm355_hit_t &h, const mm355_tags_t &t)
@@ -167,7 +171,7 @@ struct SamNames {
 };
 
 inline SamRead mm355_sam_read_of(const mm355_hits_t *H, int64_t i, const char *const *qnames, const char *const *seqs, const int32_t *qlens,
-                                 const char *const *quals, const int32_t *rep_len, const SamNames &nm, int sam_flags)
+                                 const char *const *quals, const int32_t *rep_len, const SamNames &nm, int sam_flags, const RecAux &ax = RecAux())
 {
 	SamRead R;
 	const int64_t k0 = H->hit_off[i];
@@ -178,16 +182,18 @@ inline SamRead mm355_sam_read_of(const mm355_hits_t *H, int64_t i, const char *c
 	R.tn = nm.bytes.data(); R.tn_off = nm.off.data();
 	R.cigar = H->cigar; R.str = H->str;
 	R.rep_len = R.n_rows == 0 && rep_len? rep_len[i] : 0; R.sam_flags = sam_flags;
+	const bool has_aux = ax.aux && ax.aux[i] && ax.len[i] > 0;
+	R.aux = has_aux? ax.aux[i] : 0; R.aux_len = has_aux? ax.len[i] : 0; R.aux_mod = has_aux? ax.mod[i] : 0;
 	return R;
 }
 
 // ---- the format as the shared writers see it (the host walk below; the device record writer, mm355_recdev.h): compile-time facts only
 struct SamFmt {
 	typedef SamLine Line; typedef SamCountSink HostCount; typedef SamWriteSink HostWrite;
-	enum { RUNS = 4 };                                                 // runs of a line the wave copies: qname, rname, cs, MD
+	enum { RUNS = 4, TILE_RUNS = 2 };                                  // runs of a line the wave copies: qname, rname, cs, MD; runs the bulk kernel writes in tiles: SEQ, QUAL
 	static constexpr bool WAVE_CIGAR = true, TILED = true, FRAMED = false;   // the CIGAR is text, which the wave writes; SEQ and QUAL go in tiles; the text is the result
-	// every line has its newline at least, and none is too long; lines the upload takes (the tile table has two runs per line)
-	static constexpr int64_t MIN_RECORD = 1, MAX_RECORD = INT64_MAX, MAX_LINES = INT32_MAX / 2;
+	// every line has its newline at least, and none is too long; lines the upload takes (the tile table has TILE_RUNS runs per line)
+	static constexpr int64_t MIN_RECORD = 1, MAX_RECORD = INT64_MAX, MAX_LINES = INT32_MAX / TILE_RUNS;
 	static MM_HD int64_t word_term(uint32_t w) { return paf_cigar_width(w); }   // summed over a row's CIGAR words: the length of the CIGAR text
 	template <typename S> static MM_HD void emit(S &s, const SamLine &L, int64_t, uint32_t) { sam_emit_line(s, L); }
 	static int64_t n_lines(const mm355_hits_t *H, const int32_t *qlens, int sam_flags, int64_t i) { return mm355_sam_n_lines(H, qlens, sam_flags, i); }
@@ -199,7 +205,8 @@ struct SamFmt {
 // once to write, then the format's framing if it has one.  The arguments must have passed the format's check.  line_off counts in the
 // unframed text.
 template <typename F> inline int mm355_rec_format_host(const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens,
-                                                       const char *const *quals, const int32_t *rep_len, const PafNames &pn, int sam_flags, mm355_text_t **out)
+                                                       const char *const *quals, const int32_t *rep_len, const PafNames &pn, int sam_flags, mm355_text_t **out,
+                                                       const RecAux &ax = RecAux())
 {
 	*out = 0;
 	const SamNames nm(pn);
@@ -209,7 +216,7 @@ template <typename F> inline int mm355_rec_format_host(const mm355_hits_t *H, co
 		first[i] = (int64_t)off.size();
 		const int64_t nl = F::n_lines(H, qlens, sam_flags, i);
 		if (nl == 0) continue;
-		const SamRead R = mm355_sam_read_of(H, i, qnames, seqs, qlens, quals, rep_len, nm, sam_flags);
+		const SamRead R = mm355_sam_read_of(H, i, qnames, seqs, qlens, quals, rep_len, nm, sam_flags, ax);
 		for (int64_t j = 0; j < nl; ++j) {
 			typename F::HostCount cs;
 			F::emit(cs, SamLine{ &R, R.n_rows? (int32_t)j : -1 }, R.n_rows? F::host_sum(H, R.rows[j]) : 0, 0);
@@ -226,7 +233,7 @@ template <typename F> inline int mm355_rec_format_host(const mm355_hits_t *H, co
 	for (int64_t i = 0; i <= H->n_reads; ++i) T->line_off[i] = off[first[i]];
 	for (int64_t i = 0; i < H->n_reads; ++i) {
 		if (first[i + 1] == first[i]) continue;
-		const SamRead R = mm355_sam_read_of(H, i, qnames, seqs, qlens, quals, rep_len, nm, sam_flags);
+		const SamRead R = mm355_sam_read_of(H, i, qnames, seqs, qlens, quals, rep_len, nm, sam_flags, ax);
 		for (int64_t l = first[i]; l < first[i + 1]; ++l) {
 			typename F::HostWrite ws(dst + off[l]);
 			const int32_t j = (int32_t)(l - first[i]);

@@ -18,7 +18,7 @@ __global__ __launch_bounds__(256) void k_sam_copy(const RecTileRun *copy, const 
 	__shared__ unsigned char comp[256];
 	comp[threadIdx.x] = sam_comp((unsigned char)threadIdx.x);
 	int64_t t;
-	const RecTileRun r = rec_tile_run(copy, tile_off, n_lines, blockIdx.x, sam_run_tiles, &t);
+	const RecTileRun r = rec_tile_run<SamFmt::TILE_RUNS>(copy, tile_off, n_lines, blockIdx.x, sam_run_tiles, &t);
 	__syncthreads();
 	const int64_t o0 = t * SAM_TILE, o1 = o0 + SAM_TILE < (int64_t)r.len? o0 + SAM_TILE : (int64_t)r.len;   // this tile: bytes [o0, o1) of the run
 	if (t < 0 || o0 >= o1) return;
@@ -41,6 +41,7 @@ __global__ __launch_bounds__(256) void k_sam_copy(const RecTileRun *copy, const 
 
 // SamFmt as the device writes it
 struct SamDevFmt : SamFmt {
+	typedef RecDev Dev;
 	struct Count : RecCount {
 		using RecCount::RecCount;
 		__device__ void seq(const char *, int64_t l, bool, bool) { n += l; tiles += sam_tiles(l); }

@@ -28,7 +28,7 @@ import numpy as np
 
 from . import _ffi
 
-__all__ = ["Aligner", "Mapping", "paf_line", "sam_lines", "shard_by_bases", "order_by_length", "bgzf_unwrap"]
+__all__ = ["Aligner", "Mapping", "paf_line", "sam_lines", "shard_by_bases", "order_by_length", "bgzf_unwrap", "bam_aux_split"]
 
 _CIGAR_OPS = "MIDNSHP=X"
 
@@ -387,6 +387,33 @@ def sam_lines(ms, name, seq, qual=None, *, softclip=False, rl=None):
 
 # the empty BGZF block that ends a BAM file
 BAM_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def bam_aux_split(aux, keep="*"):
+    """(kept, mod_off): the tags of the BAM aux block `aux` (bytes) that `keep` names -- "*" for all, or two-letter names back to back --
+    in the two groups the BAM writer takes: first every kept tag but MM ML MN Mm Ml, then, from mod_off, those (mm355_bam_aux_split; the
+    tags the writer emits itself are always dropped).  ValueError: a malformed block or `keep`."""
+    aux = bytes(aux)
+    out = C.create_string_buffer(max(1, len(aux)))
+    n_out, mod = C.c_int32(), C.c_int32()
+    if len(aux) > 2**31 - 1 or _ffi.lib().mm355_bam_aux_split(aux, len(aux), keep.encode("latin-1"), out, C.byref(n_out), C.byref(mod)) != 0:
+        raise ValueError("malformed BAM aux block, or malformed `keep`")
+    return out.raw[:n_out.value], mod.value
+
+
+def _keep_of(copy_tags):
+    """map_bam_file's copy_tags as mm355_fastx_keep_aux takes it: None for none, "*" for all, or the names back to back"""
+    if copy_tags is None or copy_tags is False:
+        return None
+    if copy_tags is True:
+        return b"*"
+    try:
+        names = list(copy_tags) if not isinstance(copy_tags, (str, bytes)) else None
+    except TypeError:
+        names = None
+    if not names or not all(isinstance(t, str) and len(t) == 2 and t.isascii() and t.isprintable() for t in names):
+        raise ValueError("`copy_tags` must be False, True, or an iterable of two-letter tag names")
+    return "".join(names).encode()
 
 
 def bgzf_wrap(data, *, compress=False):
@@ -967,11 +994,12 @@ class Aligner:
     paf_on_device = None              # whether the device formatter wrote the text of the last map_paf / map_sam call
 
     # ---- SAM text (mm355_map_batch_sam): the lines of mappy_rs.sam_lines, formatted by the library
-    def sam_header(self):
-        """the SAM header of this index as bytes: @HD (unsorted, grouped by query), one @SQ per contig in index order, @PG of this library"""
+    def sam_header(self, rg=b""):
+        """the SAM header of this index as bytes: @HD (unsorted, grouped by query), one @SQ per contig in index order, @PG of this library;
+        rg: @RG lines (bytes, newline-terminated) to stand between the @SQ lines and @PG"""
         L = self._L
         sq = "".join("@SQ\tSN:%s\tLN:%d\n" % (nm, L.mm355_index_seq_len(self._idx, i)) for i, nm in enumerate(self._names()))
-        return ("@HD\tVN:1.6\tSO:unsorted\tGO:query\n" + sq + "@PG\tID:mappy_rs\tPN:mappy_rs\n").encode()
+        return ("@HD\tVN:1.6\tSO:unsorted\tGO:query\n" + sq).encode() + bytes(rg) + b"@PG\tID:mappy_rs\tPN:mappy_rs\n"
 
     def _sam_flags(self, cs, MD):
         if not self._mo.flag & 4:
@@ -1021,21 +1049,42 @@ class Aligner:
             L.mm355_free_text(tp)
 
     # ---- BAM records (mm355_map_batch_bam): the BAM encoding of map_sam's lines in stored BGZF blocks, formed by the library
-    def map_bam(self, seqs, names=None, quals=None, cs=False, MD=False, *, softclip=False, hit_only=False, where=_ffi.PAF_AUTO, compress=False):
+    def map_bam(self, seqs, names=None, quals=None, cs=False, MD=False, *, softclip=False, hit_only=False, where=_ffi.PAF_AUTO, compress=False, aux=None):
         """the BAM records of `seqs` as bytes: whole BGZF blocks (stored, not compressed) without the header (bam_header()) and without the
         EOF block (BAM_EOF), in input order; one mm355_map_batch_bam call.  A record is the BAM encoding of the line map_sam writes for the
         same arguments (include/mm355.h states it field by field); the results of consecutive calls, one behind the other, continue the
         stream.  Besides what map_sam refuses: a read name of more than 254 bytes (RuntimeError).  Arguments and `paf_on_device` as for map_sam.
         compress=True: the blocks deflated (mm355_map_batch_bam_deflate at level 1; on the device by a kernel, a workgroup per block): the same
-        records behind gzip.decompress, blocks of their real size."""
+        records behind gzip.decompress, blocks of their real size.
+        aux: a list with bytes or None for every read -- the BAM aux tags the read brought along (MM / ML, RG, ...).  Each entry goes through
+        mm355_bam_aux_split with "*"; a record that holds the whole read carries all of them behind its own tags, a hard-clipped
+        supplementary or a secondary only those that do not index the read's bases (include/mm355.h).  ValueError: a malformed entry,
+        with the read's index."""
+        if aux is not None:
+            seqs, aux = list(seqs), list(aux)
+            if len(aux) != len(seqs) or not all(a is None or isinstance(a, (bytes, bytearray)) for a in aux):
+                raise ValueError("`aux` must hold bytes or None for every read")
+            L, n = self._L, len(aux)
+            keep, lens, mods = [None] * n, (C.c_int32 * n)(), (C.c_int32 * n)()
+            for i, a in enumerate(aux):
+                if a is None:
+                    continue
+                try:
+                    keep[i], mods[i] = bam_aux_split(a)
+                except ValueError:
+                    raise ValueError("`aux[%d]` is no well-formed BAM aux block" % i) from None
+                lens[i] = len(keep[i])
+            ptrs = (C.c_void_p * n)(*[None if k is None else C.cast(C.c_char_p(k), C.c_void_p).value for k in keep])
+            return self._map_records(lambda *a: L.mm355_map_batch_bam_aux(*a[:7], ptrs, lens, mods, *a[7:-1], 1 if compress else 0, a[-1]),
+                                     seqs, names, quals, cs, MD, softclip, hit_only, where)
         if compress:
             L = self._L
             return self._map_records(lambda *a: L.mm355_map_batch_bam_deflate(*a[:-1], 1, a[-1]), seqs, names, quals, cs, MD, softclip, hit_only, where)
         return self._map_records(self._L.mm355_map_batch_bam, seqs, names, quals, cs, MD, softclip, hit_only, where)
 
-    def bam_header(self, compress=False):
-        """the BAM header of this index as BGZF blocks (compress=True: deflated): the magic, sam_header() as the text, the contigs with their lengths"""
-        text, L = self.sam_header(), self._L
+    def bam_header(self, compress=False, rg=b""):
+        """the BAM header of this index as BGZF blocks (compress=True: deflated): the magic, sam_header(rg) as the text, the contigs with their lengths"""
+        text, L = self.sam_header(rg), self._L
         refs = []
         for i, nm in enumerate(self._names()):
             b = nm.encode()
@@ -1043,7 +1092,7 @@ class Aligner:
         return bgzf_wrap(b"BAM\1" + struct.pack("<I", len(text)) + text + struct.pack("<I", len(refs)) + b"".join(refs), compress=bool(compress))
 
     def map_bam_file(self, reads_path, out_path, cs=False, MD=False, n_threads=None, sub_batch_reads=SUB_BATCH_READS, *, where=_ffi.PAF_AUTO,
-                     softclip=False, hit_only=False, compress=False, read_on_gpu=False):
+                     softclip=False, hit_only=False, compress=False, read_on_gpu=False, copy_tags=False):
         """maps a FASTA / FASTQ file of reads to an uncompressed BAM file (what `samtools view -u` writes; ready for `samtools sort` /
         `index` without a SAM parse): bam_header(), the records of map_bam per sub-batch in input order, BAM_EOF.  The reader, the workers,
         the bound on memory, the ".part" file and its rename, what a failure leaves behind and the returned dict are map_file's; n_lines
@@ -1051,10 +1100,16 @@ class Aligner:
         SAM prints one `*`): the gain is the consumer's, which parses nothing.
         compress=True: a compressed BAM file (what `samtools view -b` writes): bam_header(compress=True), the records of
         map_bam(compress=True) per sub-batch, BAM_EOF; the returned dict also has n_bytes_out, the size of the file.
-        read_on_gpu, and a BAM as the reads file: as for map_file."""
+        read_on_gpu, and a BAM as the reads file: as for map_file.
+        copy_tags: False / None drops the aux tags of a BAM reads file; True carries every tag of a read into its records (MM / ML, the
+        modified-base calls of a basecaller's BAM, among them); an iterable of two-letter names carries only those (anything else:
+        ValueError).  Which record gets which tags: include/mm355.h (a record that holds the whole read gets all, a hard-clipped
+        supplementary or a secondary those that do not index bases; the tags the writer emits itself are never copied).  The header then
+        has the input's @RG lines between @SQ and @PG, and the returned dict n_aux_bytes: the bytes of kept tags the reader handed on.
+        With a reads file that is no BAM the keyword copies nothing.  Works with either reader."""
         sam_flags = (_ffi.SAM_SOFTCLIP if softclip else 0) | (_ffi.SAM_HIT_ONLY if hit_only else 0)
         return self._map_file("bam", reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags, compress=bool(compress),
-                              read_on_gpu=bool(read_on_gpu))
+                              read_on_gpu=bool(read_on_gpu), keep_aux=_keep_of(copy_tags))
 
     def map_file(self, reads_path, out_path, cs=False, MD=False, n_threads=None, sub_batch_reads=SUB_BATCH_READS, *, where=_ffi.PAF_AUTO, format="paf",
                  read_on_gpu=False):
@@ -1080,7 +1135,7 @@ class Aligner:
             raise ValueError("`format` must be \"paf\" or \"sam\"")
         return self._map_file(format, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, 0, read_on_gpu=bool(read_on_gpu))
 
-    def _map_file(self, kind, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags, compress=False, read_on_gpu=False):
+    def _map_file(self, kind, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags, compress=False, read_on_gpu=False, keep_aux=None):
         """map_file (kind "paf" / "sam") and map_bam_file ("bam"): reader thread, workers, ordered writer, .part file"""
         sam = kind != "paf"                               # the reader keeps qualities, the call takes them and sam_flags
         flags = self._sam_flags(cs, MD) if sam else self._paf_flags(cs, MD)
@@ -1102,6 +1157,15 @@ class Aligner:
             rc = (L.mm355_fastx_open_qual if sam else L.mm355_fastx_open)(os.fsencode(reads_path), C.byref(fx))
         if rc != 0:
             raise RuntimeError("%s: %s" % (reads_path, L.mm355_strerror(rc).decode()))
+        if keep_aux is not None:                  # the tags to keep, and the header with the input's @RG lines
+            rc = L.mm355_fastx_keep_aux(fx, keep_aux)
+            if rc != 0:
+                L.mm355_fastx_close(fx)
+                raise RuntimeError("%s: %s" % (reads_path, L.mm355_strerror(rc).decode()))
+            n_rg = C.c_int64()
+            rg = L.mm355_fastx_bam_rg(fx, C.byref(n_rg))
+            if rg:
+                header = self.bam_header(compress, C.string_at(rg, n_rg.value))
         part = os.fspath(out_path) + (b".part" if isinstance(os.fspath(out_path), bytes) else ".part")
         try:
             out = open(part, "wb")          # (an unwritable path raises here: nothing has run, no file is left)
@@ -1113,13 +1177,14 @@ class Aligner:
         cv = threading.Condition()
         done, errors, workers = {}, [], []
         cancel = threading.Event()
-        st = {"n_sub": None, "n_reads": 0, "n_bases": 0}
+        st = {"n_sub": None, "n_reads": 0, "n_bases": 0, "n_aux": 0}
         mo, where = self._mo, int(where)
         acquire, release = self._ctx_acquire, self._ctx_release
         map_records = L.mm355_map_batch_bam if kind == "bam" else L.mm355_map_batch_sam
         if compress:
             def map_records(*a):
                 return L.mm355_map_batch_bam_deflate(*a[:-1], 1, a[-1])
+        level = 1 if compress else 0
 
         def fail(e):
             errors.append(e)
@@ -1143,7 +1208,15 @@ class Aligner:
                         n = int(r.n)
                         n_bases = int(np.ctypeslib.as_array(r.lens, shape=(n,)).sum(dtype=np.int64))
                         tp = C.POINTER(_ffi.Text)()
-                        if sam:
+                        n_aux = 0
+                        if keep_aux is not None:
+                            alen, amod = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
+                            ap = L.mm355_reads_aux(rp, C.byref(alen), C.byref(amod))
+                            if ap:
+                                n_aux = int(np.ctypeslib.as_array(alen, shape=(n,)).sum(dtype=np.int64))
+                            rc = L.mm355_map_batch_bam_aux(ctx[1], C.byref(mo), n, r.seqs, r.lens, r.names, L.mm355_reads_quals(rp), ap, alen, amod, flags,
+                                                           sam_flags, where, level, C.byref(tp))
+                        elif sam:
                             rc = map_records(ctx[1], C.byref(mo), n, r.seqs, r.lens, r.names, L.mm355_reads_quals(rp), flags, sam_flags, where, C.byref(tp))
                         else:
                             rc = L.mm355_map_batch_paf(ctx[1], C.byref(mo), n, r.seqs, r.lens, r.names, flags, where, C.byref(tp))
@@ -1154,6 +1227,7 @@ class Aligner:
                     with cv:
                         st["n_reads"] += n
                         st["n_bases"] += n_bases
+                        st["n_aux"] += n_aux
                         done[k] = tp
                         cv.notify_all()
             except Exception as e:
@@ -1244,6 +1318,8 @@ class Aligner:
             res["n_bytes_out"] = n_out
         if read_on_gpu:
             res["reader_on_device"] = reader_on_device
+        if keep_aux is not None:
+            res["n_aux_bytes"] = st["n_aux"]
         return res
 
     def _stage_runner(self):

@@ -123,6 +123,7 @@ EXPORTS = [
     "mm355_bam_format", "mm355_map_batch_bam", "mm355_bgzf_wrap",
     "mm355_bam_format_deflate", "mm355_map_batch_bam_deflate", "mm355_bgzf_deflate",
     "mm355_bgzf_inflate", "mm355_fastx_open_device",
+    "mm355_bam_format_aux", "mm355_map_batch_bam_aux", "mm355_bam_aux_split", "mm355_fastx_keep_aux", "mm355_reads_aux", "mm355_fastx_bam_rg",
 ]
 
 _LIB = None
@@ -178,6 +179,15 @@ def lib():
     # the three with `level` in front of the result: 0 stored blocks, 1 deflate
     L.mm355_bam_format_deflate.argtypes = L.mm355_sam_format.argtypes[:-1] + [C.c_int, C.POINTER(C.POINTER(Text))]
     L.mm355_map_batch_bam_deflate.argtypes = L.mm355_map_batch_sam.argtypes[:-1] + [C.c_int, C.POINTER(C.POINTER(Text))]
+    auxp = [C.POINTER(C.c_void_p), i32p, i32p]           # aux, aux_len, aux_mod: the copied tags of every read
+    L.mm355_bam_format_aux.argtypes = L.mm355_sam_format.argtypes[:8] + auxp + [C.c_int, C.c_int, C.c_int, C.POINTER(C.POINTER(Text))]
+    L.mm355_map_batch_bam_aux.argtypes = L.mm355_map_batch_sam.argtypes[:7] + auxp + [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.POINTER(Text))]
+    L.mm355_bam_aux_split.argtypes = [C.c_char_p, C.c_int32, C.c_char_p, C.c_char_p, i32p, i32p]
+    L.mm355_fastx_keep_aux.argtypes = [vp, C.c_char_p]
+    L.mm355_reads_aux.argtypes = [C.POINTER(Reads), C.POINTER(i32p), C.POINTER(i32p)]
+    L.mm355_reads_aux.restype = C.POINTER(C.c_void_p)
+    L.mm355_fastx_bam_rg.argtypes = [vp, i64p]
+    L.mm355_fastx_bam_rg.restype = C.c_void_p
     L.mm355_bgzf_deflate.argtypes = [vp, C.c_char_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.POINTER(Text))]
     L.mm355_bgzf_inflate.argtypes = [vp, C.c_char_p, C.c_int64, C.c_int, C.POINTER(C.POINTER(Text))]
     L.mm355_fastx_open_device.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(vp)]
