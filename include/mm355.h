@@ -352,6 +352,44 @@ int mm355_map_batch_bam_aux(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t 
  * partial tag, n < 0, a `keep` that is NULL, empty or of odd length (but "*"). */
 int mm355_bam_aux_split(const uint8_t *aux, int32_t n, const char *keep, uint8_t *out, int32_t *n_out, int32_t *mod_off);
 
+/* --- coordinate-sorted BAM: the records of a call in samtools' coordinate order, as a RUN a file writer merges with others.  The key of a
+ * record (mm355_bamsort.h::bam_sort_key; refID, pos and flag are the record's own little-endian fields):
+ *   (uint64)(uint32)refID << 32 | (uint32)(pos + 1) << 1 | (flag >> 4 & 1)
+ * -- contigs in header order; inside a contig by position; at one position forward before reverse; records without a contig (refID -1; the
+ * unmapped record has pos -1, so its low word is 0) last.  TIES KEEP INPUT ORDER: a run is the stable sort of its input, so the stable merge
+ * of the runs of a file's calls, taken in call order, is the stable sort of the file the unsorted calls write, however the reads were cut
+ * into calls.  `rec` is the records in key order, back to back and UNFRAMED (mm355_bgzf_deflate frames a stream of them), rec_off their
+ * n_rec + 1 offsets, key their keys, ascending; ms_sort the sort step alone (keys, sort, permutation; on the device between two events);
+ * on_device: 1 when the device sorted.
+ * mm355_bam_sort is the stage by itself: n_rec records in the n_bytes at rec (host memory), record i at rec_off[i] .. rec_off[i + 1].
+ * `where`: MM355_PAF_HOST (ctx may be NULL: keys, std::stable_sort of indices, memcpy), MM355_PAF_DEVICE (an upload; mm355_bam.hip: k_rec_key
+ * a thread per record, rocPRIM's radix sort of (key, index) pairs, which is stable, a gather and two scans for the new offsets and tiles,
+ * k_rec_permute a block per 4096 output bytes of a record with aligned 16-byte stores from shifted source dwords; a copy back), or
+ * MM355_PAF_AUTO, which is the host as for mm355_bgzf_wrap.  n_rec == 0 (and n_bytes == 0) gives an empty run.
+ * MM355_EINVAL, before anything is allocated or launched: offsets that do not ascend from 0 to n_bytes, a piece of fewer than 37 bytes
+ * (block_size, the 32 fixed bytes, a one-byte name), a piece whose block_size + 4 is not its length, more than 2^31 - 1 records, an
+ * unknown `where`, MM355_PAF_DEVICE without a context.
+ * mm355_map_batch_bam_run is mm355_map_batch_bam_aux up to the finished records (aux == NULL allowed), then the sort where the records
+ * were formed -- `where` and its threshold are the formatter's: on the device the records never leave HBM before they are sorted -- and
+ * one copy of rec, key and rec_off to the host.  Nothing is framed.  It refuses what mm355_map_batch_bam_aux refuses.
+ * mm355_bam_gather is the copy loop of the merge: piece i is len[i] bytes at base + src_off[i]; the pieces go back to back into out.
+ * MM355_EINVAL before a byte is copied: a negative offset or length, a piece that passes base_len, a total that passes out_cap.
+ * MM355_BAM_TIMES=1: a sorted call on the device prints a line of its own on stderr (records, bytes, the sort step between two events). */
+typedef struct {
+	int64_t n_rec, n_bytes;
+	uint64_t *key;                  /* n_rec, ascending */
+	int64_t *rec_off;               /* n_rec + 1 offsets into rec */
+	char *rec;                      /* the records, sorted, UNFRAMED */
+	double ms_sort;                 /* the sort step alone */
+	int32_t on_device, reserved;
+} mm355_run_t;
+int mm355_bam_sort(mm355_ctx_t *ctx, const void *rec, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec, int where, mm355_run_t **out);
+int mm355_map_batch_bam_run(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
+                            const char *const *names, const char *const *quals, const uint8_t *const *aux, const int32_t *aux_len,
+                            const int32_t *aux_mod, int flags, int sam_flags, int where, mm355_run_t **out);
+int mm355_bam_gather(const void *base, int64_t base_len, const int64_t *src_off, const int64_t *len, int64_t n, void *out, int64_t out_cap);
+void mm355_free_run(mm355_run_t *r);
+
 /* --- BGZF input: the inverse of mm355_bgzf_deflate.  `data` is n bytes of BGZF members (what mm355_bgzf_wrap / _deflate, bgzip or any BAM
  * writer produced): gzip members with the BC extra subfield (other subfields may stand in front of it; MTIME, XFL and OS are ignored), cdata of
  * at most 64 KB holding any RFC 1951 stream -- several deflate blocks, stored, fixed and dynamic ones, run symbols 16 - 18, codes of 15 bits,

@@ -20,8 +20,11 @@
 //                 CRC-32 by the framing kernel's lanes, ISIZE) OR-ed together in the LDS the table had, then stored to the staging buffer in
 //                 16-byte pieces at DFL_STRIDE * block.  A payload that deflate would not shorten is framed exactly as k_bgzf_frame does.
 //   k_bgzf_compact  after an exclusive scan of the blocks' sizes: every block to its place, aligned 16-byte stores from shifted source dwords.
+// A sorted call (mm355_map_batch_bam_run) frames nothing: its last step puts the records into coordinate order in a second buffer
+// (k_rec_key, rocPRIM's radix sort, k_rec_sorted_len, k_rec_permute: further down) and returns them with their keys as a run.
 #include "mm355_bgzfdev.h"
 #include "mm355_deflate.h"
+#include <rocprim/device/device_radix_sort.hpp>
 
 #define BAM_TILE 4096         // output bytes of one k_bam_bulk block: 256 threads x 16 bytes
 
@@ -211,17 +214,105 @@ __global__ __launch_bounds__(BGZF_LANES) void k_bgzf_compact(const char *stage, 
 	bgzf_copy(stage + b * DFL_STRIDE, out + off[b], (uint32_t)size[b], threadIdx.x);
 }
 
+// ---- the sort stage of a sorted call (mm355_bamsort.h states the order): keys, rocPRIM's radix sort of (key, index), the new offsets, and
+//   k_rec_permute  work item = (sorted record j, tile of BAM_TILE output bytes), one block each, as k_bam_bulk's mode 5: a thread owns an
+//                 aligned 16-byte piece of the destination, the source comes from shifted aligned dwords, the ragged head and tail of a tile
+//                 are byte stores.  Every byte has one writer.
+// record i of the stream at src + off[i]: its key, and its index as the sort's value
+__global__ __launch_bounds__(256) void k_rec_key(const char *src, const int64_t *off, int64_t n, uint64_t *key, uint32_t *idx)
+{
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	key[i] = bam_sort_key((const uint8_t*)src + off[i]);       // (byte loads: a record starts at any residue)
+	idx[i] = (uint32_t)i;
+}
+// the lengths and tile counts in sorted order; entry n of each is 0, where the scans leave the totals
+__global__ __launch_bounds__(256) void k_rec_sorted_len(const int64_t *off, const uint32_t *idx, int64_t n, int64_t *len, int64_t *ntile)
+{
+	const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (j > n) return;
+	const int64_t l = j < n? off[idx[j] + 1] - off[idx[j]] : 0;
+	len[j] = l; ntile[j] = bam_tiles(l);
+}
+// src: readable for 8 bytes behind its last record (whole dwords are read around a span); new_off, tile_off: n + 1 entries; the grid may
+// be larger than the tile total (it is sized on the host by a bound): the blocks behind it leave
+__global__ __launch_bounds__(256) void k_rec_permute(const char *src, const int64_t *off, const uint32_t *idx, const int64_t *new_off, const int64_t *tile_off, int64_t n, char *out)
+{
+	const int64_t b = blockIdx.x;
+	if (b >= tile_off[n]) return;              // (the whole block)
+	int64_t lo = 0, hi = n;                    // the last record whose first tile is <= b (rec_tile_run's search; every record has a tile)
+	while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (tile_off[mid] <= b) lo = mid; else hi = mid; }
+	const int64_t t = b - tile_off[lo], len = new_off[lo + 1] - new_off[lo];
+	const int64_t o0 = t * BAM_TILE, o1 = o0 + BAM_TILE < len? o0 + BAM_TILE : len;   // this tile: bytes [o0, o1) of the record
+	if (o0 >= o1) return;
+	const char *s = src + off[idx[lo]];
+	char *dst = out + new_off[lo];
+	const uintptr_t d0 = (uintptr_t)(dst + o0), d1 = (uintptr_t)(dst + o1);
+	for (uintptr_t c = (d0 & ~(uintptr_t)15) + 16 * (uintptr_t)threadIdx.x; c < d1; c += 16 * 256) {
+		if (c >= d0 && c + 16 <= d1) {
+			uint32_t v[4];
+			sam_load16(s, (int64_t)c - (int64_t)(uintptr_t)dst, v);
+			*(uint4*)c = make_uint4(v[0], v[1], v[2], v[3]);
+		} else {
+			const uintptr_t e = c + 16 < d1? c + 16 : d1;
+			for (uintptr_t a = c > d0? c : d0; a < e; ++a) *(char*)a = s[(int64_t)(a - (uintptr_t)dst)];
+		}
+	}
+}
+
 // ------------------------------------------------------------------ host side
-// frames the n bytes at c->rec_text.p (readable for 8 more) into c->bam_out and copies the blocks to `to`; timed: the kernel between the
-// context's two events, microseconds in *k_us
-static int bam_frame_device(mm355_ctx *c, int64_t n, char *to, bool timed, double *k_us)
+// Sorts the n records of the stream at d_src (device memory, n_bytes, readable for 8 more; record i at d_off[i], n + 1 offsets on the device)
+// into c->bam_sorted and copies the records, their keys and their new offsets into R's arrays (allocated for n and n_bytes).  The four
+// launches and the library calls between them lie between the context's two events: microseconds in *k_us.  The permute grid is sized by a
+// bound on the tiles, n_bytes / BAM_TILE + n, so that nothing crosses to the host before the one copy at the end.
+static int bam_sort_device(mm355_ctx *c, const char *d_src, int64_t n_bytes, const int64_t *d_off, int64_t n, mm355_run_t *R, double *k_us)
+{
+	hipStream_t st = c->st;
+	*k_us = 0;
+	if (n == 0) return 0;
+	const int64_t max_tiles = n_bytes / BAM_TILE + n;
+	if (n > (int64_t)INT32_MAX || max_tiles > (int64_t)INT32_MAX) return MM355_EINVAL;
+	size_t tb_sort = 0, tb_scan = 0;
+	(void)rocprim::radix_sort_pairs(nullptr, tb_sort, (uint64_t*)0, (uint64_t*)0, (uint32_t*)0, (uint32_t*)0, (size_t)n, 0u, 64u, st);
+	(void)rocprim::exclusive_scan(nullptr, tb_scan, (int64_t*)0, (int64_t*)0, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st);
+	const size_t w8 = up256((size_t)(n + 1) * 8), w4 = up256((size_t)n * 4);
+	const size_t w_key0 = 0, w_key1 = w_key0 + w8, w_idx0 = w_key1 + w8, w_idx1 = w_idx0 + w4, w_len = w_idx1 + w4, w_noff = w_len + w8, w_nt = w_noff + w8, w_to = w_nt + w8,
+	             w_tmp = w_to + w8;
+	if (c->bam_work.ensure(w_tmp + up256(std::max(tb_sort, tb_scan) + 256)) || c->bam_sorted.ensure((size_t)n_bytes + 64)) return MM355_ENOMEM;
+	char *dw = (char*)c->bam_work.p;
+	uint64_t *key0 = (uint64_t*)(dw + w_key0), *key1 = (uint64_t*)(dw + w_key1);
+	uint32_t *idx0 = (uint32_t*)(dw + w_idx0), *idx1 = (uint32_t*)(dw + w_idx1);
+	int64_t *d_len = (int64_t*)(dw + w_len), *d_noff = (int64_t*)(dw + w_noff), *d_nt = (int64_t*)(dw + w_nt), *d_to = (int64_t*)(dw + w_to);
+	(void)hipEventRecord(c->ev0, st);
+	hipLaunchKernelGGL(k_rec_key, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_src, d_off, n, key0, idx0);
+	HIPCHK(hipGetLastError());
+	HIPCHK(rocprim::radix_sort_pairs(dw + w_tmp, tb_sort, key0, key1, idx0, idx1, (size_t)n, 0u, 64u, st));   // (a radix sort is stable: equal keys in index order)
+	hipLaunchKernelGGL(k_rec_sorted_len, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st, d_off, (const uint32_t*)idx1, n, d_len, d_nt);
+	HIPCHK(hipGetLastError());
+	HIPCHK(rocprim::exclusive_scan(dw + w_tmp, tb_scan, d_len, d_noff, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st));
+	HIPCHK(rocprim::exclusive_scan(dw + w_tmp, tb_scan, d_nt, d_to, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st));
+	hipLaunchKernelGGL(k_rec_permute, dim3((unsigned)max_tiles), dim3(256), 0, st, d_src, d_off, (const uint32_t*)idx1, (const int64_t*)d_noff, (const int64_t*)d_to, n, (char*)c->bam_sorted.p);
+	HIPCHK(hipGetLastError());
+	(void)hipEventRecord(c->ev1, st);
+	HIPCHK(hipMemcpyAsync(R->rec, c->bam_sorted.p, (size_t)n_bytes, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(R->key, key1, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(R->rec_off, d_noff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(mm355_wait_stream(st));
+	if (R->rec_off[n] != n_bytes) return MM355_EHIP;           // (the lengths are a permutation of the input's)
+	float ms = 0; (void)hipEventElapsedTime(&ms, c->ev0, c->ev1); *k_us = (double)ms * 1e3;
+	return 0;
+}
+
+// frames the n bytes at src (device memory, readable for 8 more: c->rec_text.p, or the sorted stream) into c->bam_out and copies the blocks to
+// `to`; timed: the kernel between the context's two events, microseconds in *k_us
+static int bam_frame_device(mm355_ctx *c, const char *src, int64_t n, char *to, bool timed, double *k_us)
 {
 	hipStream_t st = c->st;
 	if (n == 0) return 0;
 	if (bgzf_blocks(n) > (int64_t)INT32_MAX) return MM355_EINVAL;
 	if (c->bam_out.ensure((size_t)bgzf_size(n) + 64)) return MM355_ENOMEM;
 	if (timed) (void)hipEventRecord(c->ev0, st);
-	hipLaunchKernelGGL(k_bgzf_frame, dim3((unsigned)bgzf_blocks(n)), dim3(BGZF_LANES), 0, st, (const char*)c->rec_text.p, n, (char*)c->bam_out.p);
+	hipLaunchKernelGGL(k_bgzf_frame, dim3((unsigned)bgzf_blocks(n)), dim3(BGZF_LANES), 0, st, src, n, (char*)c->bam_out.p);
 	HIPCHK(hipGetLastError());
 	if (timed) (void)hipEventRecord(c->ev1, st);
 	HIPCHK(hipMemcpyAsync(to, c->bam_out.p, (size_t)bgzf_size(n), hipMemcpyDeviceToHost, st));
@@ -230,9 +321,9 @@ static int bam_frame_device(mm355_ctx *c, int64_t n, char *to, bool timed, doubl
 	return 0;
 }
 
-// deflates the n bytes at c->rec_text.p (readable for 8 more) into c->bam_out: *n_out bytes of blocks, which the caller copies; timed: the two
+// deflates the n bytes at src (device memory, readable for 8 more) into c->bam_out: *n_out bytes of blocks, which the caller copies; timed: the two
 // kernels and the scan between the context's two events, microseconds in *k_us, and the count of blocks that were written stored
-static int bam_deflate_device(mm355_ctx *c, int64_t n, int64_t *n_out, bool timed, double *k_us, int64_t *n_stored)
+static int bam_deflate_device(mm355_ctx *c, const char *src, int64_t n, int64_t *n_out, bool timed, double *k_us, int64_t *n_stored)
 {
 	hipStream_t st = c->st;
 	*n_out = 0; *n_stored = 0;
@@ -249,7 +340,7 @@ static int bam_deflate_device(mm355_ctx *c, int64_t n, int64_t *n_out, bool time
 	int64_t *d_size = (int64_t*)(dw + w_size), *d_off = (int64_t*)(dw + w_off);
 	HIPCHK(hipMemsetAsync(d_size + nb, 0, 8, st));
 	if (timed) (void)hipEventRecord(c->ev0, st);
-	hipLaunchKernelGGL(k_bgzf_deflate, dim3(grid), dim3(BGZF_LANES), 0, st, (const char*)c->rec_text.p, n, nb, (uint32_t*)(dw + w_scr), (char*)c->bam_stage.p, d_size);
+	hipLaunchKernelGGL(k_bgzf_deflate, dim3(grid), dim3(BGZF_LANES), 0, st, src, n, nb, (uint32_t*)(dw + w_scr), (char*)c->bam_stage.p, d_size);
 	HIPCHK(hipGetLastError());
 	HIPCHK(rocprim::exclusive_scan(dw + w_tmp, tb, d_size, d_off, (int64_t)0, (size_t)nb + 1, rocprim::plus<int64_t>(), st));
 	hipLaunchKernelGGL(k_bgzf_compact, dim3((unsigned)nb), dim3(BGZF_LANES), 0, st, (const char*)c->bam_stage.p, d_size, d_off, (char*)c->bam_out.p);
@@ -331,11 +422,11 @@ struct BamDevFmt : BamFmt {
 		double k_us = 0, d_us = 0;
 		int64_t n_out = bgzf_size(k.n_text), n_stored = 0;
 		if (c->bgzf_level)
-			if (int rc = bam_deflate_device(c, k.n_text, &n_out, k.times, &d_us, &n_stored)) return rc;
+			if (int rc = bam_deflate_device(c, (const char*)c->rec_text.p, k.n_text, &n_out, k.times, &d_us, &n_stored)) return rc;
 		mm355_text_t *T = mm355_text_alloc(k.n_reads, k.n_lines, n_out);
 		if (T == 0) return MM355_ENOMEM;
 		hipError_t e = hipMemcpyAsync(T->line_off, d_lo, (size_t)(k.n_reads + 1) * 8, hipMemcpyDeviceToHost, c->st);
-		int rc = e != hipSuccess? MM355_EHIP : c->bgzf_level? bam_blocks_back(c, n_out, T->text) : bam_frame_device(c, k.n_text, T->text, k.times, &k_us);
+		int rc = e != hipSuccess? MM355_EHIP : c->bgzf_level? bam_blocks_back(c, n_out, T->text) : bam_frame_device(c, (const char*)c->rec_text.p, k.n_text, T->text, k.times, &k_us);
 		if (rc) { fprintf(stderr, "[mm355] error %d in the BAM writer (%s)\n", rc, hipGetErrorString(e)); mm355_free_text_host(T); return rc; }
 		if (k.times && k.bulk_ev[1]) { float ms = 0; (void)hipEventElapsedTime(&ms, k.bulk_ev[0], k.bulk_ev[1]); *b_us = (double)ms * 1e3; }   // (the stream has been waited for)
 		if (k.times && c->bgzf_level) bam_deflate_times("records", k.n_text, n_out, n_stored, d_us, true);
@@ -349,6 +440,35 @@ struct BamDevFmt : BamFmt {
 
 // BamDevFmt for a call with copied tags: the kernels' argument carries them
 struct BamAuxDevFmt : BamDevFmt { typedef RecDevAux Dev; };
+
+// The sorted call (mm355_map_batch_bam_run): the kernels, sinks and bulk step are B's -- the same instantiations an unsorted call launches --
+// and the last step sorts the records where they lie instead of framing them: the result is a run.
+// MM355_BAM_TIMES=1 (tools/sort_bench.py): a line of its own with the sort step's time between two events and k_bam_bulk's
+template <typename B> struct BamRunFmtOf : B {
+	typedef B Kern;
+	static int finish(mm355_ctx *c, RecCall &k, const int64_t *, mm355_run_t **out)
+	{
+		double s_us = 0, b_us = 0;
+		mm355_run_t *R = mm355_run_alloc(k.n_lines, k.n_text);
+		int rc = R? bam_sort_device(c, (const char*)c->rec_text.p, k.n_text, k.d_off, k.n_lines, R, &s_us) : MM355_ENOMEM;
+		if (rc == 0 && k.times && k.bulk_ev[1]) { float ms = 0; (void)hipEventElapsedTime(&ms, k.bulk_ev[0], k.bulk_ev[1]); b_us = (double)ms * 1e3; }   // (the stream has been waited for)
+		for (hipEvent_t &e : k.bulk_ev) if (e) { (void)hipEventDestroy(e); e = 0; }
+		if (rc) {                                  // (a copy into R's arrays may be queued: the stream first, then the free)
+			(void)mm355_wait_stream(c->st);
+			fprintf(stderr, "[mm355] error %d in the BAM sort stage\n", rc);
+			mm355_free_run_host(R);
+			return rc;
+		}
+		if (k.times)
+			fprintf(stderr, "[mm355] bam_sort_times records %lld stream_bytes %lld tiles %lld k_rec_key_sort_permute_us %.1f k_bam_bulk_us %.1f total_ms %.3f\n", (long long)k.n_lines,
+			        (long long)k.n_text, (long long)k.n_tiles, s_us, b_us, mm355_now_ms() - k.t_begin);
+		R->ms_sort = s_us / 1e3;
+		*out = R;
+		return 0;
+	}
+};
+typedef BamRunFmtOf<BamDevFmt> BamRunDevFmt;
+typedef BamRunFmtOf<BamAuxDevFmt> BamAuxRunDevFmt;
 
 // MM355_PAF_AUTO for BAM: the device formatter from this many hits on.  Measured with tools/bam_bench.py (profiles/bam_file.json, format_sweep:
 // ms_format of the two formatters on the hits of 16 .. 9216 reads, map-ont with cs, reads of N50 8 kb with qualities): the host is ahead at 16
@@ -422,6 +542,96 @@ extern "C" int mm355_map_batch_bam(mm355_ctx_t *c, const mm355_mapopt_t *mo, int
 	return mm355_map_batch_bam_aux(c, mo, n_reads, seqs, lens, names, quals, 0, 0, 0, flags, sam_flags, where, 0, out);
 }
 
+// ---- sorted calls
+// the host formatter's records as they are: BamFmt without the framing
+struct BamRawFmt : BamFmt {
+	static constexpr bool FRAMED = false;
+	static int64_t out_size(int64_t n) { return n; }
+};
+
+extern "C" void mm355_free_run(mm355_run_t *r) { mm355_free_run_host(r); }
+
+extern "C" int mm355_bam_gather(const void *base, int64_t base_len, const int64_t *src_off, const int64_t *len, int64_t n, void *out, int64_t out_cap)
+{
+	return bam_gather(base, base_len, src_off, len, n, out, out_cap);
+}
+
+extern "C" int mm355_bam_sort(mm355_ctx_t *c, const void *rec, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec, int where, mm355_run_t **out)
+{
+	if (out == 0) return MM355_EINVAL;
+	*out = 0;
+	if (where < MM355_PAF_AUTO || where > MM355_PAF_DEVICE || (where == MM355_PAF_DEVICE && c == 0)) return MM355_EINVAL;
+	if (int rc = bam_sort_check(rec, n_bytes, rec_off, n_rec)) return rc;
+	const double t0 = mm355_now_ms();
+	// AUTO: the host, as for the bare wrap -- the bytes are the caller's, in host memory
+	if (where != MM355_PAF_DEVICE || n_rec == 0) {
+		if (int rc = bam_sort_run_host(rec, n_bytes, rec_off, n_rec, out)) return rc;
+		(*out)->ms_sort = mm355_now_ms() - t0;
+		return 0;
+	}
+	HIPCHK(hipSetDevice(c->dev));
+	if (c->rec_text.ensure((size_t)n_bytes + 64) || c->rec_work.ensure((size_t)(n_rec + 1) * 8)) return MM355_ENOMEM;
+	HIPCHK(hipMemcpyAsync(c->rec_text.p, rec, (size_t)n_bytes, hipMemcpyHostToDevice, c->st));
+	HIPCHK(hipMemcpyAsync(c->rec_work.p, rec_off, (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice, c->st));
+	mm355_run_t *R = mm355_run_alloc(n_rec, n_bytes);
+	if (R == 0) { (void)mm355_wait_stream(c->st); return MM355_ENOMEM; }     // (the uploads read the caller's memory)
+	double k_us = 0;
+	const int rc = bam_sort_device(c, (const char*)c->rec_text.p, n_bytes, (const int64_t*)c->rec_work.p, n_rec, R, &k_us);
+	if (rc) { (void)mm355_wait_stream(c->st); mm355_free_run_host(R); return rc; }
+	if (bam_times_on())
+		fprintf(stderr, "[mm355] bam_sort_times stage records %lld stream_bytes %lld k_rec_key_sort_permute_us %.1f total_ms %.3f\n", (long long)n_rec, (long long)n_bytes, k_us, mm355_now_ms() - t0);
+	R->ms_sort = k_us / 1e3; R->on_device = 1;
+	*out = R;
+	return 0;
+}
+
+// the records of a batch result as a run: mm355_bam_format_aux's check and its choice of formatter, then the sort where the records were formed
+static int bam_run_format(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens,
+                          const char *const *quals, const int32_t *rep_len, const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod, int sam_flags,
+                          int where, mm355_run_t **out)
+{
+	if (c == 0 || mo == 0 || H == 0 || where < MM355_PAF_AUTO || where > MM355_PAF_DEVICE) return MM355_EINVAL;
+	if (c->mi == 0) return MM355_ENOIDX;
+	const PafNames nm = { c->mi->names.data(), c->mi->n_seq };
+	RecAux ax;
+	if (aux) { ax.aux = aux; ax.len = aux_len; ax.mod = aux_mod; }
+	if (int rc = mm355_bam_check_aux(H, nm, (mo->flag & MMF_CIGAR) != 0, qnames, seqs, qlens, rep_len, sam_flags, ax)) return rc;
+	c->bgzf_level = 0;
+	if (rec_where(where, H->n_hits, "MM355_BAM_MIN_HITS", MM355_BAM_MIN_HITS_DEFAULT) == MM355_PAF_DEVICE) {
+		const int rc = ax.aux? rec_format_device_to<BamAuxRunDevFmt, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out, ax)
+		                     : rec_format_device_to<BamRunDevFmt, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out);
+		if (rc == 0) (*out)->on_device = 1;
+		return rc;
+	}
+	mm355_text_t *T = 0;
+	if (int rc = mm355_rec_format_host<BamRawFmt>(H, qnames, seqs, qlens, quals, rep_len, nm, sam_flags, &T, ax)) return rc;
+	std::vector<int64_t> off((size_t)T->n_lines + 1);
+	int64_t at = 0;
+	for (int64_t i = 0; i < T->n_lines; ++i) { off[(size_t)i] = at; at += (int64_t)bam_rec_u32((const uint8_t*)T->text + at) + 4; }   // (the writer's own block_size words)
+	off[(size_t)T->n_lines] = at;
+	const double t0 = mm355_now_ms();
+	int rc = at == T->n_text? bam_sort_run_host(T->text, T->n_text, off.data(), T->n_lines, out) : MM355_EINVAL;
+	if (rc == 0) (*out)->ms_sort = mm355_now_ms() - t0;
+	mm355_free_text_host(T);
+	return rc;
+}
+
+extern "C" int mm355_map_batch_bam_run(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
+                                       const char *const *names, const char *const *quals, const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod,
+                                       int flags, int sam_flags, int where, mm355_run_t **out)
+{
+	if (out == 0) return MM355_EINVAL;
+	*out = 0;
+	if (aux && (aux_len == 0 || aux_mod == 0)) return MM355_EINVAL;   // (before anything is mapped)
+	if (mo && !(mo->flag & MMF_CIGAR)) return MM355_EINVAL;
+	mm355_hits_t *H = 0; const int32_t *rep_len = 0;
+	int rc = mm355_map_batch_rl(c, mo, n_reads, seqs, lens, names, flags | MM355_OUT_TAGS, &H, &rep_len);
+	if (rc) return rc;
+	rc = bam_run_format(c, mo, H, names, seqs, lens, quals, rep_len, aux, aux_len, aux_mod, sam_flags, where, out);
+	mm355_free_hits(H);
+	return rc;
+}
+
 extern "C" int mm355_bgzf_deflate(mm355_ctx_t *c, const void *data, int64_t n, int where, int level, mm355_text_t **out)
 {
 	if (out == 0) return MM355_EINVAL;
@@ -446,11 +656,11 @@ extern "C" int mm355_bgzf_deflate(mm355_ctx_t *c, const void *data, int64_t n, i
 		if (c->rec_text.ensure((size_t)n + 64)) return MM355_ENOMEM;
 		if (n) HIPCHK(hipMemcpyAsync(c->rec_text.p, data, (size_t)n, hipMemcpyHostToDevice, c->st));
 		if (level)
-			if (int rc = bam_deflate_device(c, n, &n_out, times, &k_us, &n_stored)) return rc;
+			if (int rc = bam_deflate_device(c, (const char*)c->rec_text.p, n, &n_out, times, &k_us, &n_stored)) return rc;
 		mm355_text_t *T = mm355_text_alloc(0, bgzf_blocks(n), n_out);
 		if (T == 0) return MM355_ENOMEM;
 		T->line_off[0] = 0;
-		const int rc = level? bam_blocks_back(c, n_out, T->text) : bam_frame_device(c, n, T->text, false, &k_us);
+		const int rc = level? bam_blocks_back(c, n_out, T->text) : bam_frame_device(c, (const char*)c->rec_text.p, n, T->text, false, &k_us);
 		if (rc) { mm355_free_text_host(T); return rc; }
 		*out = T;
 	}

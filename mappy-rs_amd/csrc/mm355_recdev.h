@@ -32,6 +32,7 @@
 #include "mm355_pipeline.h"
 #include "mm355_wave.h"
 #include "mm355_sam.h"
+#include "mm355_bamsort.h"
 
 // the batch result, the tables and the reads as the kernels see them
 struct RecDev {
@@ -335,19 +336,32 @@ static int rec_text_empty(int64_t nr, mm355_text_t **out)
 
 // what a call's format-specific steps are told: the records, the bytes of the unframed text in c->rec_text, the tiles, the host clock at the
 // call's begin and after the packing; times: the format's *_TIMES variable is set
-struct RecCall { int64_t n_reads, n_lines, n_text, n_tiles; double t_begin, t_packed, t_copy; bool times; hipEvent_t bulk_ev[2] = { 0, 0 }; };   // bulk_ev: a format's own, around its bulk kernel
+struct RecCall { int64_t n_reads, n_lines, n_text, n_tiles; double t_begin, t_packed, t_copy; bool times; hipEvent_t bulk_ev[2] = { 0, 0 }; const int64_t *d_off = 0; };   // bulk_ev: a format's own, around its bulk kernel; d_off: the n_lines + 1 record offsets on the device
+
+// the result of a sorted call that writes nothing (mm355_bam.hip: BamRunDevFmt)
+static int rec_text_empty(int64_t, mm355_run_t **out)
+{
+	*out = mm355_run_alloc(0, 0);
+	return *out? 0 : MM355_ENOMEM;
+}
+
+// the format whose kernels a format launches: its own, unless it only replaces the last step of another (typedef ... Kern)
+template <typename F, typename = void> struct rec_kern { typedef F type; };
+template <typename F> struct rec_kern<F, std::void_t<typename F::Kern>> { typedef typename F::Kern type; };
 
 // The driver.  F is the format's device half: its traits struct plus Count and Write (the device sinks), TIMES_ENV (the variable that
 // asks for a line of timings on stderr, or null), bulk() (with tiles: launches the bulk kernel on the run table) and finish() (the last
 // step: the result record from the text in c->rec_text and line_off[] on the device).
-template <typename F> static int rec_format_device(mm355_ctx *c, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens,
-                                                   const char *const *quals, const int32_t *rep_len, int sam_flags, bool has_cigar, mm355_text_t **out, const RecAux &ax = RecAux())
+// Out: the result record F::finish makes (mm355_text_t; mm355_run_t for a sorted BAM call)
+template <typename F, typename Out> static int rec_format_device_to(mm355_ctx *c, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens,
+                                                                    const char *const *quals, const int32_t *rep_len, int sam_flags, bool has_cigar, Out **out, const RecAux &ax = RecAux())
 {
+	typedef typename rec_kern<F>::type K;
 	RecCall k; k.n_reads = H->n_reads; k.n_tiles = 0;
 	const char *te = F::TIMES_ENV? getenv(F::TIMES_ENV) : 0; k.times = te && *te && *te != '0';   // (read per call)
 	k.t_begin = mm355_now_ms();
 	typename F::Dev D;
-	if (int rc = rec_upload<F>(c, H, qnames, seqs, qlens, quals, rep_len, ax, sam_flags, has_cigar, &D, &k.t_packed)) return rc;
+	if (int rc = rec_upload<K>(c, H, qnames, seqs, qlens, quals, rep_len, ax, sam_flags, has_cigar, &D, &k.t_packed)) return rc;
 	const int64_t nr = k.n_reads, nl = k.n_lines = D.n_lines;
 	if (nl == 0) return rec_text_empty(nr, out);   // nothing to launch
 	hipStream_t st = c->st;
@@ -368,7 +382,7 @@ template <typename F> static int rec_format_device(mm355_ctx *c, const mm355_hit
 	HIPCHK(hipMemsetAsync(d_len + nl, 0, 8, st));
 	if constexpr (F::TILED) HIPCHK(hipMemsetAsync(d_nt + nl, 0, 8, st));
 	const unsigned grid = (unsigned)((nl + 3) / 4);
-	hipLaunchKernelGGL(k_rec_len<F>, dim3(grid), dim3(256), 0, st, D, d_len, d_aux, d_nt);
+	hipLaunchKernelGGL(k_rec_len<K>, dim3(grid), dim3(256), 0, st, D, d_len, d_aux, d_nt);
 	HIPCHK(hipGetLastError());
 	HIPCHK(rocprim::exclusive_scan(dw + w_tmp, tb, d_len, d_off, (int64_t)0, (size_t)nl + 1, rocprim::plus<int64_t>(), st));
 	if constexpr (F::TILED) HIPCHK(rocprim::exclusive_scan(dw + w_tmp, tb, d_nt, d_to, (int64_t)0, (size_t)nl + 1, rocprim::plus<int64_t>(), st));
@@ -385,10 +399,16 @@ template <typename F> static int rec_format_device(mm355_ctx *c, const mm355_hit
 		if (k.n_tiles < 0 || k.n_tiles > tot || k.n_tiles > (int64_t)INT32_MAX) return MM355_EHIP;
 	}
 	if (c->rec_text.ensure((size_t)tot + 64)) return MM355_ENOMEM;
-	hipLaunchKernelGGL(k_rec_fields<F>, dim3(grid), dim3(256), 0, st, D, d_off, d_aux, (char*)c->rec_text.p, d_run);
+	hipLaunchKernelGGL(k_rec_fields<K>, dim3(grid), dim3(256), 0, st, D, d_off, d_aux, (char*)c->rec_text.p, d_run);
 	HIPCHK(hipGetLastError());
 	if constexpr (F::TILED) if (int rc = F::bulk(c, k, d_run, d_to)) return rc;
+	k.d_off = d_off;
 	return F::finish(c, k, d_lo, out);
+}
+template <typename F> static int rec_format_device(mm355_ctx *c, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens,
+                                                   const char *const *quals, const int32_t *rep_len, int sam_flags, bool has_cigar, mm355_text_t **out, const RecAux &ax = RecAux())
+{
+	return rec_format_device_to<F, mm355_text_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, has_cigar, out, ax);
 }
 
 // the last step of a text format: the text and line_off[] copied into the result record.  k.t_copy: the host clock before the copies
@@ -407,15 +427,18 @@ static int rec_text_back(mm355_ctx *c, RecCall &k, const int64_t *d_lo, const ch
 
 // ---- the front: what follows a format's input check in mm355_{paf,sam,bam}_format.  MM355_PAF_AUTO is resolved against the format's
 // variable (read per call: the tests switch it) and its default, one of the two formatters runs, the result is stamped
+static int rec_where(int where, int64_t n_hits, const char *min_hits_env, int64_t min_hits_default)
+{
+	if (where != MM355_PAF_AUTO) return where;
+	const char *e = getenv(min_hits_env);
+	const int64_t min_hits = e && *e? atoll(e) : min_hits_default;
+	return n_hits >= min_hits? MM355_PAF_DEVICE : MM355_PAF_HOST;
+}
 template <typename Host, typename Dev> static int rec_format_where(int where, int64_t n_hits, const char *min_hits_env, int64_t min_hits_default, Host on_host, Dev on_device,
                                                                    mm355_text_t **out)
 {
 	const double t0 = mm355_now_ms();
-	if (where == MM355_PAF_AUTO) {
-		const char *e = getenv(min_hits_env);
-		const int64_t min_hits = e && *e? atoll(e) : min_hits_default;
-		where = n_hits >= min_hits? MM355_PAF_DEVICE : MM355_PAF_HOST;
-	}
+	where = rec_where(where, n_hits, min_hits_env, min_hits_default);
 	const int rc = where == MM355_PAF_DEVICE? on_device() : on_host();
 	if (rc) return rc;
 	(*out)->on_device = where == MM355_PAF_DEVICE;

@@ -16,6 +16,7 @@ import ctypes as C
 import os
 import queue
 import struct
+import tempfile
 import threading
 import time
 import weakref
@@ -35,6 +36,7 @@ _CIGAR_OPS = "MIDNSHP=X"
 # capacity constants of the reference (lib.rs:429-430, 950)
 SUB_BATCH_READS, SUB_BATCH_BASES = 9216, 96_000_000   # one GPU sub-batch of map_batch (bench.py's default shape: a 73 728-read block over eight contexts)
 WORK_QUEUE_CAP = 50000
+SORT_CHUNK_BYTES = 64 << 20        # map_bam_file(sort=True): the records one step of the merge gathers, deflates and writes
 # results a batch may hold before its workers wait for the consumer: the reference's results_queue (ArrayQueue of 50 000, lib.rs:430) plus its
 # bounded(20000) channel (lib.rs:950) -- here one channel.  (With 20 000 alone the workers stall while map_batch is still consuming its
 # iterable, which nobody reads during: -12 % on 262 144 reads.)
@@ -994,12 +996,14 @@ class Aligner:
     paf_on_device = None              # whether the device formatter wrote the text of the last map_paf / map_sam call
 
     # ---- SAM text (mm355_map_batch_sam): the lines of mappy_rs.sam_lines, formatted by the library
-    def sam_header(self, rg=b""):
+    def sam_header(self, rg=b"", *, sort=False):
         """the SAM header of this index as bytes: @HD (unsorted, grouped by query), one @SQ per contig in index order, @PG of this library;
-        rg: @RG lines (bytes, newline-terminated) to stand between the @SQ lines and @PG"""
+        rg: @RG lines (bytes, newline-terminated) to stand between the @SQ lines and @PG.  sort=True: @HD says SO:coordinate (the header of
+        a file map_bam_file(sort=True) writes)"""
         L = self._L
         sq = "".join("@SQ\tSN:%s\tLN:%d\n" % (nm, L.mm355_index_seq_len(self._idx, i)) for i, nm in enumerate(self._names()))
-        return ("@HD\tVN:1.6\tSO:unsorted\tGO:query\n" + sq).encode() + bytes(rg) + b"@PG\tID:mappy_rs\tPN:mappy_rs\n"
+        hd = "@HD\tVN:1.6\tSO:coordinate\n" if sort else "@HD\tVN:1.6\tSO:unsorted\tGO:query\n"
+        return (hd + sq).encode() + bytes(rg) + b"@PG\tID:mappy_rs\tPN:mappy_rs\n"
 
     def _sam_flags(self, cs, MD):
         if not self._mo.flag & 4:
@@ -1013,8 +1017,9 @@ class Aligner:
         a str as long as the read; softclip: minimap2 -Y.  where and `paf_on_device`: as for map_paf."""
         return self._map_records(self._L.mm355_map_batch_sam, seqs, names, quals, cs, MD, softclip, hit_only, where)
 
-    def _map_records(self, call, seqs, names, quals, cs, MD, softclip, hit_only, where):
-        """map_sam / map_bam: the arguments checked, one call of mm355_map_batch_sam or mm355_map_batch_bam, the text as bytes"""
+    def _map_records(self, call, seqs, names, quals, cs, MD, softclip, hit_only, where, run_level=None):
+        """map_sam / map_bam: the arguments checked, one call of mm355_map_batch_sam or mm355_map_batch_bam, the text as bytes.
+        run_level (map_bam(sort=True)): `call` returns a run (mm355_map_batch_bam_run); its records go through mm355_bgzf_deflate at that level"""
         flags = self._sam_flags(cs, MD)
         seqs = list(seqs)
         for s in seqs:
@@ -1038,6 +1043,26 @@ class Aligner:
         packed, narr = _ffi.pack_reads(seqs), _ffi.pack_names(names)
         sam_flags = (_ffi.SAM_SOFTCLIP if softclip else 0) | (_ffi.SAM_HIT_ONLY if hit_only else 0)
         tp = C.POINTER(_ffi.Text)()
+        if run_level is not None:
+            rp = C.POINTER(_ffi.Run)()
+            with self._lock:
+                rc = call(self._context(), C.byref(self._mo), len(seqs), packed.arr, packed.lens, narr, qarr, flags, sam_flags, int(where), C.byref(rp))
+                if rc != 0:
+                    raise RuntimeError(L.mm355_strerror(rc).decode())
+                try:
+                    r = rp.contents
+                    self.paf_on_device = bool(r.on_device)
+                    # deflated where the records were sorted; stored blocks are the host's (mm355_bgzf_wrap's rule)
+                    rc = L.mm355_bgzf_deflate(self._context(), C.cast(r.rec, C.c_char_p), r.n_bytes, _ffi.PAF_DEVICE if run_level and r.on_device else _ffi.PAF_HOST,
+                                              run_level, C.byref(tp))
+                finally:
+                    L.mm355_free_run(rp)
+            if rc != 0:
+                raise RuntimeError(L.mm355_strerror(rc).decode())
+            try:
+                return bytes(_ffi.text_view(tp))
+            finally:
+                L.mm355_free_text(tp)
         with self._lock:
             rc = call(self._context(), C.byref(self._mo), len(seqs), packed.arr, packed.lens, narr, qarr, flags, sam_flags, int(where), C.byref(tp))
         if rc != 0:
@@ -1049,7 +1074,7 @@ class Aligner:
             L.mm355_free_text(tp)
 
     # ---- BAM records (mm355_map_batch_bam): the BAM encoding of map_sam's lines in stored BGZF blocks, formed by the library
-    def map_bam(self, seqs, names=None, quals=None, cs=False, MD=False, *, softclip=False, hit_only=False, where=_ffi.PAF_AUTO, compress=False, aux=None):
+    def map_bam(self, seqs, names=None, quals=None, cs=False, MD=False, *, softclip=False, hit_only=False, where=_ffi.PAF_AUTO, compress=False, aux=None, sort=False):
         """the BAM records of `seqs` as bytes: whole BGZF blocks (stored, not compressed) without the header (bam_header()) and without the
         EOF block (BAM_EOF), in input order; one mm355_map_batch_bam call.  A record is the BAM encoding of the line map_sam writes for the
         same arguments (include/mm355.h states it field by field); the results of consecutive calls, one behind the other, continue the
@@ -1059,7 +1084,11 @@ class Aligner:
         aux: a list with bytes or None for every read -- the BAM aux tags the read brought along (MM / ML, RG, ...).  Each entry goes through
         mm355_bam_aux_split with "*"; a record that holds the whole read carries all of them behind its own tags, a hard-clipped
         supplementary or a secondary only those that do not index the read's bases (include/mm355.h).  ValueError: a malformed entry,
-        with the read's index."""
+        with the read's index.
+        sort=True: the same records in coordinate order (samtools' key: contig, position, forward before reverse, unmapped last; records of
+        equal key in input order) -- one mm355_map_batch_bam_run call, which sorts the records where they were formed, then
+        mm355_bgzf_deflate of the sorted stream.  The blocks of THIS call's records: a file of several calls is map_bam_file(sort=True)'s."""
+        ptrs = lens = mods = None
         if aux is not None:
             seqs, aux = list(seqs), list(aux)
             if len(aux) != len(seqs) or not all(a is None or isinstance(a, (bytes, bytearray)) for a in aux):
@@ -1075,6 +1104,11 @@ class Aligner:
                     raise ValueError("`aux[%d]` is no well-formed BAM aux block" % i) from None
                 lens[i] = len(keep[i])
             ptrs = (C.c_void_p * n)(*[None if k is None else C.cast(C.c_char_p(k), C.c_void_p).value for k in keep])
+        if sort:
+            L = self._L
+            return self._map_records(lambda *a: L.mm355_map_batch_bam_run(*a[:7], ptrs, lens, mods, *a[7:]), seqs, names, quals, cs, MD, softclip, hit_only, where,
+                                     run_level=1 if compress else 0)
+        if aux is not None:
             return self._map_records(lambda *a: L.mm355_map_batch_bam_aux(*a[:7], ptrs, lens, mods, *a[7:-1], 1 if compress else 0, a[-1]),
                                      seqs, names, quals, cs, MD, softclip, hit_only, where)
         if compress:
@@ -1082,9 +1116,10 @@ class Aligner:
             return self._map_records(lambda *a: L.mm355_map_batch_bam_deflate(*a[:-1], 1, a[-1]), seqs, names, quals, cs, MD, softclip, hit_only, where)
         return self._map_records(self._L.mm355_map_batch_bam, seqs, names, quals, cs, MD, softclip, hit_only, where)
 
-    def bam_header(self, compress=False, rg=b""):
-        """the BAM header of this index as BGZF blocks (compress=True: deflated): the magic, sam_header(rg) as the text, the contigs with their lengths"""
-        text, L = self.sam_header(rg), self._L
+    def bam_header(self, compress=False, rg=b"", *, sort=False):
+        """the BAM header of this index as BGZF blocks (compress=True: deflated): the magic, sam_header(rg) as the text, the contigs with their
+        lengths.  sort=True: the text is sam_header(rg, sort=True)"""
+        text, L = self.sam_header(rg, sort=bool(sort)), self._L
         refs = []
         for i, nm in enumerate(self._names()):
             b = nm.encode()
@@ -1092,7 +1127,7 @@ class Aligner:
         return bgzf_wrap(b"BAM\1" + struct.pack("<I", len(text)) + text + struct.pack("<I", len(refs)) + b"".join(refs), compress=bool(compress))
 
     def map_bam_file(self, reads_path, out_path, cs=False, MD=False, n_threads=None, sub_batch_reads=SUB_BATCH_READS, *, where=_ffi.PAF_AUTO,
-                     softclip=False, hit_only=False, compress=False, read_on_gpu=False, copy_tags=False):
+                     softclip=False, hit_only=False, compress=False, read_on_gpu=False, copy_tags=False, sort=False, tmp_dir=None):
         """maps a FASTA / FASTQ file of reads to an uncompressed BAM file (what `samtools view -u` writes; ready for `samtools sort` /
         `index` without a SAM parse): bam_header(), the records of map_bam per sub-batch in input order, BAM_EOF.  The reader, the workers,
         the bound on memory, the ".part" file and its rename, what a failure leaves behind and the returned dict are map_file's; n_lines
@@ -1106,10 +1141,24 @@ class Aligner:
         ValueError).  Which record gets which tags: include/mm355.h (a record that holds the whole read gets all, a hard-clipped
         supplementary or a secondary those that do not index bases; the tags the writer emits itself are never copied).  The header then
         has the input's @RG lines between @SQ and @PG, and the returned dict n_aux_bytes: the bytes of kept tags the reader handed on.
-        With a reads file that is no BAM the keyword copies nothing.  Works with either reader."""
+        With a reads file that is no BAM the keyword copies nothing.  Works with either reader.
+        sort=True: a coordinate-sorted BAM file (what `samtools sort` writes; @HD says SO:coordinate): exactly the stable sort of the file
+        the call writes without the keyword, by samtools' key (contig in header order, position, forward before reverse, records without a
+        contig last; records of equal key stay in input order), whatever sub_batch_reads, the worker count, the reader or the formatter.
+        Two phases.  Runs: every sub-batch is mapped and its records sorted where they were formed (mm355_map_batch_bam_run: on the device
+        a radix sort of the keys and a tiled permutation in HBM); the records of each run are appended, uncompressed, to one temporary file
+        in `tmp_dir` (default: the directory of out_path), which is unlinked as soon as it is open, and 24 bytes per record (key, length,
+        place) stay in memory.  Merge: one stable argsort of all keys, then in steps of SORT_CHUNK_BYTES the records are gathered from the
+        memory-mapped temporary file (mm355_bam_gather), framed or deflated (mm355_bgzf_deflate: on the device when compress) and written;
+        what does not fill a block is carried into the next step, so the file is bam_header(sort=True), the BGZF blocks of the whole
+        sorted stream, BAM_EOF -- the same bytes for any step or sub-batch size.  The temporary file is as large as the uncompressed
+        records, about 1.5 bytes per base (compressed runs, which the device inflater could read back, are a follow-up); memory grows with
+        the number of records, not with their bytes.  No index is written: `samtools index` reads the file.  The returned dict also has
+        n_runs, seconds_merge and n_tmp_bytes, and ms_format sums the runs' sort steps.  A failure in either phase removes the ".part"
+        file and leaves what was at out_path.  Composes with every other keyword.  map_file (SAM, PAF) has no `sort`."""
         sam_flags = (_ffi.SAM_SOFTCLIP if softclip else 0) | (_ffi.SAM_HIT_ONLY if hit_only else 0)
         return self._map_file("bam", reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags, compress=bool(compress),
-                              read_on_gpu=bool(read_on_gpu), keep_aux=_keep_of(copy_tags))
+                              read_on_gpu=bool(read_on_gpu), keep_aux=_keep_of(copy_tags), sort=bool(sort), tmp_dir=tmp_dir)
 
     def map_file(self, reads_path, out_path, cs=False, MD=False, n_threads=None, sub_batch_reads=SUB_BATCH_READS, *, where=_ffi.PAF_AUTO, format="paf",
                  read_on_gpu=False):
@@ -1135,11 +1184,13 @@ class Aligner:
             raise ValueError("`format` must be \"paf\" or \"sam\"")
         return self._map_file(format, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, 0, read_on_gpu=bool(read_on_gpu))
 
-    def _map_file(self, kind, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags, compress=False, read_on_gpu=False, keep_aux=None):
-        """map_file (kind "paf" / "sam") and map_bam_file ("bam"): reader thread, workers, ordered writer, .part file"""
+    def _map_file(self, kind, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags, compress=False, read_on_gpu=False, keep_aux=None, sort=False,
+                  tmp_dir=None):
+        """map_file (kind "paf" / "sam") and map_bam_file ("bam"): reader thread, workers, ordered writer, .part file.  sort (BAM only): the
+        workers make sorted runs, the writer spools them to a temporary file, and a merge phase writes the records (map_bam_file's docstring)"""
         sam = kind != "paf"                               # the reader keeps qualities, the call takes them and sam_flags
         flags = self._sam_flags(cs, MD) if sam else self._paf_flags(cs, MD)
-        header = self.sam_header() if kind == "sam" else self.bam_header(compress) if kind == "bam" else b""
+        header = self.sam_header() if kind == "sam" else self.bam_header(compress, sort=sort) if kind == "bam" else b""
         trailer = BAM_EOF if kind == "bam" else b""
         L = self._L
         nt = self._n_threads if n_threads is None else int(n_threads)
@@ -1165,7 +1216,7 @@ class Aligner:
             n_rg = C.c_int64()
             rg = L.mm355_fastx_bam_rg(fx, C.byref(n_rg))
             if rg:
-                header = self.bam_header(compress, C.string_at(rg, n_rg.value))
+                header = self.bam_header(compress, C.string_at(rg, n_rg.value), sort=sort)
         part = os.fspath(out_path) + (b".part" if isinstance(os.fspath(out_path), bytes) else ".part")
         try:
             out = open(part, "wb")          # (an unwritable path raises here: nothing has run, no file is left)
@@ -1207,9 +1258,18 @@ class Aligner:
                         r = rp.contents
                         n = int(r.n)
                         n_bases = int(np.ctypeslib.as_array(r.lens, shape=(n,)).sum(dtype=np.int64))
-                        tp = C.POINTER(_ffi.Text)()
+                        tp = C.POINTER(_ffi.Run if sort else _ffi.Text)()
                         n_aux = 0
-                        if keep_aux is not None:
+                        if sort:
+                            ap = alen = amod = None
+                            if keep_aux is not None:
+                                alen, amod = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
+                                ap = L.mm355_reads_aux(rp, C.byref(alen), C.byref(amod))
+                                if ap:
+                                    n_aux = int(np.ctypeslib.as_array(alen, shape=(n,)).sum(dtype=np.int64))
+                            rc = L.mm355_map_batch_bam_run(ctx[1], C.byref(mo), n, r.seqs, r.lens, r.names, L.mm355_reads_quals(rp), ap, alen, amod, flags,
+                                                           sam_flags, where, C.byref(tp))
+                        elif keep_aux is not None:
                             alen, amod = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
                             ap = L.mm355_reads_aux(rp, C.byref(alen), C.byref(amod))
                             if ap:
@@ -1267,28 +1327,51 @@ class Aligner:
         n_out = len(header) + len(trailer)
         ms_format = 0.0
         rd = None
+        free_result = L.mm355_free_run if sort else L.mm355_free_text
+        tmp, runs, n_tmp, seconds_merge = None, {}, 0, 0.0       # sort: the spool file, per sub-batch (keys, lengths, place in the file), its bytes
         try:
             self._names()
             out.write(header)
+            if sort:                        # (unlinked as soon as it is open: no exit path leaves it behind)
+                tmp = tempfile.TemporaryFile(dir=os.fspath(tmp_dir) if tmp_dir is not None else os.path.dirname(os.path.abspath(os.fspath(out_path))))
             rd = threading.Thread(target=reader, daemon=True)
             rd.start()
             while True:
                 with cv:
-                    while nxt not in done and not cancel.is_set() and (st["n_sub"] is None or nxt < st["n_sub"]):
+                    # in input order; the runs of a sorted file in completion order (nxt counts them)
+                    while not (done if sort else nxt in done) and not cancel.is_set() and (st["n_sub"] is None or nxt < st["n_sub"]):
                         cv.wait(0.2)
-                    if cancel.is_set() or nxt not in done:
+                    if cancel.is_set() or not (done if sort else nxt in done):
                         break
-                    tp = done.pop(nxt)
+                    k_run = next(iter(done)) if sort else nxt
+                    tp = done.pop(k_run)
                 try:
                     t = tp.contents
-                    n_lines += int(t.n_lines); n_dev += int(t.on_device); ms_format += float(t.ms_format); n_out += int(t.n_text)
-                    out.write(_ffi.text_view(tp))
+                    if sort:
+                        n = int(t.n_rec)
+                        n_lines += n; n_dev += int(t.on_device); ms_format += float(t.ms_sort)
+                        keys = np.ctypeslib.as_array(t.key, shape=(n,)).copy() if n else np.zeros(0, np.uint64)
+                        lens = np.diff(np.ctypeslib.as_array(t.rec_off, shape=(n + 1,))) if n else np.zeros(0, np.int64)
+                        runs[k_run] = (keys, lens, n_tmp)
+                        if t.n_bytes:
+                            tmp.write(memoryview((C.c_char * int(t.n_bytes)).from_address(C.addressof(t.rec.contents))))
+                        n_tmp += int(t.n_bytes)
+                    else:
+                        n_lines += int(t.n_lines); n_dev += int(t.on_device); ms_format += float(t.ms_format); n_out += int(t.n_text)
+                        out.write(_ffi.text_view(tp))
                 finally:
-                    L.mm355_free_text(tp)
+                    free_result(tp)
                     tokens.release()
                 nxt += 1
             if errors:
                 raise errors[0]
+            if sort:
+                rd.join()
+                for t in workers:           # (their contexts are back in the pool: the merge takes one)
+                    t.join()
+                t_merge = time.perf_counter()
+                n_out += self._merge_runs([runs[k] for k in sorted(runs)], tmp, n_tmp, out, level)
+                seconds_merge = time.perf_counter() - t_merge
             out.write(trailer)
             out.close()
             os.replace(part, out_path)
@@ -1310,7 +1393,9 @@ class Aligner:
                 if item is not None:
                     L.mm355_reads_free(item[1])
             for tp in done.values():
-                L.mm355_free_text(tp)
+                free_result(tp)
+            if tmp is not None:
+                tmp.close()
             L.mm355_fastx_close(fx)
         res = {"n_reads": st["n_reads"], "n_bases": st["n_bases"], "n_lines": n_lines, "n_sub_batches": st["n_sub"],
                "seconds": time.perf_counter() - t0, "ms_format": ms_format, "n_on_device": n_dev}
@@ -1320,7 +1405,55 @@ class Aligner:
             res["reader_on_device"] = reader_on_device
         if keep_aux is not None:
             res["n_aux_bytes"] = st["n_aux"]
+        if sort:
+            res["n_runs"], res["seconds_merge"], res["n_tmp_bytes"] = len(runs), seconds_merge, n_tmp
         return res
+
+    def _merge_runs(self, runs, tmp, n_tmp, out, level):
+        """the merge phase of map_bam_file(sort=True).  runs: per sub-batch, in input order, (keys, lengths, place of its records in tmp), the
+        records of a run in key order; tmp: the spool file of n_tmp bytes.  The stable argsort of the concatenated keys is the k-way merge
+        -- and the stable sort of the unsorted file, because ties inside a run are in input order already.  Writes the BGZF blocks of the
+        sorted stream to `out` and returns their bytes.  Array operations and one library call per step: no Python work per record."""
+        L = self._L
+        keys = np.concatenate([r[0] for r in runs]) if runs else np.zeros(0, np.uint64)
+        lens = np.concatenate([r[1] for r in runs]).astype(np.int64, copy=False) if runs else np.zeros(0, np.int64)
+        if len(keys) == 0:
+            return 0
+        src = np.concatenate([r[2] + np.cumsum(r[1], dtype=np.int64) - r[1] for r in runs])
+        order = np.argsort(keys, kind="stable")
+        lens, src = np.ascontiguousarray(lens[order]), np.ascontiguousarray(src[order])
+        end_at = np.cumsum(lens)                         # the sorted stream's offset behind every record
+        tmp.flush()
+        spool = np.memmap(tmp, dtype=np.uint8, mode="r", shape=(n_tmp,))
+        dev_ctx = self._ctx_acquire(0) if level else None   # the deflate kernels need a context; stored blocks are framed on the host
+        n_out, carry = 0, np.zeros(0, np.uint8)
+        try:
+            i, n = 0, len(lens)
+            while i < n:
+                base = int(end_at[i - 1]) if i else 0
+                j = max(i + 1, int(np.searchsorted(end_at, base + SORT_CHUNK_BYTES, side="right")))
+                n_new = int(end_at[j - 1]) - base
+                buf = np.empty(len(carry) + n_new, np.uint8)
+                buf[:len(carry)] = carry
+                _ffi.check(L.mm355_bam_gather(spool.ctypes.data, n_tmp, src[i:j].ctypes.data, lens[i:j].ctypes.data, j - i, buf.ctypes.data + len(carry), n_new))
+                # whole payloads now; what is left opens the next step's buffer (the last step writes everything)
+                n_now = len(buf) if j == n else len(buf) // 0xff00 * 0xff00
+                if n_now:
+                    tp = C.POINTER(_ffi.Text)()
+                    _ffi.check(L.mm355_bgzf_deflate(dev_ctx[1] if level else None, C.cast(buf.ctypes.data, C.c_char_p), n_now, _ffi.PAF_DEVICE if level else _ffi.PAF_HOST,
+                                                    level, C.byref(tp)))
+                    try:
+                        n_out += int(tp.contents.n_text)
+                        out.write(_ffi.text_view(tp))
+                    finally:
+                        L.mm355_free_text(tp)
+                carry = buf[n_now:].copy()
+                i = j
+        finally:
+            del spool
+            if dev_ctx is not None:
+                self._ctx_release(dev_ctx)
+        return n_out
 
     def _stage_runner(self):
         """per-stage access to the same kernels (parity tests, kernel bench)"""

@@ -72,6 +72,11 @@ class Text(C.Structure):       # mm355_text_t: the PAF or SAM lines of one batch
                 ("text", C.POINTER(C.c_char)), ("ms_format", C.c_double), ("on_device", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Run(C.Structure):        # mm355_run_t: the BAM records of one call in coordinate order, unframed, with their keys and offsets
+    _fields_ = [("n_rec", C.c_int64), ("n_bytes", C.c_int64), ("key", C.POINTER(C.c_uint64)), ("rec_off", C.POINTER(C.c_int64)),
+                ("rec", C.POINTER(C.c_char)), ("ms_sort", C.c_double), ("on_device", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Reads(C.Structure):      # mm355_reads_t: one sub-batch of the streaming FASTA / FASTQ reader
     _fields_ = [("n", C.c_int64), ("seqs", C.POINTER(C.c_char_p)), ("lens", C.POINTER(C.c_int32)), ("names", C.POINTER(C.c_char_p))]
 
@@ -124,6 +129,7 @@ EXPORTS = [
     "mm355_bam_format_deflate", "mm355_map_batch_bam_deflate", "mm355_bgzf_deflate",
     "mm355_bgzf_inflate", "mm355_fastx_open_device",
     "mm355_bam_format_aux", "mm355_map_batch_bam_aux", "mm355_bam_aux_split", "mm355_fastx_keep_aux", "mm355_reads_aux", "mm355_fastx_bam_rg",
+    "mm355_bam_sort", "mm355_map_batch_bam_run", "mm355_bam_gather", "mm355_free_run",
 ]
 
 _LIB = None
@@ -188,6 +194,11 @@ def lib():
     L.mm355_reads_aux.restype = C.POINTER(C.c_void_p)
     L.mm355_fastx_bam_rg.argtypes = [vp, i64p]
     L.mm355_fastx_bam_rg.restype = C.c_void_p
+    L.mm355_bam_sort.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, C.POINTER(C.POINTER(Run))]
+    L.mm355_map_batch_bam_run.argtypes = L.mm355_map_batch_sam.argtypes[:7] + auxp + [C.c_int, C.c_int, C.c_int, C.POINTER(C.POINTER(Run))]
+    L.mm355_bam_gather.argtypes = [vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64]
+    L.mm355_free_run.argtypes = [C.POINTER(Run)]
+    L.mm355_free_run.restype = None
     L.mm355_bgzf_deflate.argtypes = [vp, C.c_char_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.POINTER(Text))]
     L.mm355_bgzf_inflate.argtypes = [vp, C.c_char_p, C.c_int64, C.c_int, C.POINTER(C.POINTER(Text))]
     L.mm355_fastx_open_device.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(vp)]
