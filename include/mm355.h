@@ -382,6 +382,7 @@ typedef struct {
 	char *rec;                      /* the records, sorted, UNFRAMED */
 	double ms_sort;                 /* the sort step alone */
 	int32_t on_device, reserved;
+	int64_t *span;                  /* n_rec spans in the order of rec, or NULL: only the _span calls below fill it */
 } mm355_run_t;
 int mm355_bam_sort(mm355_ctx_t *ctx, const void *rec, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec, int where, mm355_run_t **out);
 int mm355_map_batch_bam_run(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
@@ -389,6 +390,55 @@ int mm355_map_batch_bam_run(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t 
                             const int32_t *aux_mod, int flags, int sam_flags, int where, mm355_run_t **out);
 int mm355_bam_gather(const void *base, int64_t base_len, const int64_t *src_off, const int64_t *len, int64_t n, void *out, int64_t out_cap);
 void mm355_free_run(mm355_run_t *r);
+
+/* --- the .bai index of a coordinate-sorted BAM file (mm355_bai.h states the rule once; SAM v1 sections 5.2 and 5.3).
+ * THE SPAN of a record (`rec` with its block_size word, any address): l_read_name is the byte at 12, n_cigar_op the uint16 at 16, flag the
+ * uint16 at 18, pos the int32 at 8, and the CIGAR words lie at 36 + l_read_name.  reflen is the 64-bit sum of the lengths (word >> 4) of
+ * the words whose op (word & 15) is M, D, N, = or X (0, 2, 3, 7, 8); every other op code, 9 to 15 included, adds nothing; reflen is 0 when
+ * flag & 4 or n_cigar_op == 0.  end = pos + max(1, reflen): the writer's own rule for `bin`, and htslib's bam_endpos.  The long-CIGAR
+ * form needs no case: its two placeholder words `l_seq S, reflen N` sum to reflen, and the CG tag is not read.
+ *   span = end << 1 | (flag >> 2 & 1)
+ * The _span calls take the arguments of their siblings and also fill run->span, n_rec entries in the order of rec: on the host serially,
+ * on the device by k_rec_span (mm355_bam.hip) on the sorted stream where it lies in HBM -- a wave per record, the words lane-strided from
+ * aligned dwords shifted into place, a 64-bit wave sum -- so that 8 more bytes per record cross to the host.  MM355_EINVAL, before
+ * anything is launched: a record whose 36 + l_read_name + 4 * n_cigar_op passes its length.  The calls without _span are these without the
+ * span: they launch, copy and return what they always did, and their run->span is NULL.  MM355_BAM_TIMES=1: the bam_sort_times line of a
+ * _span call on the device ends with k_rec_span_us.
+ * THE BUILDER is host code and takes keys, spans, lengths and BGZF blocks -- never record bytes.
+ *   mm355_bai_open     n_ref contigs; first_block_at: the file offset of the first block of records (the length of the header blocks)
+ *   mm355_bai_records  n records in FILE ORDER, repeatable: record i has ref = key >> 32 (as int32), beg = pos = ((uint32)key >> 1) - 1,
+ *                      end = span >> 1, the unmapped bit span & 1 and len[i] bytes; u_i, the running sum of the lengths, is its offset in
+ *                      the unframed stream
+ *   mm355_bai_blocks   n bytes of whole BGZF blocks as they were just written behind those before, repeatable: walked by BSIZE
+ *                      (mm355_bgzfwalk.h); a block's size and ISIZE are noted.  No block is assumed to hold 0xff00 bytes.
+ *   mm355_bai_finish   the bytes of the .bai as a text (free: mm355_free_text; n_reads / n_lines: the bins' chunks before / after the
+ *                      finishing merges).  May be called again after more records or blocks.
+ *   mm355_bai_close
+ * Virtual offsets: V(u) = coffset(b) << 16 | (u - isum(b)), b the first block with isum(b + 1) > u -- blocks of ISIZE 0 are passed over;
+ * for u the stream's length b is one past the last block, uoffset 0.  vb_i = V(u_i), ve_i = V(u_{i+1}).
+ * Records with ref < 0 only count in n_no_coor.  bin = reg2bin(beg, end) of section 5.3, recomputed, not taken from the record.  Raw
+ * chunks: the maximal runs of consecutive records of equal (ref, bin), [vb of the first, ve of the last) (hts_idx_push's rule).  Linear
+ * index: for w in beg >> 14 .. (end - 1) >> 14, ioffset[ref][w] is the vb of the first record in file order that touches w; n_intv is one
+ * past the largest touched w; an untouched window takes the value of the next touched one above it.  Pseudo-bin 37450 per ref with records:
+ * the chunks (vb of its first record, ve of its last) and (n_mapped, n_unmapped) -- unmapped is the flag bit.  Finishing a ref, in the
+ * spirit of htslib's compress_binning (no claim of byte equality with samtools): level 5 down to 1, bins ascending, a bin is emptied into
+ * its parent (b - 1) >> 3 (created if absent) and removed when (max end >> 16) - (min beg >> 16) < 0x10000 over the chunks it then holds
+ * -- so a merge can cascade; then every bin's chunks are sorted by (beg, end) and merged while next.beg >> 16 <= prev.end >> 16, end = max.
+ * Bytes: "BAI\1", n_ref; per ref n_bin, the bins ASCENDING BY NUMBER with 37450 last (bin, n_chunk, the chunks), n_intv and the offsets;
+ * n_no_coor as a trailing uint64.  A ref without records has n_bin = 0 and n_intv = 0.  The file is a pure function of the BAM file.
+ * MM355_EINVAL: keys that do not ascend (an unsorted stream has no index; also across calls), ref >= n_ref, pos < 0 on a placed record,
+ * end > 2^29 (or end <= pos), a length below 37 -- all n records of a call are checked before one is taken; bytes that are not whole BGZF
+ * blocks; at finish, ISIZEs that do not sum to the records' lengths.  n_ref < 0 or first_block_at < 0 at open. */
+int mm355_bam_sort_span(mm355_ctx_t *ctx, const void *rec, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec, int where, mm355_run_t **out);
+int mm355_map_batch_bam_run_span(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
+                                 const char *const *names, const char *const *quals, const uint8_t *const *aux, const int32_t *aux_len,
+                                 const int32_t *aux_mod, int flags, int sam_flags, int where, mm355_run_t **out);
+typedef struct mm355_bai mm355_bai_t;
+int mm355_bai_open(int32_t n_ref, int64_t first_block_at, mm355_bai_t **out);
+int mm355_bai_records(mm355_bai_t *h, const uint64_t *key, const int64_t *span, const int64_t *len, int64_t n);
+int mm355_bai_blocks(mm355_bai_t *h, const void *bytes, int64_t n);
+int mm355_bai_finish(mm355_bai_t *h, mm355_text_t **out);
+void mm355_bai_close(mm355_bai_t *h);
 
 /* --- BGZF input: the inverse of mm355_bgzf_deflate.  `data` is n bytes of BGZF members (what mm355_bgzf_wrap / _deflate, bgzip or any BAM
  * writer produced): gzip members with the BC extra subfield (other subfields may stand in front of it; MTIME, XFL and OS are ignored), cdata of

@@ -21,9 +21,11 @@
 //                 16-byte pieces at DFL_STRIDE * block.  A payload that deflate would not shorten is framed exactly as k_bgzf_frame does.
 //   k_bgzf_compact  after an exclusive scan of the blocks' sizes: every block to its place, aligned 16-byte stores from shifted source dwords.
 // A sorted call (mm355_map_batch_bam_run) frames nothing: its last step puts the records into coordinate order in a second buffer
-// (k_rec_key, rocPRIM's radix sort, k_rec_sorted_len, k_rec_permute: further down) and returns them with their keys as a run.
+// (k_rec_key, rocPRIM's radix sort, k_rec_sorted_len, k_rec_permute: further down) and returns them with their keys as a run.  A call that
+// asked for spans (the .bai index: mm355_bai.h) runs k_rec_span on the sorted stream behind the permutation.
 #include "mm355_bgzfdev.h"
 #include "mm355_deflate.h"
+#include "mm355_bai.h"
 #include <rocprim/device/device_radix_sort.hpp>
 
 #define BAM_TILE 4096         // output bytes of one k_bam_bulk block: 256 threads x 16 bytes
@@ -260,15 +262,46 @@ __global__ __launch_bounds__(256) void k_rec_permute(const char *src, const int6
 	}
 }
 
+// The span of every record of the sorted stream (mm355_bai.h states it; the pieces are its functions): a wave per record.  The fixed fields by
+// byte loads; the CIGAR words, which start at any residue, lane-strided from aligned dwords shifted into place -- the dword below a word
+// starts at most 3 bytes before it, inside the record's fixed part, the one above is read only where the word reaches into it; a 64-bit sum
+// per lane and over the wave; lane 0 stores.  The word count is held to the record's length, so nothing outside the record is read.
+__global__ __launch_bounds__(256) void k_rec_span(const char *src, const int64_t *off, int64_t n, int64_t *span)
+{
+	const int lane = threadIdx.x & 63;
+	const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (j >= n) return;                        // (the whole wave)
+	const int64_t at = off[j], len = off[j + 1] - at;
+	const uint8_t *rec = (const uint8_t*)src + at;
+	const uint32_t flag = bam_rec_flag(rec), l_name = bam_rec_l_name(rec);
+	const int64_t room = (len - 36 - (int64_t)l_name) / 4;
+	uint32_t nw = bam_span_words(flag, bam_rec_n_cigar(rec));
+	if ((int64_t)nw > room) nw = room > 0? (uint32_t)room : 0u;
+	const uintptr_t w0 = (uintptr_t)(rec + 36 + l_name);
+	const int sh = (int)(w0 & 3) * 8;
+	const uint32_t *pa = (const uint32_t*)(w0 & ~(uintptr_t)3);
+	uint64_t sum = 0;
+	for (uint32_t i = (uint32_t)lane; i < nw; i += 64) {
+		uint32_t w = pa[i];
+		if (sh) w = w >> sh | pa[i + 1] << (32 - sh);
+		sum += bam_cigar_ref_len(w);
+	}
+	sum = wave_reduce_add64(sum);
+	if (lane == 0) span[j] = bam_span_of((int32_t)bam_rec_u32(rec + 8), flag, sum);
+}
+
 // ------------------------------------------------------------------ host side
 // Sorts the n records of the stream at d_src (device memory, n_bytes, readable for 8 more; record i at d_off[i], n + 1 offsets on the device)
 // into c->bam_sorted and copies the records, their keys and their new offsets into R's arrays (allocated for n and n_bytes).  The four
 // launches and the library calls between them lie between the context's two events: microseconds in *k_us.  The permute grid is sized by a
 // bound on the tiles, n_bytes / BAM_TILE + n, so that nothing crosses to the host before the one copy at the end.
-static int bam_sort_device(mm355_ctx *c, const char *d_src, int64_t n_bytes, const int64_t *d_off, int64_t n, mm355_run_t *R, double *k_us)
+// R->span (a call that asked for spans): k_rec_span on the sorted stream, before the second event, and 8 bytes more per record in the copy;
+// span_us (MM355_BAM_TIMES=1): that kernel between two events of its own
+static int bam_sort_device(mm355_ctx *c, const char *d_src, int64_t n_bytes, const int64_t *d_off, int64_t n, mm355_run_t *R, double *k_us, double *span_us = 0)
 {
 	hipStream_t st = c->st;
 	*k_us = 0;
+	if (span_us) *span_us = 0;
 	if (n == 0) return 0;
 	const int64_t max_tiles = n_bytes / BAM_TILE + n;
 	if (n > (int64_t)INT32_MAX || max_tiles > (int64_t)INT32_MAX) return MM355_EINVAL;
@@ -277,7 +310,7 @@ static int bam_sort_device(mm355_ctx *c, const char *d_src, int64_t n_bytes, con
 	(void)rocprim::exclusive_scan(nullptr, tb_scan, (int64_t*)0, (int64_t*)0, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st);
 	const size_t w8 = up256((size_t)(n + 1) * 8), w4 = up256((size_t)n * 4);
 	const size_t w_key0 = 0, w_key1 = w_key0 + w8, w_idx0 = w_key1 + w8, w_idx1 = w_idx0 + w4, w_len = w_idx1 + w4, w_noff = w_len + w8, w_nt = w_noff + w8, w_to = w_nt + w8,
-	             w_tmp = w_to + w8;
+	             w_span = w_to + w8, w_tmp = w_span + (R->span? w8 : 0);
 	if (c->bam_work.ensure(w_tmp + up256(std::max(tb_sort, tb_scan) + 256)) || c->bam_sorted.ensure((size_t)n_bytes + 64)) return MM355_ENOMEM;
 	char *dw = (char*)c->bam_work.p;
 	uint64_t *key0 = (uint64_t*)(dw + w_key0), *key1 = (uint64_t*)(dw + w_key1);
@@ -293,13 +326,23 @@ static int bam_sort_device(mm355_ctx *c, const char *d_src, int64_t n_bytes, con
 	HIPCHK(rocprim::exclusive_scan(dw + w_tmp, tb_scan, d_nt, d_to, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st));
 	hipLaunchKernelGGL(k_rec_permute, dim3((unsigned)max_tiles), dim3(256), 0, st, d_src, d_off, (const uint32_t*)idx1, (const int64_t*)d_noff, (const int64_t*)d_to, n, (char*)c->bam_sorted.p);
 	HIPCHK(hipGetLastError());
+	struct SpanEvents { hipEvent_t v[2] = { 0, 0 }; ~SpanEvents() { for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e); } } sev;   // (span_us: the kernel timed alone)
+	if (R->span) {
+		const bool timed = span_us && hipEventCreate(&sev.v[0]) == hipSuccess && hipEventCreate(&sev.v[1]) == hipSuccess;
+		if (timed) (void)hipEventRecord(sev.v[0], st);
+		hipLaunchKernelGGL(k_rec_span, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const char*)c->bam_sorted.p, (const int64_t*)d_noff, n, (int64_t*)(dw + w_span));
+		HIPCHK(hipGetLastError());
+		if (timed) (void)hipEventRecord(sev.v[1], st);
+	}
 	(void)hipEventRecord(c->ev1, st);
+	if (R->span) HIPCHK(hipMemcpyAsync(R->span, dw + w_span, (size_t)n * 8, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipMemcpyAsync(R->rec, c->bam_sorted.p, (size_t)n_bytes, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipMemcpyAsync(R->key, key1, (size_t)n * 8, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipMemcpyAsync(R->rec_off, d_noff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
 	HIPCHK(mm355_wait_stream(st));
 	if (R->rec_off[n] != n_bytes) return MM355_EHIP;           // (the lengths are a permutation of the input's)
 	float ms = 0; (void)hipEventElapsedTime(&ms, c->ev0, c->ev1); *k_us = (double)ms * 1e3;
+	if (R->span && span_us && sev.v[1]) { (void)hipEventElapsedTime(&ms, sev.v[0], sev.v[1]); *span_us = (double)ms * 1e3; }
 	return 0;
 }
 
@@ -444,13 +487,14 @@ struct BamAuxDevFmt : BamDevFmt { typedef RecDevAux Dev; };
 // The sorted call (mm355_map_batch_bam_run): the kernels, sinks and bulk step are B's -- the same instantiations an unsorted call launches --
 // and the last step sorts the records where they lie instead of framing them: the result is a run.
 // MM355_BAM_TIMES=1 (tools/sort_bench.py): a line of its own with the sort step's time between two events and k_bam_bulk's
-template <typename B> struct BamRunFmtOf : B {
+// SPAN (mm355_map_batch_bam_run_span): the run carries the records' spans, from k_rec_span behind the permutation; the line ends with its time
+template <typename B, bool SPAN = false> struct BamRunFmtOf : B {
 	typedef B Kern;
 	static int finish(mm355_ctx *c, RecCall &k, const int64_t *, mm355_run_t **out)
 	{
-		double s_us = 0, b_us = 0;
-		mm355_run_t *R = mm355_run_alloc(k.n_lines, k.n_text);
-		int rc = R? bam_sort_device(c, (const char*)c->rec_text.p, k.n_text, k.d_off, k.n_lines, R, &s_us) : MM355_ENOMEM;
+		double s_us = 0, b_us = 0, sp_us = 0;
+		mm355_run_t *R = mm355_run_alloc(k.n_lines, k.n_text, SPAN);
+		int rc = R? bam_sort_device(c, (const char*)c->rec_text.p, k.n_text, k.d_off, k.n_lines, R, &s_us, SPAN && k.times? &sp_us : 0) : MM355_ENOMEM;
 		if (rc == 0 && k.times && k.bulk_ev[1]) { float ms = 0; (void)hipEventElapsedTime(&ms, k.bulk_ev[0], k.bulk_ev[1]); b_us = (double)ms * 1e3; }   // (the stream has been waited for)
 		for (hipEvent_t &e : k.bulk_ev) if (e) { (void)hipEventDestroy(e); e = 0; }
 		if (rc) {                                  // (a copy into R's arrays may be queued: the stream first, then the free)
@@ -459,9 +503,12 @@ template <typename B> struct BamRunFmtOf : B {
 			mm355_free_run_host(R);
 			return rc;
 		}
-		if (k.times)
-			fprintf(stderr, "[mm355] bam_sort_times records %lld stream_bytes %lld tiles %lld k_rec_key_sort_permute_us %.1f k_bam_bulk_us %.1f total_ms %.3f\n", (long long)k.n_lines,
+		if (k.times) {
+			fprintf(stderr, "[mm355] bam_sort_times records %lld stream_bytes %lld tiles %lld k_rec_key_sort_permute_us %.1f k_bam_bulk_us %.1f total_ms %.3f", (long long)k.n_lines,
 			        (long long)k.n_text, (long long)k.n_tiles, s_us, b_us, mm355_now_ms() - k.t_begin);
+			if (SPAN) fprintf(stderr, " k_rec_span_us %.1f", sp_us);
+			fprintf(stderr, "\n");
+		}
 		R->ms_sort = s_us / 1e3;
 		*out = R;
 		return 0;
@@ -469,6 +516,8 @@ template <typename B> struct BamRunFmtOf : B {
 };
 typedef BamRunFmtOf<BamDevFmt> BamRunDevFmt;
 typedef BamRunFmtOf<BamAuxDevFmt> BamAuxRunDevFmt;
+typedef BamRunFmtOf<BamDevFmt, true> BamRunSpanDevFmt;
+typedef BamRunFmtOf<BamAuxDevFmt, true> BamAuxRunSpanDevFmt;
 
 // MM355_PAF_AUTO for BAM: the device formatter from this many hits on.  Measured with tools/bam_bench.py (profiles/bam_file.json, format_sweep:
 // ms_format of the two formatters on the hits of 16 .. 9216 reads, map-ont with cs, reads of N50 8 kb with qualities): the host is ahead at 16
@@ -556,16 +605,19 @@ extern "C" int mm355_bam_gather(const void *base, int64_t base_len, const int64_
 	return bam_gather(base, base_len, src_off, len, n, out, out_cap);
 }
 
-extern "C" int mm355_bam_sort(mm355_ctx_t *c, const void *rec, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec, int where, mm355_run_t **out)
+// mm355_bam_sort and, with span, mm355_bam_sort_span
+static int bam_sort_stage(mm355_ctx_t *c, const void *rec, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec, int where, bool span, mm355_run_t **out)
 {
 	if (out == 0) return MM355_EINVAL;
 	*out = 0;
 	if (where < MM355_PAF_AUTO || where > MM355_PAF_DEVICE || (where == MM355_PAF_DEVICE && c == 0)) return MM355_EINVAL;
 	if (int rc = bam_sort_check(rec, n_bytes, rec_off, n_rec)) return rc;
+	if (span)
+		if (int rc = bam_span_check(rec, rec_off, n_rec)) return rc;
 	const double t0 = mm355_now_ms();
 	// AUTO: the host, as for the bare wrap -- the bytes are the caller's, in host memory
 	if (where != MM355_PAF_DEVICE || n_rec == 0) {
-		if (int rc = bam_sort_run_host(rec, n_bytes, rec_off, n_rec, out)) return rc;
+		if (int rc = span? bam_sort_run_span_host(rec, n_bytes, rec_off, n_rec, out) : bam_sort_run_host(rec, n_bytes, rec_off, n_rec, out)) return rc;
 		(*out)->ms_sort = mm355_now_ms() - t0;
 		return 0;
 	}
@@ -573,22 +625,34 @@ extern "C" int mm355_bam_sort(mm355_ctx_t *c, const void *rec, int64_t n_bytes, 
 	if (c->rec_text.ensure((size_t)n_bytes + 64) || c->rec_work.ensure((size_t)(n_rec + 1) * 8)) return MM355_ENOMEM;
 	HIPCHK(hipMemcpyAsync(c->rec_text.p, rec, (size_t)n_bytes, hipMemcpyHostToDevice, c->st));
 	HIPCHK(hipMemcpyAsync(c->rec_work.p, rec_off, (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice, c->st));
-	mm355_run_t *R = mm355_run_alloc(n_rec, n_bytes);
+	mm355_run_t *R = mm355_run_alloc(n_rec, n_bytes, span);
 	if (R == 0) { (void)mm355_wait_stream(c->st); return MM355_ENOMEM; }     // (the uploads read the caller's memory)
-	double k_us = 0;
-	const int rc = bam_sort_device(c, (const char*)c->rec_text.p, n_bytes, (const int64_t*)c->rec_work.p, n_rec, R, &k_us);
+	double k_us = 0, sp_us = 0;
+	const bool times = bam_times_on();
+	const int rc = bam_sort_device(c, (const char*)c->rec_text.p, n_bytes, (const int64_t*)c->rec_work.p, n_rec, R, &k_us, span && times? &sp_us : 0);
 	if (rc) { (void)mm355_wait_stream(c->st); mm355_free_run_host(R); return rc; }
-	if (bam_times_on())
-		fprintf(stderr, "[mm355] bam_sort_times stage records %lld stream_bytes %lld k_rec_key_sort_permute_us %.1f total_ms %.3f\n", (long long)n_rec, (long long)n_bytes, k_us, mm355_now_ms() - t0);
+	if (times) {
+		fprintf(stderr, "[mm355] bam_sort_times stage records %lld stream_bytes %lld k_rec_key_sort_permute_us %.1f total_ms %.3f", (long long)n_rec, (long long)n_bytes, k_us, mm355_now_ms() - t0);
+		if (span) fprintf(stderr, " k_rec_span_us %.1f", sp_us);
+		fprintf(stderr, "\n");
+	}
 	R->ms_sort = k_us / 1e3; R->on_device = 1;
 	*out = R;
 	return 0;
+}
+extern "C" int mm355_bam_sort(mm355_ctx_t *c, const void *rec, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec, int where, mm355_run_t **out)
+{
+	return bam_sort_stage(c, rec, n_bytes, rec_off, n_rec, where, false, out);
+}
+extern "C" int mm355_bam_sort_span(mm355_ctx_t *c, const void *rec, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec, int where, mm355_run_t **out)
+{
+	return bam_sort_stage(c, rec, n_bytes, rec_off, n_rec, where, true, out);
 }
 
 // the records of a batch result as a run: mm355_bam_format_aux's check and its choice of formatter, then the sort where the records were formed
 static int bam_run_format(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens,
                           const char *const *quals, const int32_t *rep_len, const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod, int sam_flags,
-                          int where, mm355_run_t **out)
+                          int where, bool span, mm355_run_t **out)
 {
 	if (c == 0 || mo == 0 || H == 0 || where < MM355_PAF_AUTO || where > MM355_PAF_DEVICE) return MM355_EINVAL;
 	if (c->mi == 0) return MM355_ENOIDX;
@@ -598,8 +662,14 @@ static int bam_run_format(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_
 	if (int rc = mm355_bam_check_aux(H, nm, (mo->flag & MMF_CIGAR) != 0, qnames, seqs, qlens, rep_len, sam_flags, ax)) return rc;
 	c->bgzf_level = 0;
 	if (rec_where(where, H->n_hits, "MM355_BAM_MIN_HITS", MM355_BAM_MIN_HITS_DEFAULT) == MM355_PAF_DEVICE) {
-		const int rc = ax.aux? rec_format_device_to<BamAuxRunDevFmt, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out, ax)
-		                     : rec_format_device_to<BamRunDevFmt, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out);
+		int rc;
+		if (span) {
+			rc = ax.aux? rec_format_device_to<BamAuxRunSpanDevFmt, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out, ax)
+			           : rec_format_device_to<BamRunSpanDevFmt, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out);
+			if (rc == 0 && (*out)->span == 0 && ((*out)->span = (int64_t*)malloc(8)) == 0) { mm355_free_run_host(*out); *out = 0; return MM355_ENOMEM; }   // (the empty run)
+		} else
+			rc = ax.aux? rec_format_device_to<BamAuxRunDevFmt, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out, ax)
+			           : rec_format_device_to<BamRunDevFmt, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out);
 		if (rc == 0) (*out)->on_device = 1;
 		return rc;
 	}
@@ -610,15 +680,16 @@ static int bam_run_format(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_
 	for (int64_t i = 0; i < T->n_lines; ++i) { off[(size_t)i] = at; at += (int64_t)bam_rec_u32((const uint8_t*)T->text + at) + 4; }   // (the writer's own block_size words)
 	off[(size_t)T->n_lines] = at;
 	const double t0 = mm355_now_ms();
-	int rc = at == T->n_text? bam_sort_run_host(T->text, T->n_text, off.data(), T->n_lines, out) : MM355_EINVAL;
+	int rc = at != T->n_text? MM355_EINVAL : span? bam_span_check(T->text, off.data(), T->n_lines) : 0;
+	if (rc == 0) rc = span? bam_sort_run_span_host(T->text, T->n_text, off.data(), T->n_lines, out) : bam_sort_run_host(T->text, T->n_text, off.data(), T->n_lines, out);
 	if (rc == 0) (*out)->ms_sort = mm355_now_ms() - t0;
 	mm355_free_text_host(T);
 	return rc;
 }
 
-extern "C" int mm355_map_batch_bam_run(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
-                                       const char *const *names, const char *const *quals, const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod,
-                                       int flags, int sam_flags, int where, mm355_run_t **out)
+static int bam_map_batch_run(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
+                             const char *const *names, const char *const *quals, const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod,
+                             int flags, int sam_flags, int where, bool span, mm355_run_t **out)
 {
 	if (out == 0) return MM355_EINVAL;
 	*out = 0;
@@ -627,10 +698,63 @@ extern "C" int mm355_map_batch_bam_run(mm355_ctx_t *c, const mm355_mapopt_t *mo,
 	mm355_hits_t *H = 0; const int32_t *rep_len = 0;
 	int rc = mm355_map_batch_rl(c, mo, n_reads, seqs, lens, names, flags | MM355_OUT_TAGS, &H, &rep_len);
 	if (rc) return rc;
-	rc = bam_run_format(c, mo, H, names, seqs, lens, quals, rep_len, aux, aux_len, aux_mod, sam_flags, where, out);
+	rc = bam_run_format(c, mo, H, names, seqs, lens, quals, rep_len, aux, aux_len, aux_mod, sam_flags, where, span, out);
 	mm355_free_hits(H);
 	return rc;
 }
+extern "C" int mm355_map_batch_bam_run(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
+                                       const char *const *names, const char *const *quals, const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod,
+                                       int flags, int sam_flags, int where, mm355_run_t **out)
+{
+	return bam_map_batch_run(c, mo, n_reads, seqs, lens, names, quals, aux, aux_len, aux_mod, flags, sam_flags, where, false, out);
+}
+extern "C" int mm355_map_batch_bam_run_span(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
+                                            const char *const *names, const char *const *quals, const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod,
+                                            int flags, int sam_flags, int where, mm355_run_t **out)
+{
+	return bam_map_batch_run(c, mo, n_reads, seqs, lens, names, quals, aux, aux_len, aux_mod, flags, sam_flags, where, true, out);
+}
+
+// ---- the .bai builder (mm355_bai.h): host code, keys, spans, lengths and blocks
+struct mm355_bai { BaiBuilder b; };
+extern "C" int mm355_bai_open(int32_t n_ref, int64_t first_block_at, mm355_bai_t **out)
+{
+	if (out == 0) return MM355_EINVAL;
+	*out = 0;
+	if (n_ref < 0 || first_block_at < 0) return MM355_EINVAL;
+	mm355_bai *h = new (std::nothrow) mm355_bai;
+	if (h == 0) return MM355_ENOMEM;
+	h->b.n_ref = n_ref; h->b.first_block_at = first_block_at;
+	*out = h;
+	return 0;
+}
+extern "C" int mm355_bai_records(mm355_bai_t *h, const uint64_t *key, const int64_t *span, const int64_t *len, int64_t n)
+{
+	if (h == 0) return MM355_EINVAL;
+	try { return h->b.records(key, span, len, n); } catch (const std::bad_alloc&) { return MM355_ENOMEM; }
+}
+extern "C" int mm355_bai_blocks(mm355_bai_t *h, const void *bytes, int64_t n)
+{
+	if (h == 0) return MM355_EINVAL;
+	try { return h->b.blocks(bytes, n); } catch (const std::bad_alloc&) { return MM355_ENOMEM; }
+}
+extern "C" int mm355_bai_finish(mm355_bai_t *h, mm355_text_t **out)
+{
+	if (out == 0) return MM355_EINVAL;
+	*out = 0;
+	if (h == 0) return MM355_EINVAL;
+	try {
+		std::string o;
+		if (int rc = h->b.finish(o)) return rc;
+		mm355_text_t *T = mm355_text_alloc(0, 0, (int64_t)o.size());
+		if (T == 0) return MM355_ENOMEM;
+		memcpy(T->text, o.data(), o.size());
+		T->n_reads = h->b.n_raw_chunks; T->n_lines = h->b.n_chunks;
+		*out = T;
+		return 0;
+	} catch (const std::bad_alloc&) { return MM355_ENOMEM; }
+}
+extern "C" void mm355_bai_close(mm355_bai_t *h) { delete h; }
 
 extern "C" int mm355_bgzf_deflate(mm355_ctx_t *c, const void *data, int64_t n, int where, int level, mm355_text_t **out)
 {

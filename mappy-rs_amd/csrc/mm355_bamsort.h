@@ -78,9 +78,9 @@ inline int bam_gather(const void *base, int64_t base_len, const int64_t *src_off
 	return 0;
 }
 
-// ---- the result record (mm355_run_t): three arrays of the host's
-inline void mm355_free_run_host(mm355_run_t *r) { if (r) { free(r->key); free(r->rec_off); free(r->rec); free(r); } }
-inline mm355_run_t *mm355_run_alloc(int64_t n_rec, int64_t n_bytes)
+// ---- the result record (mm355_run_t): three arrays of the host's, and the spans (mm355_bai.h) where a call asked for them
+inline void mm355_free_run_host(mm355_run_t *r) { if (r) { free(r->key); free(r->rec_off); free(r->rec); free(r->span); free(r); } }
+inline mm355_run_t *mm355_run_alloc(int64_t n_rec, int64_t n_bytes, bool span = false)
 {
 	mm355_run_t *R = (mm355_run_t*)calloc(1, sizeof(mm355_run_t));
 	if (R == 0) return 0;
@@ -88,15 +88,16 @@ inline mm355_run_t *mm355_run_alloc(int64_t n_rec, int64_t n_bytes)
 	R->key = (uint64_t*)malloc((size_t)(n_rec > 0? n_rec : 1) * 8);
 	R->rec_off = (int64_t*)malloc((size_t)(n_rec + 1) * 8);
 	R->rec = (char*)malloc((size_t)n_bytes + 1);
-	if (R->key == 0 || R->rec_off == 0 || R->rec == 0) { mm355_free_run_host(R); return 0; }
+	if (span) R->span = (int64_t*)malloc((size_t)(n_rec > 0? n_rec : 1) * 8);
+	if (R->key == 0 || R->rec_off == 0 || R->rec == 0 || (span && R->span == 0)) { mm355_free_run_host(R); return 0; }
 	R->rec_off[0] = 0; R->rec[n_bytes] = 0;
 	return R;
 }
 
 // mm355_bam_sort on the host
-inline int bam_sort_run_host(const void *rec, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec, mm355_run_t **out)
+inline int bam_sort_run_host(const void *rec, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec, mm355_run_t **out, bool span = false)
 {
-	mm355_run_t *R = mm355_run_alloc(n_rec, n_bytes);
+	mm355_run_t *R = mm355_run_alloc(n_rec, n_bytes, span);
 	if (R == 0) return MM355_ENOMEM;
 	if (n_rec > 0) bam_sort_host(rec, rec_off, n_rec, R->key, R->rec_off, R->rec);
 	*out = R;

@@ -289,5 +289,14 @@ __device__ inline long long wave_reduce_max64(long long v)   // maximum of a 64-
 	const uint32_t rlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63), rhi = (uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), 63);
 	return (long long)(((unsigned long long)rhi << 32) | rlo);
 }
+// sum of a 64-bit value over the wave (uniform result): the halves move by DPP with 0 where a lane has no source, the add carries
+#define DPP_U64(v, ctrl, rmask) ((unsigned long long)(uint32_t)DPP_I32(0, (int)(v >> 32), ctrl, rmask) << 32 | (uint32_t)DPP_I32(0, (int)(uint32_t)v, ctrl, rmask))
+__device__ inline unsigned long long wave_reduce_add64(unsigned long long v)
+{
+	v += DPP_U64(v, 0x111, 0xf); v += DPP_U64(v, 0x112, 0xf); v += DPP_U64(v, 0x114, 0xf); v += DPP_U64(v, 0x118, 0xf);
+	v += DPP_U64(v, 0x142, 0xa); v += DPP_U64(v, 0x143, 0xc);
+	const uint32_t rlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63), rhi = (uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), 63);
+	return (unsigned long long)rhi << 32 | rlo;
+}
 
 struct key_hi32 { __host__ __device__ uint64_t operator()(const uint64_t &v) const { return v >> 32; } };

@@ -37,6 +37,7 @@ _CIGAR_OPS = "MIDNSHP=X"
 SUB_BATCH_READS, SUB_BATCH_BASES = 9216, 96_000_000   # one GPU sub-batch of map_batch (bench.py's default shape: a 73 728-read block over eight contexts)
 WORK_QUEUE_CAP = 50000
 SORT_CHUNK_BYTES = 64 << 20        # map_bam_file(sort=True): the records one step of the merge gathers, deflates and writes
+BAI_MAX_LEN = 1 << 29              # map_bam_file(index=True): the longest contig a .bai index can hold
 # results a batch may hold before its workers wait for the consumer: the reference's results_queue (ArrayQueue of 50 000, lib.rs:430) plus its
 # bounded(20000) channel (lib.rs:950) -- here one channel.  (With 20 000 alone the workers stall while map_batch is still consuming its
 # iterable, which nobody reads during: -12 % on 262 144 reads.)
@@ -1127,7 +1128,7 @@ class Aligner:
         return bgzf_wrap(b"BAM\1" + struct.pack("<I", len(text)) + text + struct.pack("<I", len(refs)) + b"".join(refs), compress=bool(compress))
 
     def map_bam_file(self, reads_path, out_path, cs=False, MD=False, n_threads=None, sub_batch_reads=SUB_BATCH_READS, *, where=_ffi.PAF_AUTO,
-                     softclip=False, hit_only=False, compress=False, read_on_gpu=False, copy_tags=False, sort=False, tmp_dir=None):
+                     softclip=False, hit_only=False, compress=False, read_on_gpu=False, copy_tags=False, sort=False, tmp_dir=None, index=False):
         """maps a FASTA / FASTQ file of reads to an uncompressed BAM file (what `samtools view -u` writes; ready for `samtools sort` /
         `index` without a SAM parse): bam_header(), the records of map_bam per sub-batch in input order, BAM_EOF.  The reader, the workers,
         the bound on memory, the ".part" file and its rename, what a failure leaves behind and the returned dict are map_file's; n_lines
@@ -1153,12 +1154,27 @@ class Aligner:
         what does not fill a block is carried into the next step, so the file is bam_header(sort=True), the BGZF blocks of the whole
         sorted stream, BAM_EOF -- the same bytes for any step or sub-batch size.  The temporary file is as large as the uncompressed
         records, about 1.5 bytes per base (compressed runs, which the device inflater could read back, are a follow-up); memory grows with
-        the number of records, not with their bytes.  No index is written: `samtools index` reads the file.  The returned dict also has
+        the number of records, not with their bytes.  The returned dict also has
         n_runs, seconds_merge and n_tmp_bytes, and ms_format sums the runs' sort steps.  A failure in either phase removes the ".part"
-        file and leaves what was at out_path.  Composes with every other keyword.  map_file (SAM, PAF) has no `sort`."""
+        file and leaves what was at out_path.  Composes with every other keyword.  map_file (SAM, PAF) has no `sort`.
+        index=True (with sort=True only: ValueError otherwise): also writes the .bai index to out_path + ".bai", from numbers the writer has
+        in hand -- no second pass over the BAM.  The workers call mm355_map_batch_bam_run_span: on the device k_rec_span sums every
+        record's CIGAR on the sorted stream in HBM, and 8 bytes per record come back with the key (32 bytes per record stay in memory
+        instead of 24).  The merge gives the ordered keys, spans and lengths to the builder once (mm355_bai_records) and, after every
+        step's mm355_bgzf_deflate, the blocks just written (mm355_bai_blocks); mm355_bai_finish makes the file's bytes (include/mm355.h
+        states the index rule).  The index goes to out_path + ".bai.part" and is renamed after the BAM's rename; a failure in any phase
+        leaves no ".part" file and what was at both paths.  A .bai holds coordinates up to 2^29: a longer contig raises ValueError, naming
+        it, before anything is opened or mapped.  The returned dict also has n_index_bytes and seconds_index (the builder's calls and the
+        write).  Without the keyword nothing changes: no byte, call, kernel argument or dict key."""
+        if index and not sort:
+            raise ValueError("`index=True` needs `sort=True`: an unsorted BAM file has no .bai index")
+        if index:
+            for i, nm in enumerate(self._names()):
+                if self._L.mm355_index_seq_len(self._idx, i) > BAI_MAX_LEN:
+                    raise ValueError("contig %s is longer than 2^29 bases: a .bai index cannot hold it" % nm)
         sam_flags = (_ffi.SAM_SOFTCLIP if softclip else 0) | (_ffi.SAM_HIT_ONLY if hit_only else 0)
         return self._map_file("bam", reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags, compress=bool(compress),
-                              read_on_gpu=bool(read_on_gpu), keep_aux=_keep_of(copy_tags), sort=bool(sort), tmp_dir=tmp_dir)
+                              read_on_gpu=bool(read_on_gpu), keep_aux=_keep_of(copy_tags), sort=bool(sort), tmp_dir=tmp_dir, index=bool(index))
 
     def map_file(self, reads_path, out_path, cs=False, MD=False, n_threads=None, sub_batch_reads=SUB_BATCH_READS, *, where=_ffi.PAF_AUTO, format="paf",
                  read_on_gpu=False):
@@ -1185,9 +1201,10 @@ class Aligner:
         return self._map_file(format, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, 0, read_on_gpu=bool(read_on_gpu))
 
     def _map_file(self, kind, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags, compress=False, read_on_gpu=False, keep_aux=None, sort=False,
-                  tmp_dir=None):
+                  tmp_dir=None, index=False):
         """map_file (kind "paf" / "sam") and map_bam_file ("bam"): reader thread, workers, ordered writer, .part file.  sort (BAM only): the
-        workers make sorted runs, the writer spools them to a temporary file, and a merge phase writes the records (map_bam_file's docstring)"""
+        workers make sorted runs, the writer spools them to a temporary file, and a merge phase writes the records (map_bam_file's docstring);
+        index (with sort): the runs carry spans, the merge feeds the .bai builder, and the index is written beside the file"""
         sam = kind != "paf"                               # the reader keeps qualities, the call takes them and sam_flags
         flags = self._sam_flags(cs, MD) if sam else self._paf_flags(cs, MD)
         header = self.sam_header() if kind == "sam" else self.bam_header(compress, sort=sort) if kind == "bam" else b""
@@ -1218,6 +1235,8 @@ class Aligner:
             if rg:
                 header = self.bam_header(compress, C.string_at(rg, n_rg.value), sort=sort)
         part = os.fspath(out_path) + (b".part" if isinstance(os.fspath(out_path), bytes) else ".part")
+        bai_path = os.fspath(out_path) + (b".bai" if isinstance(os.fspath(out_path), bytes) else ".bai")
+        bai_part = bai_path + (b".part" if isinstance(bai_path, bytes) else ".part")
         try:
             out = open(part, "wb")          # (an unwritable path raises here: nothing has run, no file is left)
         except BaseException:
@@ -1236,6 +1255,7 @@ class Aligner:
             def map_records(*a):
                 return L.mm355_map_batch_bam_deflate(*a[:-1], 1, a[-1])
         level = 1 if compress else 0
+        map_run = L.mm355_map_batch_bam_run_span if index else L.mm355_map_batch_bam_run
 
         def fail(e):
             errors.append(e)
@@ -1267,7 +1287,7 @@ class Aligner:
                                 ap = L.mm355_reads_aux(rp, C.byref(alen), C.byref(amod))
                                 if ap:
                                     n_aux = int(np.ctypeslib.as_array(alen, shape=(n,)).sum(dtype=np.int64))
-                            rc = L.mm355_map_batch_bam_run(ctx[1], C.byref(mo), n, r.seqs, r.lens, r.names, L.mm355_reads_quals(rp), ap, alen, amod, flags,
+                            rc = map_run(ctx[1], C.byref(mo), n, r.seqs, r.lens, r.names, L.mm355_reads_quals(rp), ap, alen, amod, flags,
                                                            sam_flags, where, C.byref(tp))
                         elif keep_aux is not None:
                             alen, amod = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
@@ -1329,8 +1349,11 @@ class Aligner:
         rd = None
         free_result = L.mm355_free_run if sort else L.mm355_free_text
         tmp, runs, n_tmp, seconds_merge = None, {}, 0, 0.0       # sort: the spool file, per sub-batch (keys, lengths, place in the file), its bytes
+        bai, n_index, seconds_index = C.c_void_p(), 0, 0.0       # index: the builder, the .bai's bytes, the builder's calls and the write
         try:
             self._names()
+            if index:
+                _ffi.check(L.mm355_bai_open(len(self._names()), len(header), C.byref(bai)))
             out.write(header)
             if sort:                        # (unlinked as soon as it is open: no exit path leaves it behind)
                 tmp = tempfile.TemporaryFile(dir=os.fspath(tmp_dir) if tmp_dir is not None else os.path.dirname(os.path.abspath(os.fspath(out_path))))
@@ -1352,7 +1375,7 @@ class Aligner:
                         n_lines += n; n_dev += int(t.on_device); ms_format += float(t.ms_sort)
                         keys = np.ctypeslib.as_array(t.key, shape=(n,)).copy() if n else np.zeros(0, np.uint64)
                         lens = np.diff(np.ctypeslib.as_array(t.rec_off, shape=(n + 1,))) if n else np.zeros(0, np.int64)
-                        runs[k_run] = (keys, lens, n_tmp)
+                        runs[k_run] = (keys, lens, n_tmp, np.ctypeslib.as_array(t.span, shape=(n,)).copy() if index and n else np.zeros(0, np.int64))
                         if t.n_bytes:
                             tmp.write(memoryview((C.c_char * int(t.n_bytes)).from_address(C.addressof(t.rec.contents))))
                         n_tmp += int(t.n_bytes)
@@ -1370,18 +1393,34 @@ class Aligner:
                 for t in workers:           # (their contexts are back in the pool: the merge takes one)
                     t.join()
                 t_merge = time.perf_counter()
-                n_out += self._merge_runs([runs[k] for k in sorted(runs)], tmp, n_tmp, out, level)
+                tix = [0.0]
+                n_out += self._merge_runs([runs[k] for k in sorted(runs)], tmp, n_tmp, out, level, bai if index else None, tix)
                 seconds_merge = time.perf_counter() - t_merge
+                seconds_index = tix[0]
             out.write(trailer)
             out.close()
+            if index:                       # the whole index exists as a file before either name changes
+                t_ix = time.perf_counter()
+                tp = C.POINTER(_ffi.Text)()
+                _ffi.check(L.mm355_bai_finish(bai, C.byref(tp)))
+                try:
+                    n_index = int(tp.contents.n_text)
+                    with open(bai_part, "wb") as f:
+                        f.write(_ffi.text_view(tp))
+                finally:
+                    L.mm355_free_text(tp)
+                seconds_index += time.perf_counter() - t_ix
             os.replace(part, out_path)
+            if index:
+                os.replace(bai_part, bai_path)
         except BaseException:
             cancel.set()
             out.close()
-            try:
-                os.remove(part)
-            except OSError:
-                pass
+            for p in (part, bai_part) if index else (part,):
+                try:
+                    os.remove(p)
+                except OSError:
+                    pass
             raise
         finally:
             if rd is not None:
@@ -1396,6 +1435,8 @@ class Aligner:
                 free_result(tp)
             if tmp is not None:
                 tmp.close()
+            if bai:
+                L.mm355_bai_close(bai)
             L.mm355_fastx_close(fx)
         res = {"n_reads": st["n_reads"], "n_bases": st["n_bases"], "n_lines": n_lines, "n_sub_batches": st["n_sub"],
                "seconds": time.perf_counter() - t0, "ms_format": ms_format, "n_on_device": n_dev}
@@ -1407,13 +1448,17 @@ class Aligner:
             res["n_aux_bytes"] = st["n_aux"]
         if sort:
             res["n_runs"], res["seconds_merge"], res["n_tmp_bytes"] = len(runs), seconds_merge, n_tmp
+        if index:
+            res["n_index_bytes"], res["seconds_index"] = n_index, seconds_index
         return res
 
-    def _merge_runs(self, runs, tmp, n_tmp, out, level):
+    def _merge_runs(self, runs, tmp, n_tmp, out, level, bai=None, t_index=None):
         """the merge phase of map_bam_file(sort=True).  runs: per sub-batch, in input order, (keys, lengths, place of its records in tmp), the
         records of a run in key order; tmp: the spool file of n_tmp bytes.  The stable argsort of the concatenated keys is the k-way merge
         -- and the stable sort of the unsorted file, because ties inside a run are in input order already.  Writes the BGZF blocks of the
-        sorted stream to `out` and returns their bytes.  Array operations and one library call per step: no Python work per record."""
+        sorted stream to `out` and returns their bytes.  Array operations and one library call per step: no Python work per record.
+        bai: the .bai builder -- it gets the ordered keys, spans (a run's fourth entry) and lengths once, and every step's blocks as they
+        are written; t_index[0] collects the seconds of those calls"""
         L = self._L
         keys = np.concatenate([r[0] for r in runs]) if runs else np.zeros(0, np.uint64)
         lens = np.concatenate([r[1] for r in runs]).astype(np.int64, copy=False) if runs else np.zeros(0, np.int64)
@@ -1422,6 +1467,11 @@ class Aligner:
         src = np.concatenate([r[2] + np.cumsum(r[1], dtype=np.int64) - r[1] for r in runs])
         order = np.argsort(keys, kind="stable")
         lens, src = np.ascontiguousarray(lens[order]), np.ascontiguousarray(src[order])
+        if bai is not None:
+            t_ix = time.perf_counter()
+            keys, spans = np.ascontiguousarray(keys[order]), np.ascontiguousarray(np.concatenate([r[3] for r in runs])[order])
+            _ffi.check(L.mm355_bai_records(bai, keys.ctypes.data, spans.ctypes.data, lens.ctypes.data, len(lens)))
+            t_index[0] += time.perf_counter() - t_ix
         end_at = np.cumsum(lens)                         # the sorted stream's offset behind every record
         tmp.flush()
         spool = np.memmap(tmp, dtype=np.uint8, mode="r", shape=(n_tmp,))
@@ -1445,6 +1495,10 @@ class Aligner:
                     try:
                         n_out += int(tp.contents.n_text)
                         out.write(_ffi.text_view(tp))
+                        if bai is not None:
+                            t_ix = time.perf_counter()
+                            _ffi.check(L.mm355_bai_blocks(bai, C.addressof(tp.contents.text.contents), int(tp.contents.n_text)))
+                            t_index[0] += time.perf_counter() - t_ix
                     finally:
                         L.mm355_free_text(tp)
                 carry = buf[n_now:].copy()
