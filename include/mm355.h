@@ -381,8 +381,10 @@ typedef struct {
 	int64_t *rec_off;               /* n_rec + 1 offsets into rec */
 	char *rec;                      /* the records, sorted, UNFRAMED */
 	double ms_sort;                 /* the sort step alone */
-	int32_t on_device, reserved;
+	int32_t on_device, packed;      /* packed: 1 only from mm355_map_batch_bam_run_packed (below): rec holds BGZF members */
 	int64_t *span;                  /* n_rec spans in the order of rec, or NULL: only the _span calls below fill it */
+	int64_t n_blk;                  /* a packed run: the BGZF members in rec; otherwise 0 */
+	int64_t *blk_off;               /* a packed run: n_blk + 1 offsets of the members inside rec; otherwise NULL */
 } mm355_run_t;
 int mm355_bam_sort(mm355_ctx_t *ctx, const void *rec, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec, int where, mm355_run_t **out);
 int mm355_map_batch_bam_run(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
@@ -439,6 +441,54 @@ int mm355_bai_records(mm355_bai_t *h, const uint64_t *key, const int64_t *span, 
 int mm355_bai_blocks(mm355_bai_t *h, const void *bytes, int64_t n);
 int mm355_bai_finish(mm355_bai_t *h, mm355_text_t **out);
 void mm355_bai_close(mm355_bai_t *h);
+
+/* --- compressed runs: a sorted file whose records never lie uncompressed outside HBM (mm355_bammerge.h states the step once).
+ * A PACKED RUN is what mm355_map_batch_bam_run_packed returns: the arguments of mm355_map_batch_bam_run_span plus want_span (0: no spans,
+ * as mm355_map_batch_bam_run; anything else: spans).  Everything up to the sorted stream (and the spans) is that call's; then the stream
+ * is deflated where it lies (the device: k_bgzf_deflate / k_bgzf_compact on the sorted records in HBM, and only the members, keys,
+ * offsets and spans cross to the host; the host formatter: the serial coder, the same bytes).  Field by field:
+ *   n_rec, key, span, ms_sort, on_device   as in an unpacked run
+ *   rec_off    still the n_rec + 1 offsets into the UNFRAMED stream: rec_off[n_rec] is the raw length
+ *   rec        the BGZF members of that stream at level 1: byte for byte mm355_bgzf_deflate(level 1) of the unpacked run's rec
+ *   n_bytes    the members' byte count (never more than raw + 31 * n_blk: a payload deflate would not shorten is stored)
+ *   n_blk      the members: ceil(raw / 0xff00); member b holds raw bytes [b * 0xff00, min((b + 1) * 0xff00, raw))
+ *   blk_off    n_blk + 1 offsets of the members inside rec; blk_off[n_blk] == n_bytes
+ *   packed     1
+ * The calls without _packed return what they always did, with packed == 0, n_blk == 0 and blk_off == NULL.
+ * THE MERGE STEP takes records out of such members and writes the next BGZF blocks of the merged file.
+ *   base, base_len        the spool: the members of all runs as they were written, memory-mapped
+ *   slice_at[s], slice_bytes[s]   s < n_slice: a range of the spool that holds whole members of one run
+ *   slice_raw_at[s]       the offset, in that run's unframed stream, of the first payload byte of the slice's first member
+ *   rec_slice[i], rec_at[i], rec_len[i]   i < n_rec, in merged order: record i is rec_len[i] bytes at offset rec_at[i] of the unframed
+ *                         stream of the run slice rec_slice[i] belongs to, i.e. at rec_at[i] - slice_raw_at[...] of the slice's payloads
+ *   carry, n_carry        the raw bytes the previous step left over, fewer than 0xff00
+ *   final                 not 0: the last step -- everything is written, a short last payload too
+ *   where                 MM355_PAF_HOST (ctx may be NULL), MM355_PAF_DEVICE, or MM355_PAF_AUTO, which is the host as for mm355_bgzf_wrap
+ *   level                 0: stored blocks, 1: deflated, as for mm355_bgzf_deflate
+ *   out                   the BGZF blocks of every whole 0xff00-byte payload of `carry + records` (final: of all of it); n_lines counts
+ *                         the blocks; a step smaller than one payload gives a text of zero bytes
+ *   carry_out, n_carry_out   room for 0xff00 bytes (it may be `carry` itself): the raw bytes behind the last whole payload, and their count
+ * The blocks of consecutive steps, one behind the other, are mm355_bgzf_deflate(level) of the merged stream, whatever the steps' sizes.
+ * On the host: mm355_bgzfwalk.h walks the members, mm355_inflate.h inflates them, mm355_bam_gather's loop copies the records, the host
+ * framer or coder writes the blocks.  On the device: one upload of the compressed slices through pinned staging; the host walks the
+ * members of all slices into one table (every payload's place a prefix sum); k_bgzf_inflate inflates them into one buffer in HBM;
+ * k_rec_gather (mm355_bam.hip) copies record i from its place in that buffer to n_carry + sum(rec_len[0 .. i)) of the output stream --
+ * k_rec_permute's tile scheme and copy loop with a per-record source address: a block per 4096 output bytes of a record, a thread per
+ * aligned 16-byte store from shifted source dwords, byte stores at the ragged ends, every byte one writer; the deflate or framing
+ * kernels run on the whole payloads, and one copy brings the blocks down.
+ * MM355_EINVAL, before anything is allocated on the device or launched: a slice that passes base_len; a negative length or offset; a
+ * record whose [rec_at - slice_raw_at, + rec_len) passes the sum of the ISIZEs of its slice's members; rec_slice out of range;
+ * n_carry >= 0xff00; an unknown `where` or `level`; MM355_PAF_DEVICE without a context.  MM355_EIO: a slice that is not whole BGZF
+ * members, or a member the inflater refuses (it checks CRC-32 and ISIZE); nothing is returned then, and carry_out is untouched.
+ * MM355_BAM_TIMES=1: a device step prints a line on stderr (members in, bytes in, records, bytes out; inflate, gather and deflate each
+ * between two events). */
+int mm355_map_batch_bam_run_packed(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
+                                   const char *const *names, const char *const *quals, const uint8_t *const *aux, const int32_t *aux_len,
+                                   const int32_t *aux_mod, int flags, int sam_flags, int where, int want_span, mm355_run_t **out);
+int mm355_bam_merge_step(mm355_ctx_t *ctx, const void *base, int64_t base_len, const int64_t *slice_at, const int64_t *slice_bytes,
+                         const int64_t *slice_raw_at, int64_t n_slice, const int32_t *rec_slice, const int64_t *rec_at, const int64_t *rec_len,
+                         int64_t n_rec, const void *carry, int64_t n_carry, int final, int where, int level, mm355_text_t **out,
+                         void *carry_out, int64_t *n_carry_out);
 
 /* --- BGZF input: the inverse of mm355_bgzf_deflate.  `data` is n bytes of BGZF members (what mm355_bgzf_wrap / _deflate, bgzip or any BAM
  * writer produced): gzip members with the BC extra subfield (other subfields may stand in front of it; MTIME, XFL and OS are ignored), cdata of

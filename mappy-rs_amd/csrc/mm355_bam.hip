@@ -22,10 +22,14 @@
 //   k_bgzf_compact  after an exclusive scan of the blocks' sizes: every block to its place, aligned 16-byte stores from shifted source dwords.
 // A sorted call (mm355_map_batch_bam_run) frames nothing: its last step puts the records into coordinate order in a second buffer
 // (k_rec_key, rocPRIM's radix sort, k_rec_sorted_len, k_rec_permute: further down) and returns them with their keys as a run.  A call that
-// asked for spans (the .bai index: mm355_bai.h) runs k_rec_span on the sorted stream behind the permutation.
+// asked for spans (the .bai index: mm355_bai.h) runs k_rec_span on the sorted stream behind the permutation.  A packed run
+// (mm355_map_batch_bam_run_packed) is deflated where the permutation left it, and the merge step of such runs (mm355_bammerge.h;
+// mm355_bam_merge_step further down) is k_bgzf_inflate, k_rec_gather -- k_rec_permute's copy loop with a per-record source
+// address -- and the deflate or framing kernels, all on buffers in HBM.
 #include "mm355_bgzfdev.h"
 #include "mm355_deflate.h"
 #include "mm355_bai.h"
+#include "mm355_bammerge.h"
 #include <rocprim/device/device_radix_sort.hpp>
 
 #define BAM_TILE 4096         // output bytes of one k_bam_bulk block: 256 threads x 16 bytes
@@ -236,19 +240,20 @@ __global__ __launch_bounds__(256) void k_rec_sorted_len(const int64_t *off, cons
 	const int64_t l = j < n? off[idx[j] + 1] - off[idx[j]] : 0;
 	len[j] = l; ntile[j] = bam_tiles(l);
 }
-// src: readable for 8 bytes behind its last record (whole dwords are read around a span); new_off, tile_off: n + 1 entries; the grid may
-// be larger than the tile total (it is sized on the host by a bound): the blocks behind it leave
-__global__ __launch_bounds__(256) void k_rec_permute(const char *src, const int64_t *off, const uint32_t *idx, const int64_t *new_off, const int64_t *tile_off, int64_t n, char *out)
+// the two halves k_rec_permute and k_rec_gather share.  The work item of block b: the output record *rec and its bytes [*o0, *o1); false: none
+__device__ __forceinline__ bool rec_tile_find(const int64_t *new_off, const int64_t *tile_off, int64_t n, int64_t b, int64_t *rec, int64_t *o0, int64_t *o1)
 {
-	const int64_t b = blockIdx.x;
-	if (b >= tile_off[n]) return;              // (the whole block)
-	int64_t lo = 0, hi = n;                    // the last record whose first tile is <= b (rec_tile_run's search; every record has a tile)
+	if (b >= tile_off[n]) return false;        // (the whole block)
+	int64_t lo = 0, hi = n;                    // the last record whose first tile is <= b (rec_tile_run's search; a record without bytes has no tile and is passed over)
 	while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (tile_off[mid] <= b) lo = mid; else hi = mid; }
 	const int64_t t = b - tile_off[lo], len = new_off[lo + 1] - new_off[lo];
-	const int64_t o0 = t * BAM_TILE, o1 = o0 + BAM_TILE < len? o0 + BAM_TILE : len;   // this tile: bytes [o0, o1) of the record
-	if (o0 >= o1) return;
-	const char *s = src + off[idx[lo]];
-	char *dst = out + new_off[lo];
+	*rec = lo;
+	*o0 = t * BAM_TILE; *o1 = *o0 + BAM_TILE < len? *o0 + BAM_TILE : len;   // this tile: bytes [o0, o1) of the record
+	return *o0 < *o1;
+}
+// The copy loop: bytes [o0, o1) of the record at s to dst, by the block's 256 threads
+__device__ __forceinline__ void rec_tile_copy(const char *s, char *dst, int64_t o0, int64_t o1)
+{
 	const uintptr_t d0 = (uintptr_t)(dst + o0), d1 = (uintptr_t)(dst + o1);
 	for (uintptr_t c = (d0 & ~(uintptr_t)15) + 16 * (uintptr_t)threadIdx.x; c < d1; c += 16 * 256) {
 		if (c >= d0 && c + 16 <= d1) {
@@ -260,6 +265,30 @@ __global__ __launch_bounds__(256) void k_rec_permute(const char *src, const int6
 			for (uintptr_t a = c > d0? c : d0; a < e; ++a) *(char*)a = s[(int64_t)(a - (uintptr_t)dst)];
 		}
 	}
+}
+// src: readable for 8 bytes behind its last record (whole dwords are read around a span); new_off, tile_off: n + 1 entries; the grid may
+// be larger than the tile total (it is sized on the host by a bound): the blocks behind it leave
+__global__ __launch_bounds__(256) void k_rec_permute(const char *src, const int64_t *off, const uint32_t *idx, const int64_t *new_off, const int64_t *tile_off, int64_t n, char *out)
+{
+	int64_t lo, o0, o1;
+	if (!rec_tile_find(new_off, tile_off, n, blockIdx.x, &lo, &o0, &o1)) return;
+	rec_tile_copy(src + off[idx[lo]], out + new_off[lo], o0, o1);
+}
+
+// ---- the merge step of compressed runs (mm355_bammerge.h states it): the records of a step, in merged order, out of the inflated slices
+//   k_rec_tiles   the tile count of every record from its length; entry n of both arrays is 0, where the scans leave the totals
+//   k_rec_gather  k_rec_permute with a per-record source address: record i lies at src + at[i] (any residue) and goes to out + new_off[i].
+//                 src is readable for 8 bytes behind its last byte; the grid is sized by the same bound, the blocks behind the tiles leave
+__global__ __launch_bounds__(256) void k_rec_tiles(const int64_t *len, int64_t n, int64_t *ntile)
+{
+	const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (j <= n) ntile[j] = bam_tiles(len[j]);
+}
+__global__ __launch_bounds__(256) void k_rec_gather(const char *src, const int64_t *at, const int64_t *new_off, const int64_t *tile_off, int64_t n, char *out)
+{
+	int64_t lo, o0, o1;
+	if (!rec_tile_find(new_off, tile_off, n, blockIdx.x, &lo, &o0, &o1)) return;
+	rec_tile_copy(src + at[lo], out + new_off[lo], o0, o1);
 }
 
 // The span of every record of the sorted stream (mm355_bai.h states it; the pieces are its functions): a wave per record.  The fixed fields by
@@ -296,8 +325,9 @@ __global__ __launch_bounds__(256) void k_rec_span(const char *src, const int64_t
 // launches and the library calls between them lie between the context's two events: microseconds in *k_us.  The permute grid is sized by a
 // bound on the tiles, n_bytes / BAM_TILE + n, so that nothing crosses to the host before the one copy at the end.
 // R->span (a call that asked for spans): k_rec_span on the sorted stream, before the second event, and 8 bytes more per record in the copy;
-// span_us (MM355_BAM_TIMES=1): that kernel between two events of its own
-static int bam_sort_device(mm355_ctx *c, const char *d_src, int64_t n_bytes, const int64_t *d_off, int64_t n, mm355_run_t *R, double *k_us, double *span_us = 0)
+// span_us (MM355_BAM_TIMES=1): that kernel between two events of its own.  rec_down false (a packed run): the records stay in c->bam_sorted and
+// R->rec is not written
+static int bam_sort_device(mm355_ctx *c, const char *d_src, int64_t n_bytes, const int64_t *d_off, int64_t n, mm355_run_t *R, double *k_us, double *span_us = 0, bool rec_down = true)
 {
 	hipStream_t st = c->st;
 	*k_us = 0;
@@ -336,7 +366,7 @@ static int bam_sort_device(mm355_ctx *c, const char *d_src, int64_t n_bytes, con
 	}
 	(void)hipEventRecord(c->ev1, st);
 	if (R->span) HIPCHK(hipMemcpyAsync(R->span, dw + w_span, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipMemcpyAsync(R->rec, c->bam_sorted.p, (size_t)n_bytes, hipMemcpyDeviceToHost, st));
+	if (rec_down) HIPCHK(hipMemcpyAsync(R->rec, c->bam_sorted.p, (size_t)n_bytes, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipMemcpyAsync(R->key, key1, (size_t)n * 8, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipMemcpyAsync(R->rec_off, d_noff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
 	HIPCHK(mm355_wait_stream(st));
@@ -365,8 +395,9 @@ static int bam_frame_device(mm355_ctx *c, const char *src, int64_t n, char *to, 
 }
 
 // deflates the n bytes at src (device memory, readable for 8 more) into c->bam_out: *n_out bytes of blocks, which the caller copies; timed: the two
-// kernels and the scan between the context's two events, microseconds in *k_us, and the count of blocks that were written stored
-static int bam_deflate_device(mm355_ctx *c, const char *src, int64_t n, int64_t *n_out, bool timed, double *k_us, int64_t *n_stored)
+// kernels and the scan between the context's two events, microseconds in *k_us, and the count of blocks that were written stored; h_blk_off (a
+// packed run): the blocks' bgzf_blocks(n) + 1 offsets inside the result
+static int bam_deflate_device(mm355_ctx *c, const char *src, int64_t n, int64_t *n_out, bool timed, double *k_us, int64_t *n_stored, int64_t *h_blk_off = 0)
 {
 	hipStream_t st = c->st;
 	*n_out = 0; *n_stored = 0;
@@ -391,6 +422,7 @@ static int bam_deflate_device(mm355_ctx *c, const char *src, int64_t n, int64_t 
 	if (timed) (void)hipEventRecord(c->ev1, st);
 	int64_t *h_tot = (int64_t*)c->h_rec_out.p;
 	HIPCHK(hipMemcpyAsync(h_tot, d_off + nb, 8, hipMemcpyDeviceToHost, st));
+	if (h_blk_off) HIPCHK(hipMemcpyAsync(h_blk_off, d_off, (size_t)(nb + 1) * 8, hipMemcpyDeviceToHost, st));
 	HIPCHK(mm355_wait_stream(st));
 	if (h_tot[0] < nb * (DFL_GZ_HEAD + 8) || h_tot[0] > bgzf_size(n)) return MM355_EHIP;   // (no block is longer than its stored form)
 	*n_out = h_tot[0];
@@ -416,6 +448,27 @@ static void bam_deflate_times(const char *who, int64_t n, int64_t n_out, int64_t
 	        (long long)bgzf_blocks(n), (long long)n, (long long)n_out, (long long)n_stored, k_us);
 }
 static bool bam_times_on() { const char *te = getenv("MM355_BAM_TIMES"); return te && *te && *te != '0'; }
+
+// A packed run: the n_raw bytes of the sorted stream in c->bam_sorted (bam_sort_device has left them there, and R's other arrays are filled)
+// deflated where they lie; R->rec becomes the members, R->blk_off their offsets.  Only the members cross to the host.
+static int bam_run_pack_device(mm355_ctx *c, int64_t n_raw, mm355_run_t *R, bool times)
+{
+	const int64_t nb = bgzf_blocks(n_raw);
+	int64_t n_out = 0, n_stored = 0;
+	double d_us = 0;
+	R->blk_off = (int64_t*)calloc((size_t)nb + 1, 8);
+	if (R->blk_off == 0) return MM355_ENOMEM;
+	if (int rc = bam_deflate_device(c, (const char*)c->bam_sorted.p, n_raw, &n_out, times, &d_us, &n_stored, R->blk_off)) return rc;
+	char *z = (char*)malloc((size_t)n_out + 1);
+	if (z == 0) return MM355_ENOMEM;
+	free(R->rec);
+	R->rec = z; z[n_out] = 0;
+	if (int rc = bam_blocks_back(c, n_out, z)) return rc;
+	if (R->blk_off[nb] != n_out) return MM355_EHIP;
+	R->n_bytes = n_out; R->n_blk = nb; R->packed = 1;
+	if (times) bam_deflate_times("run", n_raw, n_out, n_stored, d_us, true);
+	return 0;
+}
 
 // BamFmt as the device writes it
 struct BamDevFmt : BamFmt {
@@ -488,13 +541,16 @@ struct BamAuxDevFmt : BamDevFmt { typedef RecDevAux Dev; };
 // and the last step sorts the records where they lie instead of framing them: the result is a run.
 // MM355_BAM_TIMES=1 (tools/sort_bench.py): a line of its own with the sort step's time between two events and k_bam_bulk's
 // SPAN (mm355_map_batch_bam_run_span): the run carries the records' spans, from k_rec_span behind the permutation; the line ends with its time
-template <typename B, bool SPAN = false> struct BamRunFmtOf : B {
+// PACKED (mm355_map_batch_bam_run_packed): the records stay in HBM and are deflated there; the run carries their BGZF members
+template <typename B, bool SPAN = false, bool PACKED = false> struct BamRunFmtOf : B {
 	typedef B Kern;
 	static int finish(mm355_ctx *c, RecCall &k, const int64_t *, mm355_run_t **out)
 	{
 		double s_us = 0, b_us = 0, sp_us = 0;
-		mm355_run_t *R = mm355_run_alloc(k.n_lines, k.n_text, SPAN);
-		int rc = R? bam_sort_device(c, (const char*)c->rec_text.p, k.n_text, k.d_off, k.n_lines, R, &s_us, SPAN && k.times? &sp_us : 0) : MM355_ENOMEM;
+		const bool packed = PACKED;
+		mm355_run_t *R = mm355_run_alloc(k.n_lines, packed? 0 : k.n_text, SPAN);
+		int rc = R? bam_sort_device(c, (const char*)c->rec_text.p, k.n_text, k.d_off, k.n_lines, R, &s_us, SPAN && k.times? &sp_us : 0, !packed) : MM355_ENOMEM;
+		if (rc == 0 && packed) rc = bam_run_pack_device(c, k.n_text, R, k.times);
 		if (rc == 0 && k.times && k.bulk_ev[1]) { float ms = 0; (void)hipEventElapsedTime(&ms, k.bulk_ev[0], k.bulk_ev[1]); b_us = (double)ms * 1e3; }   // (the stream has been waited for)
 		for (hipEvent_t &e : k.bulk_ev) if (e) { (void)hipEventDestroy(e); e = 0; }
 		if (rc) {                                  // (a copy into R's arrays may be queued: the stream first, then the free)
@@ -649,10 +705,18 @@ extern "C" int mm355_bam_sort_span(mm355_ctx_t *c, const void *rec, int64_t n_by
 	return bam_sort_stage(c, rec, n_bytes, rec_off, n_rec, where, true, out);
 }
 
+// a packed run from the device formatter, with or without spans and copied tags
+template <bool SPAN, bool PACKED> static int bam_run_device(mm355_ctx_t *c, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens,
+                                                            const char *const *quals, const int32_t *rep_len, int sam_flags, mm355_run_t **out, const RecAux &ax)
+{
+	return ax.aux? rec_format_device_to<BamRunFmtOf<BamAuxDevFmt, SPAN, PACKED>, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out, ax)
+	             : rec_format_device_to<BamRunFmtOf<BamDevFmt, SPAN, PACKED>, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out);
+}
+
 // the records of a batch result as a run: mm355_bam_format_aux's check and its choice of formatter, then the sort where the records were formed
 static int bam_run_format(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens,
                           const char *const *quals, const int32_t *rep_len, const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod, int sam_flags,
-                          int where, bool span, mm355_run_t **out)
+                          int where, bool span, bool packed, mm355_run_t **out)
 {
 	if (c == 0 || mo == 0 || H == 0 || where < MM355_PAF_AUTO || where > MM355_PAF_DEVICE) return MM355_EINVAL;
 	if (c->mi == 0) return MM355_ENOIDX;
@@ -663,7 +727,10 @@ static int bam_run_format(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_
 	c->bgzf_level = 0;
 	if (rec_where(where, H->n_hits, "MM355_BAM_MIN_HITS", MM355_BAM_MIN_HITS_DEFAULT) == MM355_PAF_DEVICE) {
 		int rc;
-		if (span) {
+		if (packed) {
+			rc = span? bam_run_device<true, true>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, out, ax) : bam_run_device<false, true>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, out, ax);
+			if (rc == 0 && span && (*out)->span == 0 && ((*out)->span = (int64_t*)malloc(8)) == 0) { mm355_free_run_host(*out); *out = 0; return MM355_ENOMEM; }   // (the empty run)
+		} else if (span) {
 			rc = ax.aux? rec_format_device_to<BamAuxRunSpanDevFmt, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out, ax)
 			           : rec_format_device_to<BamRunSpanDevFmt, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out);
 			if (rc == 0 && (*out)->span == 0 && ((*out)->span = (int64_t*)malloc(8)) == 0) { mm355_free_run_host(*out); *out = 0; return MM355_ENOMEM; }   // (the empty run)
@@ -671,6 +738,10 @@ static int bam_run_format(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_
 			rc = ax.aux? rec_format_device_to<BamAuxRunDevFmt, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out, ax)
 			           : rec_format_device_to<BamRunDevFmt, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out);
 		if (rc == 0) (*out)->on_device = 1;
+		if (rc == 0 && packed && !(*out)->packed) {                // (the empty run: no member)
+			if (((*out)->blk_off = (int64_t*)calloc(1, 8)) == 0) { mm355_free_run_host(*out); *out = 0; return MM355_ENOMEM; }
+			(*out)->packed = 1;
+		}
 		return rc;
 	}
 	mm355_text_t *T = 0;
@@ -683,13 +754,14 @@ static int bam_run_format(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_
 	int rc = at != T->n_text? MM355_EINVAL : span? bam_span_check(T->text, off.data(), T->n_lines) : 0;
 	if (rc == 0) rc = span? bam_sort_run_span_host(T->text, T->n_text, off.data(), T->n_lines, out) : bam_sort_run_host(T->text, T->n_text, off.data(), T->n_lines, out);
 	if (rc == 0) (*out)->ms_sort = mm355_now_ms() - t0;
+	if (rc == 0 && packed && (rc = bam_run_pack_host(*out)) != 0) { mm355_free_run_host(*out); *out = 0; }   // (the serial coder: the device's bytes)
 	mm355_free_text_host(T);
 	return rc;
 }
 
 static int bam_map_batch_run(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
                              const char *const *names, const char *const *quals, const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod,
-                             int flags, int sam_flags, int where, bool span, mm355_run_t **out)
+                             int flags, int sam_flags, int where, bool span, mm355_run_t **out, bool packed = false)
 {
 	if (out == 0) return MM355_EINVAL;
 	*out = 0;
@@ -698,7 +770,7 @@ static int bam_map_batch_run(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n
 	mm355_hits_t *H = 0; const int32_t *rep_len = 0;
 	int rc = mm355_map_batch_rl(c, mo, n_reads, seqs, lens, names, flags | MM355_OUT_TAGS, &H, &rep_len);
 	if (rc) return rc;
-	rc = bam_run_format(c, mo, H, names, seqs, lens, quals, rep_len, aux, aux_len, aux_mod, sam_flags, where, span, out);
+	rc = bam_run_format(c, mo, H, names, seqs, lens, quals, rep_len, aux, aux_len, aux_mod, sam_flags, where, span, packed, out);
 	mm355_free_hits(H);
 	return rc;
 }
@@ -713,6 +785,128 @@ extern "C" int mm355_map_batch_bam_run_span(mm355_ctx_t *c, const mm355_mapopt_t
                                             int flags, int sam_flags, int where, mm355_run_t **out)
 {
 	return bam_map_batch_run(c, mo, n_reads, seqs, lens, names, quals, aux, aux_len, aux_mod, flags, sam_flags, where, true, out);
+}
+extern "C" int mm355_map_batch_bam_run_packed(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
+                                              const char *const *names, const char *const *quals, const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod,
+                                              int flags, int sam_flags, int where, int want_span, mm355_run_t **out)
+{
+	return bam_map_batch_run(c, mo, n_reads, seqs, lens, names, quals, aux, aux_len, aux_mod, flags, sam_flags, where, want_span != 0, out, true);
+}
+
+// ---- the merge step of compressed runs (mm355_bammerge.h: the plan and the host step)
+// The step on the device.  One upload through the context's pinned staging: the compressed slices back to back, the member table (cdata
+// offsets rebased to the upload), every record's place in the inflated bytes, the lengths, the carry.  Then k_bgzf_inflate into
+// c->bam_sorted, the lengths' and tile counts' scans and k_rec_gather into c->rec_text behind the carry, the deflate or framing kernels on the
+// whole payloads, and the blocks, the members' status words and the leftover bytes down.  A refused member: MM355_EIO, nothing returned.
+static int bam_merge_step_device(mm355_ctx *c, const BamMergeIn &a, const BamMergePlan &p, mm355_text_t **out, void *carry_out, int64_t *n_carry_out)
+{
+	hipStream_t st = c->st;
+	const int64_t n = a.n_rec, n_mem = (int64_t)p.mem.size();
+	const int64_t max_tiles = p.n_rec_bytes / BAM_TILE + n;
+	if (max_tiles > (int64_t)INT32_MAX || bgzf_blocks(p.n_now) > (int64_t)INT32_MAX) return MM355_EINVAL;
+	const bool times = bam_times_on();
+	HIPCHK(hipSetDevice(c->dev));
+	// the upload's layout
+	const size_t u_mem = up256((size_t)p.n_in + 64), u_src = u_mem + up256((size_t)n_mem * sizeof(BgzfMember)), u_len = u_src + up256((size_t)n * 8),
+	             u_carry = u_len + up256((size_t)(n + 1) * 8), u_end = u_carry + up256((size_t)a.n_carry);
+	size_t tb_scan = 0;
+	(void)rocprim::exclusive_scan(nullptr, tb_scan, (int64_t*)0, (int64_t*)0, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st);
+	const size_t w8 = up256((size_t)(n + 1) * 8), w_nt = 0, w_noff = w8, w_to = 2 * w8, w_status = 3 * w8, w_tmp = w_status + up256((size_t)n_mem * 4 + 4);
+	const size_t h_status = 64;                // (the first bytes of h_rec_out are the deflate stage's total)
+	if (c->h_rec_in.ensure(u_end) || c->rec_in.ensure(u_end) || c->rec_work.ensure(w_tmp + up256(tb_scan + 256)) || c->bam_sorted.ensure((size_t)p.n_inflated + 64) ||
+	    c->rec_text.ensure((size_t)p.n_stream + 64) || c->h_rec_out.ensure(h_status + (size_t)n_mem * 4 + 64)) return MM355_ENOMEM;
+	char *h = (char*)c->h_rec_in.p, *d = (char*)c->rec_in.p, *dw = (char*)c->rec_work.p;
+	{
+		int64_t at = 0;                        // the slices back to back; a member's cdata moves with its slice
+		BgzfMember *hm = (BgzfMember*)(h + u_mem);
+		size_t m = 0;
+		for (int64_t s = 0; s < a.n_slice; ++s) {
+			if (a.slice_bytes[s]) memcpy(h + at, (const char*)a.base + a.slice_at[s], (size_t)a.slice_bytes[s]);
+			for (; m < (size_t)p.slice_mem[(size_t)s + 1]; ++m) { hm[m] = p.mem[m]; hm[m].c_off += at - a.slice_at[s]; }
+			at += a.slice_bytes[s];
+		}
+		if (n) { memcpy(h + u_src, p.src.data(), (size_t)n * 8); memcpy(h + u_len, a.rec_len, (size_t)n * 8); }
+		*(int64_t*)(h + u_len + (size_t)n * 8) = 0;
+		if (a.n_carry) memcpy(h + u_carry, a.carry, (size_t)a.n_carry);
+	}
+	struct StepEvents { hipEvent_t v[4] = { 0, 0, 0, 0 }; ~StepEvents() { for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e); } } ev;   // (inflate and gather, each timed alone)
+	bool timed = times;
+	for (int i = 0; i < 4 && timed; ++i) timed = hipEventCreate(&ev.v[i]) == hipSuccess;
+	HIPCHK(hipMemcpyAsync(d, h, u_end, hipMemcpyHostToDevice, st));
+	int32_t *d_status = (int32_t*)(dw + w_status), *h_st = (int32_t*)((char*)c->h_rec_out.p + h_status);
+	if (timed) (void)hipEventRecord(ev.v[0], st);
+	if (n_mem) {
+		if (int rc = bgzf_inflate_launch(c->dev, st, (const unsigned char*)d, (const BgzfMember*)(d + u_mem), n_mem, (char*)c->bam_sorted.p, d_status)) return rc;
+	}
+	if (timed) (void)hipEventRecord(ev.v[1], st);      // (the kernel alone: the status words' copy comes behind the event)
+	if (n_mem) HIPCHK(hipMemcpyAsync(h_st, d_status, (size_t)n_mem * 4, hipMemcpyDeviceToHost, st));
+	char *stream = (char*)c->rec_text.p;
+	if (a.n_carry) HIPCHK(hipMemcpyAsync(stream, d + u_carry, (size_t)a.n_carry, hipMemcpyDeviceToDevice, st));
+	if (n) {
+		const int64_t *d_len = (const int64_t*)(d + u_len);
+		int64_t *d_nt = (int64_t*)(dw + w_nt), *d_noff = (int64_t*)(dw + w_noff), *d_to = (int64_t*)(dw + w_to);
+		hipLaunchKernelGGL(k_rec_tiles, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st, d_len, n, d_nt);
+		HIPCHK(hipGetLastError());
+		HIPCHK(rocprim::exclusive_scan(dw + w_tmp, tb_scan, d_len, d_noff, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st));
+		HIPCHK(rocprim::exclusive_scan(dw + w_tmp, tb_scan, d_nt, d_to, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st));
+		if (timed) (void)hipEventRecord(ev.v[2], st);  // (k_rec_gather alone: the carry's copy, k_rec_tiles and the scans lie in front of the event)
+		if (max_tiles > 0) {
+			hipLaunchKernelGGL(k_rec_gather, dim3((unsigned)max_tiles), dim3(256), 0, st, (const char*)c->bam_sorted.p, (const int64_t*)(d + u_src), (const int64_t*)d_noff,
+			                   (const int64_t*)d_to, n, stream + a.n_carry);
+			HIPCHK(hipGetLastError());
+		}
+	}
+	if (timed) { if (n == 0) (void)hipEventRecord(ev.v[2], st); (void)hipEventRecord(ev.v[3], st); }
+	// the blocks of the whole payloads
+	int64_t n_out = bgzf_size(p.n_now), n_stored = 0;
+	double f_us = 0;
+	if (a.level && p.n_now)
+		if (int rc = bam_deflate_device(c, stream, p.n_now, &n_out, timed, &f_us, &n_stored)) return rc;
+	mm355_text_t *T = mm355_text_alloc(0, bgzf_blocks(p.n_now), n_out);
+	if (T == 0) { (void)mm355_wait_stream(st); return MM355_ENOMEM; }
+	T->line_off[0] = 0;
+	int rc = a.level? bam_blocks_back(c, p.n_now? n_out : 0, T->text) : bam_frame_device(c, stream, p.n_now, T->text, timed, &f_us);
+	if (rc == 0 && p.n_now == 0 && mm355_wait_stream(st) != hipSuccess) rc = MM355_EHIP;     // (bam_frame_device has nothing to wait for then)
+	if (rc == 0)
+		for (int64_t b = 0; b < n_mem; ++b)
+			if (h_st[b]) { rc = MM355_EIO; break; }
+	if (rc == 0 && p.n_left) {                 // (carry_out may be `carry`: the upload that read it has long been waited for)
+		hipError_t e = hipMemcpyAsync(carry_out, stream + p.n_now, (size_t)p.n_left, hipMemcpyDeviceToHost, st);
+		if (e == hipSuccess) e = mm355_wait_stream(st);
+		if (e != hipSuccess) rc = MM355_EHIP;
+	}
+	if (rc) { (void)mm355_wait_stream(st); mm355_free_text_host(T); return rc; }
+	*n_carry_out = p.n_left;
+	if (timed) {
+		float ms_i = 0, ms_g = 0;
+		(void)hipEventElapsedTime(&ms_i, ev.v[0], ev.v[1]); (void)hipEventElapsedTime(&ms_g, ev.v[2], ev.v[3]);
+		fprintf(stderr, "[mm355] bam_merge_times members %lld bytes_in %lld records %lld bytes_out %lld k_bgzf_inflate_us %.1f k_rec_gather_us %.1f %s %.1f\n", (long long)n_mem,
+		        (long long)p.n_in, (long long)n, (long long)n_out, (double)ms_i * 1e3, (double)ms_g * 1e3, a.level? "k_bgzf_deflate_compact_us" : "k_bgzf_frame_us", f_us);
+	}
+	T->on_device = 1;
+	*out = T;
+	return 0;
+}
+
+extern "C" int mm355_bam_merge_step(mm355_ctx_t *c, const void *base, int64_t base_len, const int64_t *slice_at, const int64_t *slice_bytes,
+                                    const int64_t *slice_raw_at, int64_t n_slice, const int32_t *rec_slice, const int64_t *rec_at, const int64_t *rec_len,
+                                    int64_t n_rec, const void *carry, int64_t n_carry, int final, int where, int level, mm355_text_t **out,
+                                    void *carry_out, int64_t *n_carry_out)
+{
+	if (out == 0) return MM355_EINVAL;
+	*out = 0;
+	if (carry_out == 0 || n_carry_out == 0 || where < MM355_PAF_AUTO || where > MM355_PAF_DEVICE || (where == MM355_PAF_DEVICE && c == 0)) return MM355_EINVAL;
+	const BamMergeIn a = { base, base_len, slice_at, slice_bytes, slice_raw_at, n_slice, rec_slice, rec_at, rec_len, n_rec, carry, n_carry, final, level };
+	try {
+		BamMergePlan p;
+		if (int rc = bam_merge_plan(a, p)) return rc;
+		const double t0 = mm355_now_ms();
+		// AUTO: the host, as for the bare wrap
+		const int rc = where == MM355_PAF_DEVICE? bam_merge_step_device(c, a, p, out, carry_out, n_carry_out) : bam_merge_step_host(a, p, out, carry_out, n_carry_out);
+		if (rc) { if (*out) { mm355_free_text_host(*out); *out = 0; } return rc; }
+		(*out)->ms_format = mm355_now_ms() - t0;
+		return 0;
+	} catch (const std::bad_alloc&) { return MM355_ENOMEM; }
 }
 
 // ---- the .bai builder (mm355_bai.h): host code, keys, spans, lengths and blocks

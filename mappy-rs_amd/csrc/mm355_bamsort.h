@@ -79,7 +79,7 @@ inline int bam_gather(const void *base, int64_t base_len, const int64_t *src_off
 }
 
 // ---- the result record (mm355_run_t): three arrays of the host's, and the spans (mm355_bai.h) where a call asked for them
-inline void mm355_free_run_host(mm355_run_t *r) { if (r) { free(r->key); free(r->rec_off); free(r->rec); free(r->span); free(r); } }
+inline void mm355_free_run_host(mm355_run_t *r) { if (r) { free(r->key); free(r->rec_off); free(r->rec); free(r->span); free(r->blk_off); free(r); } }
 inline mm355_run_t *mm355_run_alloc(int64_t n_rec, int64_t n_bytes, bool span = false)
 {
 	mm355_run_t *R = (mm355_run_t*)calloc(1, sizeof(mm355_run_t));

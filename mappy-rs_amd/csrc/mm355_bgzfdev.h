@@ -3,6 +3,10 @@
 #pragma once
 #include "mm355_recdev.h"
 #include "mm355_bam.h"
+#include "mm355_bgzfwalk.h"
+
+// mm355_inflate.hip: k_bgzf_inflate on a caller's stream (the merge step of mm355_bam.hip launches it between its own kernels)
+int bgzf_inflate_launch(int dev, hipStream_t st, const unsigned char *d_in, const BgzfMember *d_mem, int64_t n_mem, char *d_out, int32_t *d_status);
 
 // len bytes from src to dst by the block's threads: a thread owns an aligned 16-byte piece of the destination, the ragged ends are byte
 // stores; src is readable for 8 bytes more (whole dwords are read around a span)

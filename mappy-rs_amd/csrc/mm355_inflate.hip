@@ -97,6 +97,15 @@ static int inflate_grid(int dev, int64_t n_mem, unsigned *grid)
 	*grid = (unsigned)(n_mem < n_cu? n_mem : n_cu);
 	return 0;
 }
+// k_bgzf_inflate on a caller's stream, for the merge step of mm355_bam.hip: the n_mem members of the table d_mem, cdata in d_in, into d_out
+int bgzf_inflate_launch(int dev, hipStream_t st, const unsigned char *d_in, const BgzfMember *d_mem, int64_t n_mem, char *d_out, int32_t *d_status)
+{
+	unsigned grid = 1;
+	if (int rc = inflate_grid(dev, n_mem, &grid)) return rc;
+	hipLaunchKernelGGL(k_bgzf_inflate, dim3(grid), dim3(BGZF_LANES), 0, st, d_in, d_mem, n_mem, d_out, d_status);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
 // a refused member among status[0 .. n)?
 static bool inflate_refused(const int32_t *status, int64_t n, bool say)
 {

@@ -1128,7 +1128,8 @@ class Aligner:
         return bgzf_wrap(b"BAM\1" + struct.pack("<I", len(text)) + text + struct.pack("<I", len(refs)) + b"".join(refs), compress=bool(compress))
 
     def map_bam_file(self, reads_path, out_path, cs=False, MD=False, n_threads=None, sub_batch_reads=SUB_BATCH_READS, *, where=_ffi.PAF_AUTO,
-                     softclip=False, hit_only=False, compress=False, read_on_gpu=False, copy_tags=False, sort=False, tmp_dir=None, index=False):
+                     softclip=False, hit_only=False, compress=False, read_on_gpu=False, copy_tags=False, sort=False, tmp_dir=None, index=False,
+                     tmp_compress=False):
         """maps a FASTA / FASTQ file of reads to an uncompressed BAM file (what `samtools view -u` writes; ready for `samtools sort` /
         `index` without a SAM parse): bam_header(), the records of map_bam per sub-batch in input order, BAM_EOF.  The reader, the workers,
         the bound on memory, the ".part" file and its rename, what a failure leaves behind and the returned dict are map_file's; n_lines
@@ -1153,7 +1154,7 @@ class Aligner:
         memory-mapped temporary file (mm355_bam_gather), framed or deflated (mm355_bgzf_deflate: on the device when compress) and written;
         what does not fill a block is carried into the next step, so the file is bam_header(sort=True), the BGZF blocks of the whole
         sorted stream, BAM_EOF -- the same bytes for any step or sub-batch size.  The temporary file is as large as the uncompressed
-        records, about 1.5 bytes per base (compressed runs, which the device inflater could read back, are a follow-up); memory grows with
+        records, about 1.5 bytes per base (tmp_compress=True, below, spools compressed runs instead); memory grows with
         the number of records, not with their bytes.  The returned dict also has
         n_runs, seconds_merge and n_tmp_bytes, and ms_format sums the runs' sort steps.  A failure in either phase removes the ".part"
         file and leaves what was at out_path.  Composes with every other keyword.  map_file (SAM, PAF) has no `sort`.
@@ -1165,7 +1166,17 @@ class Aligner:
         states the index rule).  The index goes to out_path + ".bai.part" and is renamed after the BAM's rename; a failure in any phase
         leaves no ".part" file and what was at both paths.  A .bai holds coordinates up to 2^29: a longer contig raises ValueError, naming
         it, before anything is opened or mapped.  The returned dict also has n_index_bytes and seconds_index (the builder's calls and the
-        write).  Without the keyword nothing changes: no byte, call, kernel argument or dict key."""
+        write).  Without the keyword nothing changes: no byte, call, kernel argument or dict key.
+        tmp_compress=True (with sort=True only: ValueError otherwise): the same file and the same .bai, byte for byte, from COMPRESSED runs
+        -- no record lies uncompressed outside HBM.  The workers call mm355_map_batch_bam_run_packed: the sorted stream of a sub-batch is
+        deflated where it lies, and only its BGZF members, keys, offsets and spans come to the host; the temporary file holds members.
+        The merge keeps its one stable argsort; a step takes from every run a contiguous range of records, hence of members, and one
+        mm355_bam_merge_step call inflates those members on the device, gathers the records behind the bytes the last step left over
+        (k_rec_gather), and frames or deflates every whole payload -- on the device whatever `compress` is.  The returned dict's
+        n_tmp_bytes is the temporary file's real size, and it gains n_tmp_raw_bytes, the bytes of the records it holds.  Not the default:
+        README, "Compressed runs", has the measurements."""
+        if tmp_compress and not sort:
+            raise ValueError("`tmp_compress=True` needs `sort=True`: only a sorted BAM file is written from runs")
         if index and not sort:
             raise ValueError("`index=True` needs `sort=True`: an unsorted BAM file has no .bai index")
         if index:
@@ -1174,7 +1185,7 @@ class Aligner:
                     raise ValueError("contig %s is longer than 2^29 bases: a .bai index cannot hold it" % nm)
         sam_flags = (_ffi.SAM_SOFTCLIP if softclip else 0) | (_ffi.SAM_HIT_ONLY if hit_only else 0)
         return self._map_file("bam", reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags, compress=bool(compress),
-                              read_on_gpu=bool(read_on_gpu), keep_aux=_keep_of(copy_tags), sort=bool(sort), tmp_dir=tmp_dir, index=bool(index))
+                              read_on_gpu=bool(read_on_gpu), keep_aux=_keep_of(copy_tags), sort=bool(sort), tmp_dir=tmp_dir, index=bool(index), tmp_compress=bool(tmp_compress))
 
     def map_file(self, reads_path, out_path, cs=False, MD=False, n_threads=None, sub_batch_reads=SUB_BATCH_READS, *, where=_ffi.PAF_AUTO, format="paf",
                  read_on_gpu=False):
@@ -1201,10 +1212,11 @@ class Aligner:
         return self._map_file(format, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, 0, read_on_gpu=bool(read_on_gpu))
 
     def _map_file(self, kind, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags, compress=False, read_on_gpu=False, keep_aux=None, sort=False,
-                  tmp_dir=None, index=False):
+                  tmp_dir=None, index=False, tmp_compress=False):
         """map_file (kind "paf" / "sam") and map_bam_file ("bam"): reader thread, workers, ordered writer, .part file.  sort (BAM only): the
         workers make sorted runs, the writer spools them to a temporary file, and a merge phase writes the records (map_bam_file's docstring);
-        index (with sort): the runs carry spans, the merge feeds the .bai builder, and the index is written beside the file"""
+        index (with sort): the runs carry spans, the merge feeds the .bai builder, and the index is written beside the file;
+        tmp_compress (with sort): the runs are packed (BGZF members), and the merge inflates, gathers and deflates them on the device"""
         sam = kind != "paf"                               # the reader keeps qualities, the call takes them and sam_flags
         flags = self._sam_flags(cs, MD) if sam else self._paf_flags(cs, MD)
         header = self.sam_header() if kind == "sam" else self.bam_header(compress, sort=sort) if kind == "bam" else b""
@@ -1256,6 +1268,9 @@ class Aligner:
                 return L.mm355_map_batch_bam_deflate(*a[:-1], 1, a[-1])
         level = 1 if compress else 0
         map_run = L.mm355_map_batch_bam_run_span if index else L.mm355_map_batch_bam_run
+        if tmp_compress:
+            def map_run(*a):
+                return L.mm355_map_batch_bam_run_packed(*a[:-1], 1 if index else 0, a[-1])
 
         def fail(e):
             errors.append(e)
@@ -1349,6 +1364,7 @@ class Aligner:
         rd = None
         free_result = L.mm355_free_run if sort else L.mm355_free_text
         tmp, runs, n_tmp, seconds_merge = None, {}, 0, 0.0       # sort: the spool file, per sub-batch (keys, lengths, place in the file), its bytes
+        n_tmp_raw = 0                                            # tmp_compress: the bytes of the records the spool's members hold
         bai, n_index, seconds_index = C.c_void_p(), 0, 0.0       # index: the builder, the .bai's bytes, the builder's calls and the write
         try:
             self._names()
@@ -1376,6 +1392,9 @@ class Aligner:
                         keys = np.ctypeslib.as_array(t.key, shape=(n,)).copy() if n else np.zeros(0, np.uint64)
                         lens = np.diff(np.ctypeslib.as_array(t.rec_off, shape=(n + 1,))) if n else np.zeros(0, np.int64)
                         runs[k_run] = (keys, lens, n_tmp, np.ctypeslib.as_array(t.span, shape=(n,)).copy() if index and n else np.zeros(0, np.int64))
+                        if tmp_compress:        # a packed run: rec holds members; where each begins, and the raw bytes they hold
+                            runs[k_run] += (np.ctypeslib.as_array(t.blk_off, shape=(int(t.n_blk) + 1,)).copy(),)
+                            n_tmp_raw += int(t.rec_off[n])
                         if t.n_bytes:
                             tmp.write(memoryview((C.c_char * int(t.n_bytes)).from_address(C.addressof(t.rec.contents))))
                         n_tmp += int(t.n_bytes)
@@ -1394,7 +1413,8 @@ class Aligner:
                     t.join()
                 t_merge = time.perf_counter()
                 tix = [0.0]
-                n_out += self._merge_runs([runs[k] for k in sorted(runs)], tmp, n_tmp, out, level, bai if index else None, tix)
+                merge = self._merge_packed_runs if tmp_compress else self._merge_runs
+                n_out += merge([runs[k] for k in sorted(runs)], tmp, n_tmp, out, level, bai if index else None, tix)
                 seconds_merge = time.perf_counter() - t_merge
                 seconds_index = tix[0]
             out.write(trailer)
@@ -1450,6 +1470,8 @@ class Aligner:
             res["n_runs"], res["seconds_merge"], res["n_tmp_bytes"] = len(runs), seconds_merge, n_tmp
         if index:
             res["n_index_bytes"], res["seconds_index"] = n_index, seconds_index
+        if tmp_compress:
+            res["n_tmp_raw_bytes"] = n_tmp_raw
         return res
 
     def _merge_runs(self, runs, tmp, n_tmp, out, level, bai=None, t_index=None):
@@ -1507,6 +1529,80 @@ class Aligner:
             del spool
             if dev_ctx is not None:
                 self._ctx_release(dev_ctx)
+        return n_out
+
+    def _merge_packed_runs(self, runs, tmp, n_tmp, out, level, bai=None, t_index=None):
+        """_merge_runs for packed runs (map_bam_file(tmp_compress=True)).  runs: per sub-batch, in input order, (keys, lengths, place of
+        its MEMBERS in tmp, spans, the members' offsets); tmp: the spool of n_tmp bytes of BGZF members.  The same stable argsort.  A
+        step is a contiguous range of the merged order, so it takes from every run a contiguous range of that run's records: record
+        counts per run (a bincount) and a running count of what earlier steps took give the raw range [lo, hi) each run contributes, the
+        members [lo // 0xff00, ceil(hi / 0xff00)) hold it, and one mm355_bam_merge_step call turns the slices and the records' places
+        into the step's blocks.  Array operations and one library call per step: no Python work per record or per member.
+        `where` is always MM355_PAF_DEVICE, on a context of the aligner's first device (an Aligner always has one): the host `where`
+        of mm355_bam_merge_step is the C-ABI's and the tests', and this route never uses it."""
+        L = self._L
+        keys = np.concatenate([r[0] for r in runs]) if runs else np.zeros(0, np.uint64)
+        lens = np.concatenate([r[1] for r in runs]).astype(np.int64, copy=False) if runs else np.zeros(0, np.int64)
+        if len(keys) == 0:
+            return 0
+        P = 0xff00
+        n_runs = len(runs)
+        counts = np.array([len(r[0]) for r in runs], np.int64)
+        run_of = np.repeat(np.arange(n_runs, dtype=np.int64), counts)
+        raw_all = np.concatenate([np.concatenate(([0], np.cumsum(r[1], dtype=np.int64))) for r in runs])     # per run its n + 1 raw offsets
+        raw_first = np.cumsum(counts + 1) - (counts + 1)
+        at = np.concatenate([np.cumsum(r[1], dtype=np.int64) - r[1] for r in runs])                        # a record's place in its run's unframed stream
+        blk_all = np.concatenate([r[4] for r in runs]).astype(np.int64, copy=False)                        # per run its n_blk + 1 member offsets
+        blk_n = np.array([len(r[4]) for r in runs], np.int64)
+        blk_first = np.cumsum(blk_n) - blk_n
+        place = np.array([r[2] for r in runs], np.int64)
+        order = np.argsort(keys, kind="stable")
+        lens, at, run_of = np.ascontiguousarray(lens[order]), np.ascontiguousarray(at[order]), run_of[order]
+        if bai is not None:
+            t_ix = time.perf_counter()
+            keys, spans = np.ascontiguousarray(keys[order]), np.ascontiguousarray(np.concatenate([r[3] for r in runs])[order])
+            _ffi.check(L.mm355_bai_records(bai, keys.ctypes.data, spans.ctypes.data, lens.ctypes.data, len(lens)))
+            t_index[0] += time.perf_counter() - t_ix
+        end_at = np.cumsum(lens)                         # the sorted stream's offset behind every record
+        tmp.flush()
+        spool = np.memmap(tmp, dtype=np.uint8, mode="r", shape=(n_tmp,))
+        dev_ctx = self._ctx_acquire(0)                   # inflate, gather and the blocks on the device, whatever the level
+        n_out = 0
+        carry, n_carry = np.empty(P, np.uint8), C.c_int64(0)
+        taken = np.zeros(n_runs, np.int64)               # the records of every run that earlier steps took
+        slice_of_run = np.empty(n_runs, np.int32)
+        try:
+            i, n = 0, len(lens)
+            while i < n:
+                base = int(end_at[i - 1]) if i else 0
+                j = max(i + 1, int(np.searchsorted(end_at, base + SORT_CHUNK_BYTES, side="right")))
+                took = np.bincount(run_of[i:j], minlength=n_runs)
+                sel = np.flatnonzero(took)
+                lo, hi = raw_all[raw_first[sel] + taken[sel]], raw_all[raw_first[sel] + taken[sel] + took[sel]]
+                m_lo, m_hi = lo // P, (hi + P - 1) // P
+                b_lo, b_hi = blk_all[blk_first[sel] + m_lo], blk_all[blk_first[sel] + m_hi]
+                slice_at, slice_bytes, slice_raw_at = np.ascontiguousarray(place[sel] + b_lo), np.ascontiguousarray(b_hi - b_lo), np.ascontiguousarray(m_lo * P)
+                slice_of_run[sel] = np.arange(len(sel), dtype=np.int32)
+                rec_slice = np.ascontiguousarray(slice_of_run[run_of[i:j]])
+                taken += took
+                tp = C.POINTER(_ffi.Text)()
+                _ffi.check(L.mm355_bam_merge_step(dev_ctx[1], spool.ctypes.data, n_tmp, slice_at.ctypes.data, slice_bytes.ctypes.data, slice_raw_at.ctypes.data, len(sel),
+                                                  rec_slice.ctypes.data, at[i:j].ctypes.data, lens[i:j].ctypes.data, j - i, carry.ctypes.data, n_carry.value,
+                                                  1 if j == n else 0, _ffi.PAF_DEVICE, level, C.byref(tp), carry.ctypes.data, C.byref(n_carry)))
+                try:
+                    if tp.contents.n_text:
+                        n_out += int(tp.contents.n_text)
+                        out.write(_ffi.text_view(tp))
+                        if bai is not None:
+                            t_ix = time.perf_counter()
+                            _ffi.check(L.mm355_bai_blocks(bai, C.addressof(tp.contents.text.contents), int(tp.contents.n_text)))
+                            t_index[0] += time.perf_counter() - t_ix
+                finally:
+                    L.mm355_free_text(tp)
+                i = j
+        finally:
+            del spool
+            self._ctx_release(dev_ctx)
         return n_out
 
     def _stage_runner(self):

@@ -74,8 +74,9 @@ class Text(C.Structure):       # mm355_text_t: the PAF or SAM lines of one batch
 
 class Run(C.Structure):        # mm355_run_t: the BAM records of one call in coordinate order, unframed, with their keys and offsets
     _fields_ = [("n_rec", C.c_int64), ("n_bytes", C.c_int64), ("key", C.POINTER(C.c_uint64)), ("rec_off", C.POINTER(C.c_int64)),
-                ("rec", C.POINTER(C.c_char)), ("ms_sort", C.c_double), ("on_device", C.c_int32), ("reserved", C.c_int32),
-                ("span", C.POINTER(C.c_int64))]     # NULL unless a _span call filled it (the .bai index)
+                ("rec", C.POINTER(C.c_char)), ("ms_sort", C.c_double), ("on_device", C.c_int32), ("packed", C.c_int32),
+                ("span", C.POINTER(C.c_int64)),     # NULL unless a _span call filled it (the .bai index)
+                ("n_blk", C.c_int64), ("blk_off", C.POINTER(C.c_int64))]     # a packed run (mm355_map_batch_bam_run_packed): rec holds n_blk BGZF members
 
 
 class Reads(C.Structure):      # mm355_reads_t: one sub-batch of the streaming FASTA / FASTQ reader
@@ -132,6 +133,7 @@ EXPORTS = [
     "mm355_bam_format_aux", "mm355_map_batch_bam_aux", "mm355_bam_aux_split", "mm355_fastx_keep_aux", "mm355_reads_aux", "mm355_fastx_bam_rg",
     "mm355_bam_sort", "mm355_map_batch_bam_run", "mm355_bam_gather", "mm355_free_run",
     "mm355_bam_sort_span", "mm355_map_batch_bam_run_span", "mm355_bai_open", "mm355_bai_records", "mm355_bai_blocks", "mm355_bai_finish", "mm355_bai_close",
+    "mm355_map_batch_bam_run_packed", "mm355_bam_merge_step",
 ]
 
 _LIB = None
@@ -203,6 +205,9 @@ def lib():
     L.mm355_free_run.restype = None
     L.mm355_bam_sort_span.argtypes = L.mm355_bam_sort.argtypes
     L.mm355_map_batch_bam_run_span.argtypes = L.mm355_map_batch_bam_run.argtypes
+    L.mm355_map_batch_bam_run_packed.argtypes = L.mm355_map_batch_bam_run.argtypes[:-1] + [C.c_int, C.POINTER(C.POINTER(Run))]   # want_span in front of the result
+    L.mm355_bam_merge_step.argtypes = [vp, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                       C.POINTER(C.POINTER(Text)), vp, i64p]
     L.mm355_bai_open.argtypes = [C.c_int32, C.c_int64, C.POINTER(vp)]
     L.mm355_bai_records.argtypes = [vp, vp, vp, vp, C.c_int64]
     L.mm355_bai_blocks.argtypes = [vp, vp, C.c_int64]
