@@ -167,13 +167,21 @@ int mm355_ctx_create(const mm355_index_t *idx, int device_id, mm355_ctx_t **out)
 void mm355_ctx_destroy(mm355_ctx_t *ctx);
 
 /* --- the hot path: replaces mm_map (+ mm_gen_cs / mm_gen_MD) for a whole batch of reads.
- * seqs[i] need not be NUL-terminated.  flags: bit0 = cs (short form), bit1 = MD, bit2 = tags (mm355_hits_t::tags; legal in both modes).
+ * seqs[i] need not be NUL-terminated.  flags: bit0 = cs (short form), bit1 = MD, bit2 = tags (mm355_hits_t::tags; legal in both modes),
+ * bit3 = cs in the long form (alone or together with bit0: the long form).
+ * cs, short form (minimap2 --cs, format.c::write_cs_core with no_iden): inside a match operation (CIGAR op 0, 7, 8) a maximal run of columns
+ * with equal codes prints ':' and its length, a mismatch '*' + target + query in lower case; an insertion '+' and its query bases, a deletion
+ * '-' and its target bases, lower case.  A run ends at a mismatch and at the end of its CIGAR operation.
+ * cs, long form (minimap2 --cs=long, no_iden == 0): the same, except that a run prints '=' followed by its query bases in upper case from
+ * "ACGTN" (code 4 against code 4 is equal and prints 'N').  Runs end where they end in the short form, so two adjacent match operations
+ * ("5=" then "3=") print two '='.  The '+' / '-' text, mlen, blen, n_ambi, dp_max, the gap counts and MD are those of the short form.
  * Without MM_F_CIGAR in mo->flag the call maps chain-only (minimap2 without -c): seeds, chains, regions, MAPQ from the chains, no extension.
  * Its hits have n_cigar = 0, cs_len = md_len = -1, NM = dp_max = dp_max2 = dp_score = 0; cs / MD flags are MM355_EINVAL; an index without
  * sequence (MM_I_NO_SEQ) is mappable.  The region logic runs on the device (k_regs); MM355_REGS_HOST=1 runs it on the host for every read. --- */
 #define MM355_OUT_CS 1
 #define MM355_OUT_MD 2
 #define MM355_OUT_TAGS 4
+#define MM355_OUT_CS_LONG 8   /* every map call that takes MM355_OUT_CS takes it; chain-only calls refuse it alike */
 int mm355_map_batch(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs,
                     const int32_t *lens, int flags, mm355_hits_t **out);
 /* the same call split in two, for callers that keep a batch resident in HBM (bench.py times mm355_map_resident):
@@ -255,7 +263,7 @@ void mm355_free_text(mm355_text_t *t);
 int mm355_sam_format(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, const mm355_hits_t *hits, const char *const *qnames, const char *const *seqs,
                      const int32_t *qlens, const char *const *quals, const int32_t *rep_len, int sam_flags, int where, mm355_text_t **out);
 /* == mm355_map_batch_named with flags | MM355_OUT_TAGS, then mm355_sam_format with the call's per-read rep_len, then mm355_free_hits: byte
- * for byte.  flags: MM355_OUT_CS | MM355_OUT_MD */
+ * for byte.  flags: MM355_OUT_CS | MM355_OUT_MD | MM355_OUT_CS_LONG */
 int mm355_map_batch_sam(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
                         const char *const *names, const char *const *quals, int flags, int sam_flags, int where, mm355_text_t **out);
 
@@ -296,7 +304,7 @@ int mm355_map_batch_sam(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_re
 int mm355_bam_format(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, const mm355_hits_t *hits, const char *const *qnames, const char *const *seqs,
                      const int32_t *qlens, const char *const *quals, const int32_t *rep_len, int sam_flags, int where, mm355_text_t **out);
 /* == mm355_map_batch_named with flags | MM355_OUT_TAGS, then mm355_bam_format with the call's per-read rep_len, then mm355_free_hits: byte
- * for byte.  flags: MM355_OUT_CS | MM355_OUT_MD */
+ * for byte.  flags: MM355_OUT_CS | MM355_OUT_MD | MM355_OUT_CS_LONG */
 int mm355_map_batch_bam(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
                         const char *const *names, const char *const *quals, int flags, int sam_flags, int where, mm355_text_t **out);
 /* the framing stage by itself: n arbitrary bytes into stored BGZF blocks (n == 0: zero bytes), on the host (ctx may be NULL) or on the
@@ -646,10 +654,11 @@ int mm355_stage_dp(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_jobs, c
                    const uint8_t *qcodes, int64_t n_q, const uint8_t *tcodes, int64_t n_t,
                    mm355_dpres_t *res, uint32_t *cigar, int64_t cigar_cap);
 /* the per-base walk of an aligned region (minimap2 align.c::mm_update_extra after mm_fix_cigar: mlen, blen, n_ambi, dp_max) and its cs
-   string (format.c::write_cs_core, short form), as the mapping path runs them on the device for all regions of a batch (k_extra).
+   string (format.c::write_cs_core, either form), as the mapping path runs them on the device for all regions of a batch (k_extra).
    Stage entry for parity tests: the query codes (0..4 per byte) come from the caller, the target from the index (contig rid, from t_st).
    want_cs: bit 0 = cs, bit 1 = MD (format.c::write_MD_core); both strings land in `cs` (cs_off / md_off); bit 2 = gap counts: `pad` returns
-   the number of I / D operations of the CIGAR (n_gapo) and `pad2` their summed lengths (n_gap); both stay 0 without the bit. */
+   the number of I / D operations of the CIGAR (n_gapo) and `pad2` their summed lengths (n_gap); both stay 0 without the bit; bit 3 = cs in
+   the long form (implies bit 0's cs_off / cs_len; with bit 0 still the long form). */
 typedef struct { int64_t q_off; int64_t cigar_off; int32_t rid, t_st, n_cigar, pad; } mm355_extrajob_t;
 typedef struct { int32_t mlen, blen, n_ambi, dp_max; int64_t cs_off; int32_t cs_len, pad; int64_t md_off; int32_t md_len, pad2; } mm355_extrares_t;
 int mm355_stage_extra(mm355_ctx_t *ctx, const mm355_mapopt_t *mo, int64_t n_regions, const mm355_extrajob_t *jobs,

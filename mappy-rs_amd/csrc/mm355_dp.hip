@@ -783,9 +783,14 @@ __device__ __forceinline__ uint32_t ex_target(const DevIndex &ix, const uint64_t
 //     gap costs is exact in double (< 2^20 in magnitude, fractions of 2^-23), so regrouping the additions changes nothing;
 //   * a run of matches that crosses a cut is printed once: a segment leaves the first number it would print to the composer (its `lead` plus
 //     the `tail` carried over from the segments before it) and never prints what is still pending at its end.
+//   * the long form of cs (want bit 3: k_extra_long, the same walk with LONG = true) spells the run out instead: every segment writes its matched
+//     bases as it meets them and the '=' of every run that begins behind its first flush; the '=' of its lead run is the composer's, one byte
+//     at cs_pre iff nothing is pending from the segments before it.  The rule is mm355_extra.h's inline functions, which these kernels call.
 // The string bytes go to worst-case sized slots and are compacted afterwards (k_extra_scan / k_extra_compact): only real bytes cross PCIe.
-__global__ __launch_bounds__(WAVE) void k_extra(DevIndex ix, const uint8_t *rq, const Mm355ExtraJob *segs, int n_segs, const uint32_t *cig, Mm355ExtraScore sc,
-                                                 char *cs, Mm355ExtraSegOut *out, int want)
+// LONG: the long form of cs (want bit 3).  The form is a template parameter, so the short form's walk is the code it was; the long form
+// writes every matched base as it meets it and leaves the '=' of its lead run to the composer (mm355_extra.h states the rule).
+template<bool LONG> __device__ __forceinline__ void ex_seg_walk(const DevIndex &ix, const uint8_t *rq, const Mm355ExtraJob *segs, int n_segs, const uint32_t *cig, const Mm355ExtraScore &sc,
+                                                                 char *cs, Mm355ExtraSegOut *out, int want)
 {
 	const int k = blockIdx.x * WAVE + threadIdx.x;
 	if (k >= n_segs) return;
@@ -805,7 +810,8 @@ __global__ __launch_bounds__(WAVE) void k_extra(DevIndex ix, const uint8_t *rq, 
 	if (ix.n_nr) { uint32_t c_; ref_window(ix, tb, tb + 1, nri, c_); }
 #define EX_T(off) ex_target(ix, tb + (uint64_t)(off), nri)
 #define EX_PUT(buf, pos, lead, v) do { char bf_[12]; int nb_ = 0; unsigned v_ = (v); do { bf_[nb_++] = (char)('0' + v_ % 10); v_ /= 10; } while (v_); if (lead) buf[pos++] = (lead); while (nb_ > 0) buf[pos++] = bf_[--nb_]; } while (0)
-#define EX_FLUSH_CS() do { if (!(flushed & 1)) { cs_lead = (int32_t)run; cs_pre = n_out; flushed |= 1; } else if (run) EX_PUT(o, n_out, ':', run); run = 0; } while (0)
+// (the short form keeps its own text of mm355_cs_flush<false>: the walk's registers are what they were)
+#define EX_FLUSH_CS() do { if constexpr (LONG) mm355_cs_flush<true>(o, n_out, run, flushed, cs_lead, cs_pre); else { if (!(flushed & 1)) { cs_lead = (int32_t)run; cs_pre = n_out; flushed |= 1; } else if (run) EX_PUT(o, n_out, ':', run); run = 0; } } while (0)
 #define EX_FLUSH_MD() do { if (!(flushed & 2)) { md_lead = (int32_t)l_md; flushed |= 2; } else EX_PUT(om, n_md, 0, l_md); l_md = 0; } while (0)
 #define EX_STEP(d) do { A += (d); m = A < m? A : m; C = A > C? A : C; const double am_ = A - m; P = am_ > P? am_ : P; } while (0)
 	for (int c = 0; c < jb.n_cigar; ++c) {
@@ -819,7 +825,7 @@ __global__ __launch_bounds__(WAVE) void k_extra(DevIndex ix, const uint8_t *rq, 
 				if (ct > 3 || cq > 3) ++n_ambi;
 				else if (ct != cq) ++n_diff;
 				EX_STEP((double)sc.mat[ct * 5 + cq]);
-				if (cq == ct) { ++run; ++l_md; }
+				if (cq == ct) { if (LONG) mm355_cs_long_match(o, n_out, run, flushed, cq); ++run; ++l_md; }
 				else {
 					if (want_cs) { EX_FLUSH_CS(); o[n_out++] = '*'; o[n_out++] = nt[ct]; o[n_out++] = nt[cq]; }
 					if (want_md) { EX_FLUSH_MD(); om[n_md++] = NT[ct]; }
@@ -857,12 +863,23 @@ __global__ __launch_bounds__(WAVE) void k_extra(DevIndex ix, const uint8_t *rq, 
 	r.cs_len = n_out; r.md_len = n_md; r.flushed = flushed;
 	r.cs_lead = (flushed & 1)? cs_lead : (int32_t)run; r.cs_tail = (flushed & 1)? (int32_t)run : 0;      // never flushed: everything it counted joins the carry
 	r.md_lead = (flushed & 2)? md_lead : (int32_t)l_md; r.md_tail = (flushed & 2)? (int32_t)l_md : 0;
-	r.cs_num = r.md_num = -1; r.cs_dense = r.md_dense = 0; r.cs_pre = (flushed & 1)? cs_pre : 0;
+	r.cs_num = r.md_num = -1; r.cs_dense = r.md_dense = 0; r.cs_pre = (flushed & 1)? cs_pre : 0;     // == mm355_cs_seg_close<false>
+	if constexpr (LONG) mm355_cs_seg_close<true>(n_out, run, flushed, cs_lead, cs_pre, &r.cs_lead, &r.cs_tail, &r.cs_pre);   // a segment that never flushed: its bases stand at the end of its slot
 	r.n_gap = n_gap; r.n_gapo = n_gapo; r.pad = 0;
 	out[k] = r;
 }
+__global__ __launch_bounds__(WAVE) void k_extra(DevIndex ix, const uint8_t *rq, const Mm355ExtraJob *segs, int n_segs, const uint32_t *cig, Mm355ExtraScore sc,
+                                                 char *cs, Mm355ExtraSegOut *out, int want)
+{
+	ex_seg_walk<false>(ix, rq, segs, n_segs, cig, sc, cs, out, want);
+}
+__global__ __launch_bounds__(WAVE) void k_extra_long(DevIndex ix, const uint8_t *rq, const Mm355ExtraJob *segs, int n_segs, const uint32_t *cig, Mm355ExtraScore sc,
+                                                      char *cs, Mm355ExtraSegOut *out, int want)
+{
+	ex_seg_walk<true>(ix, rq, segs, n_segs, cig, sc, cs, out, want);
+}
 
-__device__ inline int ex_digits(unsigned v) { int n = 1; while (v >= 10) { v /= 10; ++n; } return n; }
+__device__ inline int ex_digits(unsigned v) { return mm355_ex_digits(v); }
 
 // exclusive prefix sum of the regions' string lengths (one block of 256 threads: a batch has a few thousand regions; the per-segment offsets
 // inside a region come from k_extra_compose -- a scan over the ~10^5 segments in one 1024-thread block waited milliseconds for a CU under load)
@@ -889,16 +906,16 @@ __global__ __launch_bounds__(256) void k_extra_compose(Mm355ExtraSegOut *seg, co
 	double s = 0.0, mx = 0.0;
 	Mm355ExtraOut r; r.mlen = r.blen = r.n_ambi = 0; r.cs_len = r.md_len = 0; r.cs_dense = 0; r.md_end_num = -1; r.n_gap = r.n_gapo = 0; r.pad = 0;
 	unsigned cs_carry = 0, md_carry = 0;
+	const bool cs_long = (want & 8) != 0;
 	const int64_t g0 = seg_first[k], g1 = seg_first[k + 1];
 	for (int64_t g = g0; g < g1; ++g) {
 		const Mm355ExtraSegOut e = seg[g];
 		r.mlen += e.mlen; r.blen += e.blen; r.n_ambi += e.n_ambi; r.n_gap += e.n_gap; r.n_gapo += e.n_gapo;
 		int32_t cs_num = -1, md_num = -1;
 		if (want & 1) {
-			if (e.flushed & 1) { const unsigned nn = cs_carry + (unsigned)e.cs_lead; if (nn) cs_num = (int32_t)nn; cs_carry = (unsigned)e.cs_tail; }
-			else cs_carry += (unsigned)e.cs_lead;
-			seg[g].cs_dense = r.cs_len;   // offset of [number][body] inside the region's cs string
-			r.cs_len += (cs_num >= 0? 1 + ex_digits((unsigned)cs_num) : 0) + e.cs_len;
+			cs_num = cs_long? mm355_cs_compose<true>(e.flushed, e.cs_lead, e.cs_tail, cs_carry) : mm355_cs_compose<false>(e.flushed, e.cs_lead, e.cs_tail, cs_carry);
+			seg[g].cs_dense = r.cs_len;   // offset of [number][body] (long form: [=?][body]) inside the region's cs string
+			r.cs_len += (cs_long? mm355_cs_ins_bytes<true>(cs_num) : mm355_cs_ins_bytes<false>(cs_num)) + e.cs_len;
 		}
 		if (want & 2) {
 			if (e.flushed & 2) { md_num = (int32_t)(md_carry + (unsigned)e.md_lead); md_carry = (unsigned)e.md_tail; }
@@ -919,14 +936,7 @@ __global__ __launch_bounds__(256) void k_extra_compose(Mm355ExtraSegOut *seg, co
 	out[k] = r;
 }
 
-__device__ inline int ex_put_num(char *dst, char lead, unsigned v)
-{
-	char bf[12]; int nb = 0, n = 0;
-	do { bf[nb++] = (char)('0' + v % 10); v /= 10; } while (v);
-	if (lead) dst[n++] = lead;
-	while (nb > 0) dst[n++] = bf[--nb];
-	return n;
-}
+__device__ inline int ex_put_num(char *dst, char lead, unsigned v) { return mm355_ex_put_num(dst, lead, v); }
 __global__ __launch_bounds__(256) void k_extra_compact(const Mm355ExtraJob *segs, const Mm355ExtraSegOut *out, const Mm355ExtraOut *reg, const int64_t *seg_first, int n, const char *cs, char *dense, int want)
 {
 	const int k = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;   // one wave per segment
@@ -936,10 +946,11 @@ __global__ __launch_bounds__(256) void k_extra_compact(const Mm355ExtraJob *segs
 	const Mm355ExtraOut ro = reg[jb.region];
 	if (want & 1) {
 		char *dst = dense + ro.cs_dense + so.cs_dense;
-		int nn = 0;
-		if (so.cs_num >= 0) { nn = 1 + ex_digits((unsigned)so.cs_num); if (lane == 0) ex_put_num(dst + so.cs_pre, ':', (unsigned)so.cs_num); }   // behind the text of leading gaps
+		const bool cs_long = (want & 8) != 0;
+		const int nn = cs_long? mm355_cs_ins_bytes<true>(so.cs_num) : mm355_cs_ins_bytes<false>(so.cs_num);
+		if (lane == 0) { if (cs_long) mm355_cs_put_ins<true>(dst + so.cs_pre, so.cs_num); else mm355_cs_put_ins<false>(dst + so.cs_pre, so.cs_num); }   // behind the text of leading gaps
 		const char *src = cs + jb.cs_off;
-		for (int i = lane; i < so.cs_len; i += 64) dst[i < so.cs_pre? i : nn + i] = src[i];
+		for (int i = lane; i < so.cs_len; i += 64) dst[mm355_cs_place(i, so.cs_pre, nn)] = src[i];
 	}
 	if (want & 2) {
 		char *dst = dense + ro.cs_dense + ro.cs_len + so.md_dense;
@@ -956,6 +967,7 @@ int mm355_extra_run(mm355_ctx *c, const mm355_mapopt_t *mo, const Mm355ExtraJob 
 {
 	*out = 0; *cs = 0;
 	if (n_regions == 0) return 0;
+	if (want & 8) want |= 1;   // the long form of cs: bit 0's output fields; without bit 3 the kernels and their arguments are what they were
 	const size_t seg_b = (n_segs * sizeof(Mm355ExtraJob) + 63) & ~(size_t)63, first_b = (n_regions + 1) * 8;
 	if (c->x_jobs.ensure(seg_b + first_b + 64) || c->x_cig.ensure((n_cig + 16) * 4) || c->x_cs.ensure(cs_cap + 64) ||
 	    c->x_out.ensure((n_segs + 1) * sizeof(Mm355ExtraSegOut) + n_regions * sizeof(Mm355ExtraOut)) || c->h_xout.ensure(n_regions * sizeof(Mm355ExtraOut) + 64)) return MM355_ENOMEM;
@@ -976,7 +988,7 @@ int mm355_extra_run(mm355_ctx *c, const mm355_mapopt_t *mo, const Mm355ExtraJob 
 	if (n_cig) HIPCHK(hipMemcpyAsync(c->x_cig.p, cig, n_cig * 4, hipMemcpyHostToDevice, c->st));
 	mm355_kt(c, KT_EXTRA, 0, c->st);
 	if (n_segs) {
-		hipLaunchKernelGGL(k_extra, dim3((unsigned)((n_segs + WAVE - 1) / WAVE)), dim3(WAVE), 0, c->st, c->dix, c->rq.as<uint8_t>(), d_segs, (int)n_segs,
+		hipLaunchKernelGGL((want & 8)? k_extra_long : k_extra, dim3((unsigned)((n_segs + WAVE - 1) / WAVE)), dim3(WAVE), 0, c->st, c->dix, c->rq.as<uint8_t>(), d_segs, (int)n_segs,
 		                   c->x_cig.as<uint32_t>(), sc, c->x_cs.as<char>(), d_so, want);
 	}
 	hipLaunchKernelGGL(k_extra_compose, dim3((unsigned)((n_regions + 255) / 256)), dim3(256), 0, c->st, d_so, d_first, (int)n_regions, d_ro, want);
@@ -1058,7 +1070,7 @@ extern "C" int mm355_stage_dp(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t 
 	return 0;
 }
 
-// C-ABI: the device form of mm_update_extra's walk + cs / MD on caller-provided regions (parity tests).  want_cs: bit 0 cs, bit 1 MD, bit 2 gap counts (n_gapo in pad, n_gap in pad2)
+// C-ABI: the device form of mm_update_extra's walk + cs / MD on caller-provided regions (parity tests).  want_cs: bit 0 cs, bit 1 MD, bit 2 gap counts (n_gapo in pad, n_gap in pad2), bit 3 cs in long form (alone or with bit 0)
 extern "C" int mm355_stage_extra(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_regions, const mm355_extrajob_t *jobs,
                                  const uint8_t *qcodes, int64_t n_q, const uint32_t *cigar, int64_t n_cigar, int want_cs,
                                  mm355_extrares_t *res, char *cs, int64_t cs_cap)
@@ -1090,12 +1102,12 @@ extern "C" int mm355_stage_extra(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64
 	}
 	first[n_regions] = (int64_t)g;
 	const Mm355ExtraOut *xo = 0; const char *xcs = 0;
-	int rc = mm355_extra_run(c, mo, segs, n_segs, first, (size_t)n_regions, (const uint32_t*)c->h_xcig.p, (size_t)n_cigar, (size_t)slot, want_cs & 3, &xo, &xcs);
+	int rc = mm355_extra_run(c, mo, segs, n_segs, first, (size_t)n_regions, (const uint32_t*)c->h_xcig.p, (size_t)n_cigar, (size_t)slot, want_cs & 11, &xo, &xcs);
 	if (rc) return rc;
 	for (int64_t k = 0; k < n_regions; ++k) {
-		mm355_extrares_t o; o.mlen = xo[k].mlen; o.blen = xo[k].blen; o.n_ambi = xo[k].n_ambi; o.dp_max = xo[k].dp_max; o.cs_off = xo[k].cs_dense; o.cs_len = (want_cs & 1)? xo[k].cs_len : 0; o.pad = (want_cs & 4)? xo[k].n_gapo : 0;
+		mm355_extrares_t o; o.mlen = xo[k].mlen; o.blen = xo[k].blen; o.n_ambi = xo[k].n_ambi; o.dp_max = xo[k].dp_max; o.cs_off = xo[k].cs_dense; o.cs_len = (want_cs & 9)? xo[k].cs_len : 0; o.pad = (want_cs & 4)? xo[k].n_gapo : 0;
 		o.md_off = xo[k].cs_dense + xo[k].cs_len; o.md_len = (want_cs & 2)? xo[k].md_len : 0; o.pad2 = (want_cs & 4)? xo[k].n_gap : 0;
-		if (want_cs & 3) { if (o.cs_off + xo[k].cs_len + xo[k].md_len > cs_cap) return MM355_ENOMEM; memcpy(cs + o.cs_off, xcs + o.cs_off, (size_t)xo[k].cs_len + (size_t)xo[k].md_len); }
+		if (want_cs & 11) { if (o.cs_off + xo[k].cs_len + xo[k].md_len > cs_cap) return MM355_ENOMEM; memcpy(cs + o.cs_off, xcs + o.cs_off, (size_t)xo[k].cs_len + (size_t)xo[k].md_len); }
 		res[k] = o;
 	}
 	return 0;

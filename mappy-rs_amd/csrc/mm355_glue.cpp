@@ -812,7 +812,7 @@ static void fix_cigar(Reg *r, const uint8_t *qseq, const uint8_t *tseq, int *qsh
 	cg.resize(n_cigar);
 }
 
-static void gen_cs(const Reg *r, const uint8_t *qseq, const uint8_t *tseq, std::string &s);
+static void gen_cs(const Reg *r, const uint8_t *qseq, const uint8_t *tseq, std::string &s, bool long_form);
 static void gen_md(const Reg *r, const uint8_t *qseq, const uint8_t *tseq, std::string &s);
 
 // U:align.c::mm_update_cigar_eqx (MM_F_EQX): every M becomes alternating runs of '=' (7) and 'X' (8); N vs N counts as '='
@@ -908,7 +908,7 @@ static void update_extra(Reg *r, const uint8_t *qseq, const uint8_t *tseq, const
 	p->dp_max = (int32_t)(max + .499);
 	delete pf3;
 	ProfScope pf4(PF_X4);
-	if (out_flags & MM355_OUT_CS) { p->cs.clear(); gen_cs(r, qseq, tseq, p->cs); }
+	if (out_flags & (MM355_OUT_CS | MM355_OUT_CS_LONG)) { p->cs.clear(); gen_cs(r, qseq, tseq, p->cs, (out_flags & MM355_OUT_CS_LONG) != 0); }
 	if (out_flags & MM355_OUT_MD) { p->md.clear(); gen_md(r, qseq, tseq, p->md); }
 	if (eqx) cigar_eqx(r, qseq, tseq);   // after cs/MD: both read M, '=' and 'X' alike (U:format.c::write_cs_core / write_MD_core)
 }
@@ -1435,17 +1435,18 @@ static inline int match_run(const uint8_t *q, const uint8_t *t, int len)
 	return j;
 }
 
-static void gen_cs(const Reg *r, const uint8_t *qseq, const uint8_t *tseq, std::string &s)   // U:format.c::write_cs_core (short form, no introns)
+static void gen_cs(const Reg *r, const uint8_t *qseq, const uint8_t *tseq, std::string &s, bool long_form)   // U:format.c::write_cs_core (both forms, no introns)
 {
 	int q_off = 0, t_off = 0;
-	s.reserve(s.size() + (size_t)(r->qe - r->qs) / 2 + 64);
+	s.reserve(s.size() + (size_t)(r->qe - r->qs) / (long_form? 1 : 2) + (long_form? r->p->cigar.size() * 2 : 0) + 64);
 	for (size_t i = 0; i < r->p->cigar.size(); ++i) {
 		int op = r->p->cigar[i] & 0xf, len = r->p->cigar[i] >> 4;
 		if (op == 0 || op == 7 || op == 8) {
 			int j = 0;
 			while (j < len) {
 				const int m = match_run(qseq + q_off + j, tseq + t_off + j, len - j);
-				if (m > 0) { put_uint(s, ':', (unsigned)m); j += m; }
+				if (m > 0 && long_form) { s += '='; for (int k = 0; k < m; ++k) s += "ACGTN"[qseq[q_off + j + k]]; j += m; }   // MM355_OUT_CS_LONG: the run's bases
+				else if (m > 0) { put_uint(s, ':', (unsigned)m); j += m; }
 				if (j < len) { s += '*'; s += "acgtn"[tseq[t_off + j]]; s += "acgtn"[qseq[q_off + j]]; ++j; }
 			}
 			q_off += len, t_off += len;
@@ -1507,7 +1508,7 @@ void mm355_glue_finish(const mm355_index *mi, const mm355_mapopt_t *opt, ReadSta
 			h.n_cigar = (int32_t)r->p->cigar.size(); h.cigar_off = (int64_t)cigar.size();
 			cigar.insert(cigar.end(), r->p->cigar.begin(), r->p->cigar.end());
 			h.dp_max = r->p->dp_max; h.dp_max2 = r->p->dp_max2; h.dp_score = r->p->dp_score;
-			if (flags & MM355_OUT_CS) { h.cs_off = (int64_t)str.size(); h.cs_len = (int64_t)r->p->cs.size(); str += r->p->cs; str += '\0'; }
+			if (flags & (MM355_OUT_CS | MM355_OUT_CS_LONG)) { h.cs_off = (int64_t)str.size(); h.cs_len = (int64_t)r->p->cs.size(); str += r->p->cs; str += '\0'; }
 			if (flags & MM355_OUT_MD) { h.md_off = (int64_t)str.size(); h.md_len = (int64_t)r->p->md.size(); str += r->p->md; str += '\0'; }
 		}
 		hits.push_back(h);
@@ -1570,7 +1571,7 @@ void mm355_glue_extra_apply(ReadState &rs, const Mm355ExtraOut *out, const char 
 		const Mm355ExtraOut &o = out[k++];
 		r.mlen = o.mlen; r.blen = o.blen; r.p->n_ambi += (uint32_t)o.n_ambi; r.p->dp_max = o.dp_max;
 		r.p->n_gap += o.n_gap; r.p->n_gapo += o.n_gapo;
-		if (want & MM355_OUT_CS) r.p->cs.assign(cs + o.cs_dense, (size_t)o.cs_len);
+		if (want & (MM355_OUT_CS | MM355_OUT_CS_LONG)) r.p->cs.assign(cs + o.cs_dense, (size_t)o.cs_len);
 		if (want & MM355_OUT_MD) r.p->md.assign(cs + o.cs_dense + o.cs_len, (size_t)o.md_len);
 		r.p->deferred = false;
 	}

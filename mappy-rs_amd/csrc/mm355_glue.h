@@ -96,7 +96,7 @@ struct AlnTask {            // U:align.c::mm_align1 split into a one-off preambl
 };
 
 struct ReadState {
-	int out_flags = 0;                 // MM355_OUT_CS / MM355_OUT_MD requested for this batch
+	int out_flags = 0;                 // MM355_OUT_CS / MM355_OUT_CS_LONG / MM355_OUT_MD requested for this batch
 	int32_t qlen = 0;
 	const char *seq = 0;
 	std::vector<uint8_t> qc[2];        // query codes forward / reverse-complement
@@ -140,4 +140,4 @@ void mm355_glue_release(ReadState &rs);
 // apply: results back into the regions (same order as fill)
 void mm355_glue_extra_count(const ReadState &rs, int64_t *n_regions, int64_t *n_segs, int64_t *n_cig, int64_t *n_cs);
 void mm355_glue_extra_fill(const ReadState &rs, int64_t q_base, Mm355ExtraJob *segs, int64_t *seg_first, int64_t reg0, int64_t seg0, uint32_t *cig, int64_t cig0, int64_t cs0);
-void mm355_glue_extra_apply(ReadState &rs, const Mm355ExtraOut *out, const char *cs, int want);   // want: MM355_OUT_CS | MM355_OUT_MD
+void mm355_glue_extra_apply(ReadState &rs, const Mm355ExtraOut *out, const char *cs, int want);   // want: MM355_OUT_CS | MM355_OUT_MD | MM355_OUT_CS_LONG

@@ -376,7 +376,7 @@ extern "C" int mm355_map_batch_named(mm355_ctx_t *c, const mm355_mapopt_t *mo, i
                                      const char *const *names, int flags, mm355_hits_t **out)
 {
 	*out = 0;
-	if (mo && !(mo->flag & MMF_CIGAR) && (flags & (MM355_OUT_CS | MM355_OUT_MD))) return MM355_EINVAL;   // cs / MD need the base-level alignment
+	if (mo && !(mo->flag & MMF_CIGAR) && (flags & (MM355_OUT_CS | MM355_OUT_MD | MM355_OUT_CS_LONG))) return MM355_EINVAL;   // cs / MD need the base-level alignment
 	int rc = mm355_batch_upload_named(c, n_reads, seqs, lens, names);
 	if (rc) return rc;
 	return mm355_map_resident(c, mo, flags, out);
@@ -400,7 +400,7 @@ extern "C" int mm355_map_resident(mm355_ctx_t *c, const mm355_mapopt_t *mo, int 
 	int rc = mm355_check_opts(mo, c->mi);
 	if (rc) return rc;
 	const bool chain_only = !(mo->flag & MMF_CIGAR);   // minimap2 without -c: regions and MAPQ from the chains, no extension
-	if (chain_only && (flags & (MM355_OUT_CS | MM355_OUT_MD))) return MM355_EINVAL;
+	if (chain_only && (flags & (MM355_OUT_CS | MM355_OUT_MD | MM355_OUT_CS_LONG))) return MM355_EINVAL;
 	HIPCHK(hipSetDevice(c->dev));
 	const double t_start = now_ms();
 	const int64_t cpu_start = thread_cpu_ns(); tl_helper_cpu_ns = 0;
@@ -520,7 +520,7 @@ extern "C" int mm355_map_resident(mm355_ctx_t *c, const mm355_mapopt_t *mo, int 
 				if (xr[i + 1] > xr[i]) mm355_glue_extra_fill(rs[i], 2 * c->hb.roff[i], xsegs + xg[i], xfirst, xr[i], xg[i], xcig, xc[i], xs[i]);
 			});
 			const Mm355ExtraOut *xo = 0; const char *xcs = 0;
-			const int want_cs = flags & (MM355_OUT_CS | MM355_OUT_MD);
+			const int want_cs = flags & (MM355_OUT_CS | MM355_OUT_MD | MM355_OUT_CS_LONG);
 			ms_host += now_ms() - tx0; trace_add(c, "x:fill", tx0, now_ms());
 			if ((rc = mm355_extra_run(c, mo, xsegs, (size_t)tg, xfirst, (size_t)tr, xcig, (size_t)tc, (size_t)ts, want_cs, &xo, &xcs))) return rc;
 			const double tx1 = now_ms();

@@ -583,6 +583,19 @@ class AlignmentBatchResultIter:
         self._st.close()
 
 
+
+def _cs_flag(cs):
+    """the flag bits of a `cs=` argument: False (no cs), True or "short" (minimap2 --cs, `:123*ag+tt-c`), "long" (--cs=long, `=ACGT*ag+tt-c`:
+    the matched bases spelled out, what tools that rebuild both sequences of an alignment need).  Anything else: ValueError."""
+    if cs is None or (isinstance(cs, (bool, int)) and cs in (0, 1)):
+        return _ffi.OUT_CS if cs else 0
+    if isinstance(cs, str) and cs == "short":
+        return _ffi.OUT_CS
+    if isinstance(cs, str) and cs == "long":
+        return _ffi.OUT_CS_LONG
+    raise ValueError("`cs` must be False, True, 'short' or 'long'")
+
+
 class Aligner:
     """mappy-compatible aligner (lib.rs:288-671) whose mapping path runs on MI355X GPUs.
 
@@ -775,11 +788,12 @@ class Aligner:
         if not isinstance(seq, str):
             raise TypeError("argument 'seq': 'bytes' object cannot be converted to 'PyString'" if isinstance(seq, bytes)
                             else "argument 'seq' must be str")
-        if (cs or MD) and not self._mo.flag & 4:
+        cs_flag = _cs_flag(cs)
+        if (cs_flag or MD) and not self._mo.flag & 4:
             raise ValueError("cs / MD need base-level alignment: this Aligner was created with cigar=False")
         if name is not None and not isinstance(name, str):
             raise ValueError("`name` must be a string")
-        flags = (_ffi.OUT_CS if cs else 0) | (_ffi.OUT_MD if MD else 0) | self._tag_flag
+        flags = cs_flag | (_ffi.OUT_MD if MD else 0) | self._tag_flag
         r = self._map_many([seq], flags, names=None if name is None else [name])[0]
         if isinstance(r, Exception):
             raise r
@@ -797,11 +811,14 @@ class Aligner:
         min(n_threads, 8) host threads per GPU, each with its own context (HIP streams + buffers)."""
         self._n_threads = int(n_threads)
 
-    def map_batch(self, seqs, back_off=True):
+    def map_batch(self, seqs, back_off=True, *, cs=True):
         """lib.rs:639-648, 771-906.  The iterable is consumed completely before the iterator is returned (lib.rs:845-903), but -- as in the
         reference, whose workers pop the queue while `_map_batch` is still pushing -- mapping starts as soon as the first sub-batch of reads
         has been taken from it, and results stream out of the returned iterator in completion order while later sub-batches are still on the
         GPU (lib.rs:793-839: collector thread -> bounded channel -> `__next__`)."""
+        cs_flag = _cs_flag(cs)           # cs (keyword-only): True = the reference's hard-wired short form (lib.rs:589); "short", "long", False as in map()
+        if cs_flag == _ffi.OUT_CS_LONG and not self._mo.flag & 4:
+            raise ValueError("cs / MD need base-level alignment: this Aligner was created with cigar=False")
         if self._n_threads == 0:
             raise RuntimeError("Multi threading not enabled on this instance. Please call `.enable_threading()`")
         # accepted iterables: list / tuple / iterator / generator / sequence -- not dict, not str (lib.rs:782-792, 910-920)
@@ -839,7 +856,7 @@ class Aligner:
             if not all(nm is None or isinstance(nm, str) for nm in names):
                 raise ValueError("`%s` must be a string" % (name_key,))
             return names
-        out_flags = (_ffi.OUT_CS if self._mo.flag & 4 else 0) | self._tag_flag        # chain-only: no cs string to produce
+        out_flags = (cs_flag if self._mo.flag & 4 else 0) | self._tag_flag        # chain-only: no cs string to produce
 
         # (the closures below capture `st`, never the iterator handed to the caller)
         def worker(slot):
@@ -960,9 +977,10 @@ class Aligner:
 
     # ---- PAF text (mm355_map_batch_paf): the lines of mappy_rs.paf_line, formatted by the library -- on the device for large batches
     def _paf_flags(self, cs, MD):
-        if (cs or MD) and not self._mo.flag & 4:
+        cs_flag = _cs_flag(cs)
+        if (cs_flag or MD) and not self._mo.flag & 4:
             raise ValueError("cs / MD need base-level alignment: this Aligner was created with cigar=False")
-        return (_ffi.OUT_CS if cs else 0) | (_ffi.OUT_MD if MD else 0) | _ffi.OUT_TAGS
+        return cs_flag | (_ffi.OUT_MD if MD else 0) | _ffi.OUT_TAGS
 
     def map_paf(self, seqs, names=None, cs=False, MD=False, *, where=_ffi.PAF_AUTO):
         """the PAF lines of `seqs` (a list of str) as bytes, in input order: one mm355_map_batch_paf call, no Mapping objects.  Each line is
@@ -1009,7 +1027,7 @@ class Aligner:
     def _sam_flags(self, cs, MD):
         if not self._mo.flag & 4:
             raise ValueError("SAM needs base-level alignment: this Aligner was created with cigar=False")
-        return (_ffi.OUT_CS if cs else 0) | (_ffi.OUT_MD if MD else 0)
+        return _cs_flag(cs) | (_ffi.OUT_MD if MD else 0)
 
     def map_sam(self, seqs, names=None, quals=None, cs=False, MD=False, *, softclip=False, hit_only=False, where=_ffi.PAF_AUTO):
         """the SAM lines of `seqs` (a list of str) as bytes, without a header (sam_header()), in input order: one mm355_map_batch_sam call, no

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("MM355_LIB_PATH") or os.path.join(os.path.dirname(_HER
 MM355_ENODEV, MM355_EINVAL, MM355_ENOMEM, MM355_EIO, MM355_ENOIDX, MM355_EEMPTY, MM355_EUNSUP, MM355_EHIP = \
     -1, -2, -3, -4, -5, -6, -7, -8
 OUT_CS, OUT_MD, OUT_TAGS = 1, 2, 4
+OUT_CS_LONG = 8      # MM355_OUT_CS_LONG: cs in the long form (alone or with OUT_CS)
 TAG_INV, TAG_SAM_PRI, TAG_SPLIT_SHIFT = 1, 2, 2      # mm355_tags_t::flags
 PAF_AUTO, PAF_HOST, PAF_DEVICE = 0, 1, 2             # `where` of mm355_paf_format / mm355_map_batch_paf and of the SAM calls
 SAM_SOFTCLIP, SAM_HIT_ONLY = 1, 2                    # `sam_flags` of mm355_sam_format / mm355_map_batch_sam
