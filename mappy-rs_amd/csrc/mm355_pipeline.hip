@@ -565,9 +565,10 @@ static int rmq_pass(mm355_ctx *c, const RmqParams &rp, const DevParams &pr, int 
 	if (ce != hipSuccess) return MM355_EHIP;
 	if (rc) return rc;
 	for (int k = 0; k < nl; ++k) c->stats.n_v_rmq += rp.primary? hb.n_a[hl[k]] : 0;
-	for (int64_t i = 0; i < n; ++i) {
-		state[i] = hf[i];
-		if (hf[i] == MM355_RMQ_DONE) ++c->stats.n_rmq_reads; else if (hf[i] == MM355_RMQ_HOST) ++c->stats.n_rmq_host;
+	for (int64_t i = 0; i < n; ++i) state[i] = hf[i];
+	for (int k = 0; k < nl; ++k) {   // (the listed reads only: the primary pass starts every flag of the batch out as DONE, those of reads without anchors too)
+		const uint8_t s = hf[hl[k]];
+		if (s == MM355_RMQ_DONE) ++c->stats.n_rmq_reads; else if (s == MM355_RMQ_HOST) ++c->stats.n_rmq_host;
 	}
 	for (int k = 0; k < CTR_RMQ_WORDS; ++k) c->stats.rmq_scanned += (int64_t)hc[k];
 	return 0;

@@ -261,6 +261,9 @@ void mmo_lchain_dp_fill(int max_dist_x, int max_dist_y, int bw, int max_skip, in
                         int64_t n, const mm128_t *a, int32_t *f, int64_t *p, int32_t *v, int32_t *t);
 mm128_t *mmo_lchain_rmq(int max_dist, int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, int min_cnt, int min_sc,
                         float chn_pen_gap, float chn_pen_skip, int64_t n, mm128_t *a, int *n_u_, uint64_t **_u);
+/* the fill of mg_lchain_rmq only (for kernel parity): writes f[n], p[n] (int64), v[n] */
+void mmo_lchain_rmq_fill(int max_dist, int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, float chn_pen_gap, float chn_pen_skip,
+                         int64_t n, const mm128_t *a, int32_t *f, int64_t *p, int32_t *v);
 
 /* ---- hit.c / esterr.c ---- */
 mmo_reg1_t *mmo_gen_regs(uint32_t hash, int qlen, int n_u, uint64_t *u, mm128_t *a, int is_qstrand);

@@ -549,27 +549,18 @@ static inline int32_t comput_sc_simple(const mm128_t *ai, const mm128_t *aj, flo
 	return sc;
 }
 
-mm128_t *mmo_lchain_rmq(int max_dist, int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, int min_cnt, int min_sc, float chn_pen_gap, float chn_pen_skip,
-                        int64_t n, mm128_t *a, int *n_u_, uint64_t **_u)
+/* the fill loop of U:lchain.c::mg_lchain_rmq: f, p, v and the marks t (zeroed by the caller) of n > 0 anchors sorted by x */
+static void lchain_rmq_fill(int max_dist, int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, float chn_pen_gap, float chn_pen_skip,
+                            int64_t n, const mm128_t *a, int32_t *f, int64_t *p, int32_t *v, int32_t *t)
 {
-	int32_t *f,*t, *v, n_u, n_v, mmax_f = 0, max_drop = bw;
-	int64_t *p, i, i0, st = 0, st_inner = 0;
-	uint64_t *u;
+	int32_t mmax_f = 0;
+	int64_t i, i0, st = 0, st_inner = 0;
 	lc_elem_t *root = 0, *root_inner = 0;
 	pool_t mp;
 
-	if (_u) *_u = 0, *n_u_ = 0;
-	if (n == 0 || a == 0) {
-		free(a);
-		return 0;
-	}
 	if (max_dist < bw) max_dist = bw;
 	if (max_dist_inner < 0) max_dist_inner = 0;
 	if (max_dist_inner > max_dist) max_dist_inner = max_dist;
-	p = (int64_t*)malloc(n * 8);
-	f = (int32_t*)malloc(n * 4);
-	t = (int32_t*)calloc(n, 4);
-	v = (int32_t*)malloc(n * 4);
 	memset(&mp, 0, sizeof(mp));
 
 	for (i = i0 = 0; i < n; ++i) {
@@ -654,6 +645,36 @@ mm128_t *mmo_lchain_rmq(int max_dist, int max_dist_inner, int bw, int max_chn_sk
 		if (mmax_f < max_f) mmax_f = max_f;
 	}
 	pool_destroy(&mp);
+}
+
+/* the fill of mg_lchain_rmq, exposed for kernel parity (as mmo_lchain_dp_fill is for mg_lchain_dp) */
+void mmo_lchain_rmq_fill(int max_dist, int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, float chn_pen_gap, float chn_pen_skip,
+                         int64_t n, const mm128_t *a, int32_t *f, int64_t *p, int32_t *v)
+{
+	int32_t *t;
+	if (n <= 0) return;
+	t = (int32_t*)calloc(n, 4);
+	lchain_rmq_fill(max_dist, max_dist_inner, bw, max_chn_skip, cap_rmq_size, chn_pen_gap, chn_pen_skip, n, a, f, p, v, t);
+	free(t);
+}
+
+mm128_t *mmo_lchain_rmq(int max_dist, int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, int min_cnt, int min_sc, float chn_pen_gap, float chn_pen_skip,
+                        int64_t n, mm128_t *a, int *n_u_, uint64_t **_u)
+{
+	int32_t *f,*t, *v, n_u, n_v, max_drop = bw;
+	int64_t *p;
+	uint64_t *u;
+
+	if (_u) *_u = 0, *n_u_ = 0;
+	if (n == 0 || a == 0) {
+		free(a);
+		return 0;
+	}
+	p = (int64_t*)malloc(n * 8);
+	f = (int32_t*)malloc(n * 4);
+	t = (int32_t*)calloc(n, 4);
+	v = (int32_t*)malloc(n * 4);
+	lchain_rmq_fill(max_dist, max_dist_inner, bw, max_chn_skip, cap_rmq_size, chn_pen_gap, chn_pen_skip, n, a, f, p, v, t);
 
 	u = mg_chain_backtrack(n, f, p, v, t, min_cnt, min_sc, max_drop, &n_u, &n_v);
 	*n_u_ = n_u, *_u = u;

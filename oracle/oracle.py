@@ -148,6 +148,8 @@ def lib():
         L.mmo_lchain_rmq.restype = C.c_void_p
         L.mmo_lchain_rmq.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                      C.c_int64, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_void_p)]
+        L.mmo_lchain_rmq_fill.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -331,6 +333,21 @@ class OracleAligner:
         aa = np.ctypeslib.as_array(C.cast(b, C.POINTER(C.c_uint64)), shape=(nv, 2)).copy()
         L.free(u); L.free(b)
         return ua, aa
+
+    def rmq_fill(self, sorted_anchors, bw):
+        """f, p, v of mg_lchain_rmq's fill loop on anchors sorted by x, before the backtrack (bw: mo.bw for the primary chainer of the
+        MM_F_RMQ presets, mo.bw_long for the long-join re-chain)"""
+        L = lib()
+        n = sorted_anchors.shape[0]
+        a = np.ascontiguousarray(sorted_anchors, dtype=np.uint64)
+        f = np.zeros(n, np.int32); p = np.zeros(n, np.int64); v = np.zeros(n, np.int32)
+        mo = self.mo
+        pen_gap = np.float32(np.float64(mo.chain_gap_scale) * 0.01 * self.k)
+        pen_skip = np.float32(np.float64(mo.chain_skip_scale) * 0.01 * self.k)
+        if n:
+            L.mmo_lchain_rmq_fill(mo.max_gap, mo.rmq_inner_dist, bw, mo.max_chain_skip, mo.rmq_size_cap, pen_gap, pen_skip,
+                                  n, a.ctypes.data, f.ctypes.data, p.ctypes.data, v.ctypes.data)
+        return f, p, v
 
     def chains_final(self, anchors, qlen):
         """what mm_map_frag (mmo_map.c) holds before mm_gen_regs: (u, anchors, did) with did bit 0 = primary RMQ chainer ran, bit 1 = long-join re-chain ran.  MM_F_RMQ presets: mg_lchain_rmq is the primary
