@@ -517,15 +517,15 @@ struct BamDevFmt : BamFmt {
 	{
 		double k_us = 0, d_us = 0;
 		int64_t n_out = bgzf_size(k.n_text), n_stored = 0;
-		if (c->bgzf_level)
+		if (k.last.level)
 			if (int rc = bam_deflate_device(c, (const char*)c->rec_text.p, k.n_text, &n_out, k.times, &d_us, &n_stored)) return rc;
 		mm355_text_t *T = mm355_text_alloc(k.n_reads, k.n_lines, n_out);
 		if (T == 0) return MM355_ENOMEM;
 		hipError_t e = hipMemcpyAsync(T->line_off, d_lo, (size_t)(k.n_reads + 1) * 8, hipMemcpyDeviceToHost, c->st);
-		int rc = e != hipSuccess? MM355_EHIP : c->bgzf_level? bam_blocks_back(c, n_out, T->text) : bam_frame_device(c, (const char*)c->rec_text.p, k.n_text, T->text, k.times, &k_us);
+		int rc = e != hipSuccess? MM355_EHIP : k.last.level? bam_blocks_back(c, n_out, T->text) : bam_frame_device(c, (const char*)c->rec_text.p, k.n_text, T->text, k.times, &k_us);
 		if (rc) { fprintf(stderr, "[mm355] error %d in the BAM writer (%s)\n", rc, hipGetErrorString(e)); mm355_free_text_host(T); return rc; }
 		if (k.times && k.bulk_ev[1]) { float ms = 0; (void)hipEventElapsedTime(&ms, k.bulk_ev[0], k.bulk_ev[1]); *b_us = (double)ms * 1e3; }   // (the stream has been waited for)
-		if (k.times && c->bgzf_level) bam_deflate_times("records", k.n_text, n_out, n_stored, d_us, true);
+		if (k.times && k.last.level) bam_deflate_times("records", k.n_text, n_out, n_stored, d_us, true);
 		else if (k.times)
 			fprintf(stderr, "[mm355] bam_times records %lld stream_bytes %lld blocks %lld tiles %lld pack_ms %.3f k_bgzf_frame_us %.1f total_ms %.3f k_bam_bulk_us %.1f\n", (long long)k.n_lines,
 			        (long long)k.n_text, (long long)bgzf_blocks(k.n_text), (long long)k.n_tiles, k.t_packed - k.t_begin, k_us, mm355_now_ms() - k.t_begin, *b_us);
@@ -540,16 +540,16 @@ struct BamAuxDevFmt : BamDevFmt { typedef RecDevAux Dev; };
 // The sorted call (mm355_map_batch_bam_run): the kernels, sinks and bulk step are B's -- the same instantiations an unsorted call launches --
 // and the last step sorts the records where they lie instead of framing them: the result is a run.
 // MM355_BAM_TIMES=1 (tools/sort_bench.py): a line of its own with the sort step's time between two events and k_bam_bulk's
-// SPAN (mm355_map_batch_bam_run_span): the run carries the records' spans, from k_rec_span behind the permutation; the line ends with its time
-// PACKED (mm355_map_batch_bam_run_packed): the records stay in HBM and are deflated there; the run carries their BGZF members
-template <typename B, bool SPAN = false, bool PACKED = false> struct BamRunFmtOf : B {
+// k.last.span (mm355_map_batch_bam_run_span): the run carries the records' spans, from k_rec_span behind the permutation; the line ends with its time
+// k.last.packed (mm355_map_batch_bam_run_packed): the records stay in HBM and are deflated there; the run carries their BGZF members
+template <typename B> struct BamRunFmtOf : B {
 	typedef B Kern;
 	static int finish(mm355_ctx *c, RecCall &k, const int64_t *, mm355_run_t **out)
 	{
 		double s_us = 0, b_us = 0, sp_us = 0;
-		const bool packed = PACKED;
-		mm355_run_t *R = mm355_run_alloc(k.n_lines, packed? 0 : k.n_text, SPAN);
-		int rc = R? bam_sort_device(c, (const char*)c->rec_text.p, k.n_text, k.d_off, k.n_lines, R, &s_us, SPAN && k.times? &sp_us : 0, !packed) : MM355_ENOMEM;
+		const bool span = k.last.span, packed = k.last.packed;
+		mm355_run_t *R = mm355_run_alloc(k.n_lines, packed? 0 : k.n_text, span);
+		int rc = R? bam_sort_device(c, (const char*)c->rec_text.p, k.n_text, k.d_off, k.n_lines, R, &s_us, span && k.times? &sp_us : 0, !packed) : MM355_ENOMEM;
 		if (rc == 0 && packed) rc = bam_run_pack_device(c, k.n_text, R, k.times);
 		if (rc == 0 && k.times && k.bulk_ev[1]) { float ms = 0; (void)hipEventElapsedTime(&ms, k.bulk_ev[0], k.bulk_ev[1]); b_us = (double)ms * 1e3; }   // (the stream has been waited for)
 		for (hipEvent_t &e : k.bulk_ev) if (e) { (void)hipEventDestroy(e); e = 0; }
@@ -562,7 +562,7 @@ template <typename B, bool SPAN = false, bool PACKED = false> struct BamRunFmtOf
 		if (k.times) {
 			fprintf(stderr, "[mm355] bam_sort_times records %lld stream_bytes %lld tiles %lld k_rec_key_sort_permute_us %.1f k_bam_bulk_us %.1f total_ms %.3f", (long long)k.n_lines,
 			        (long long)k.n_text, (long long)k.n_tiles, s_us, b_us, mm355_now_ms() - k.t_begin);
-			if (SPAN) fprintf(stderr, " k_rec_span_us %.1f", sp_us);
+			if (span) fprintf(stderr, " k_rec_span_us %.1f", sp_us);
 			fprintf(stderr, "\n");
 		}
 		R->ms_sort = s_us / 1e3;
@@ -570,10 +570,6 @@ template <typename B, bool SPAN = false, bool PACKED = false> struct BamRunFmtOf
 		return 0;
 	}
 };
-typedef BamRunFmtOf<BamDevFmt> BamRunDevFmt;
-typedef BamRunFmtOf<BamAuxDevFmt> BamAuxRunDevFmt;
-typedef BamRunFmtOf<BamDevFmt, true> BamRunSpanDevFmt;
-typedef BamRunFmtOf<BamAuxDevFmt, true> BamAuxRunSpanDevFmt;
 
 // MM355_PAF_AUTO for BAM: the device formatter from this many hits on.  Measured with tools/bam_bench.py (profiles/bam_file.json, format_sweep:
 // ms_format of the two formatters on the hits of 16 .. 9216 reads, map-ont with cs, reads of N50 8 kb with qualities): the host is ahead at 16
@@ -586,24 +582,108 @@ struct BamDeflateFmt : BamFmt {
 	static int64_t frame_host(const char *raw, int64_t n, char *out) { return mm355_bgzf_deflate_host(raw, n, out); }
 };
 
+// the host formatter's records as they are: BamFmt without the framing (a sorted call sorts them)
+struct BamRawFmt : BamFmt {
+	static constexpr bool FRAMED = false;
+	static int64_t out_size(int64_t n) { return n; }
+};
+
+// ---- one BAM call.  Every entry point below states its call as a plan and forwards, after its own argument checks, to bam_format (a batch
+// result in hand) or bam_map_format (reads in hand).  level, span and packed (RecLast) reach the device formatter's last step in the RecCall;
+// ax: the copied tags; the result goes to *text as BGZF blocks or, a sorted call, to *run as a run
+struct BamPlan : RecLast {
+	RecAux ax;
+	mm355_text_t **text = 0; mm355_run_t **run = 0;
+	BamPlan(const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod) { if (aux) { ax.aux = aux; ax.len = aux_len; ax.mod = aux_mod; } }
+	bool sorted() const { return run != 0; }
+};
+static BamPlan bam_plan_blocks(const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod, int level, mm355_text_t **out)
+{ BamPlan p(aux, aux_len, aux_mod); p.level = level; p.text = out; return p; }
+static BamPlan bam_plan_run(const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod, bool span, bool packed, mm355_run_t **out)
+{ BamPlan p(aux, aux_len, aux_mod); p.span = span; p.packed = packed; p.run = out; return p; }
+// false: the caller gave no place for the result; otherwise that place is cleared
+static bool bam_plan_open(const BamPlan &p)
+{
+	if (p.text == 0 && p.run == 0) return false;
+	if (p.sorted()) *p.run = 0; else *p.text = 0;
+	return true;
+}
+
+// a run from the device formatter: the kernels an unsorted call launches, then the sort where the records were formed
+static int bam_run_device(mm355_ctx_t *c, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens, const char *const *quals,
+                          const int32_t *rep_len, int sam_flags, const BamPlan &p)
+{
+	const int rc = p.ax.aux? rec_format_device_to<BamRunFmtOf<BamAuxDevFmt>, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, p.run, p.ax, p)
+	                       : rec_format_device_to<BamRunFmtOf<BamDevFmt>, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, p.run, p.ax, p);
+	if (rc) return rc;
+	mm355_run_t *R = *p.run;
+	R->on_device = 1;
+	// the empty run comes from rec_text_empty, which knows no plan: the arrays a run with spans and a packed run always have (no member)
+	if ((p.span && R->span == 0 && (R->span = (int64_t*)malloc(8)) == 0) || (p.packed && !R->packed && (R->blk_off = (int64_t*)calloc(1, 8)) == 0)) {
+		mm355_free_run_host(R); *p.run = 0;
+		return MM355_ENOMEM;
+	}
+	if (p.packed) R->packed = 1;
+	return 0;
+}
+// a run from the host formatter: its unframed records, the host sort and, packed, the serial coder (the device's bytes)
+static int bam_run_host(const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens, const char *const *quals, const int32_t *rep_len,
+                        const PafNames &nm, int sam_flags, const BamPlan &p)
+{
+	mm355_text_t *T = 0;
+	if (int rc = mm355_rec_format_host<BamRawFmt>(H, qnames, seqs, qlens, quals, rep_len, nm, sam_flags, &T, p.ax)) return rc;
+	std::vector<int64_t> off((size_t)T->n_lines + 1);
+	int64_t at = 0;
+	for (int64_t i = 0; i < T->n_lines; ++i) { off[(size_t)i] = at; at += (int64_t)bam_rec_u32((const uint8_t*)T->text + at) + 4; }   // (the writer's own block_size words)
+	off[(size_t)T->n_lines] = at;
+	const double t0 = mm355_now_ms();
+	int rc = at != T->n_text? MM355_EINVAL : p.span? bam_span_check(T->text, off.data(), T->n_lines) : 0;
+	if (rc == 0) rc = p.span? bam_sort_run_span_host(T->text, T->n_text, off.data(), T->n_lines, p.run) : bam_sort_run_host(T->text, T->n_text, off.data(), T->n_lines, p.run);
+	if (rc == 0) (*p.run)->ms_sort = mm355_now_ms() - t0;
+	if (rc == 0 && p.packed && (rc = bam_run_pack_host(*p.run)) != 0) { mm355_free_run_host(*p.run); *p.run = 0; }
+	mm355_free_text_host(T);
+	return rc;
+}
+
+// format: the records of a batch result as the plan says -- the input check, the choice of formatter, blocks or a run
+static int bam_format(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens,
+                      const char *const *quals, const int32_t *rep_len, int sam_flags, int where, const BamPlan &p)
+{
+	if (!bam_plan_open(p)) return MM355_EINVAL;
+	if (c == 0 || mo == 0 || H == 0 || where < MM355_PAF_AUTO || where > MM355_PAF_DEVICE || p.level < 0 || p.level > 1) return MM355_EINVAL;
+	if (c->mi == 0) return MM355_ENOIDX;
+	const PafNames nm = { c->mi->names.data(), c->mi->n_seq };
+	if (int rc = mm355_bam_check_aux(H, nm, (mo->flag & MMF_CIGAR) != 0, qnames, seqs, qlens, rep_len, sam_flags, p.ax)) return rc;
+	if (p.sorted())
+		return rec_where(where, H->n_hits, "MM355_BAM_MIN_HITS", MM355_BAM_MIN_HITS_DEFAULT) == MM355_PAF_DEVICE? bam_run_device(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, p)
+		                                                                                                   : bam_run_host(H, qnames, seqs, qlens, quals, rep_len, nm, sam_flags, p);
+	return rec_format_where(where, H->n_hits, "MM355_BAM_MIN_HITS", MM355_BAM_MIN_HITS_DEFAULT,
+	                        [&] { return p.level? mm355_rec_format_host<BamDeflateFmt>(H, qnames, seqs, qlens, quals, rep_len, nm, sam_flags, p.text, p.ax)
+	                                            : mm355_bam_format_host(H, qnames, seqs, qlens, quals, rep_len, nm, sam_flags, p.text, p.ax); },
+	                        [&] { return p.ax.aux? rec_format_device_to<BamAuxDevFmt, mm355_text_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, p.text, p.ax, p)
+	                                             : rec_format_device_to<BamDevFmt, mm355_text_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, p.text, p.ax, p); }, p.text);
+}
+
+// map, then format: the reads mapped with rep_len kept, then bam_format on the result
+static int bam_map_format(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens, const char *const *names,
+                          const char *const *quals, int flags, int sam_flags, int where, const BamPlan &p)
+{
+	if (!bam_plan_open(p)) return MM355_EINVAL;
+	if (p.level < 0 || p.level > 1 || (p.ax.aux && (p.ax.len == 0 || p.ax.mod == 0))) return MM355_EINVAL;   // (before anything is mapped)
+	if (mo && !(mo->flag & MMF_CIGAR)) return MM355_EINVAL;
+	mm355_hits_t *H = 0; const int32_t *rep_len = 0;
+	int rc = mm355_map_batch_rl(c, mo, n_reads, seqs, lens, names, flags | MM355_OUT_TAGS, &H, &rep_len);
+	if (rc) return rc;
+	rc = bam_format(c, mo, H, names, seqs, lens, quals, rep_len, sam_flags, where, p);
+	mm355_free_hits(H);
+	return rc;
+}
+
 extern "C" int mm355_bam_format_aux(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs,
                                     const int32_t *qlens, const char *const *quals, const int32_t *rep_len, const uint8_t *const *aux, const int32_t *aux_len,
                                     const int32_t *aux_mod, int sam_flags, int where, int level, mm355_text_t **out)
 {
-	if (out == 0) return MM355_EINVAL;
-	*out = 0;
-	if (c == 0 || mo == 0 || H == 0 || where < MM355_PAF_AUTO || where > MM355_PAF_DEVICE || level < 0 || level > 1) return MM355_EINVAL;
-	if (c->mi == 0) return MM355_ENOIDX;
-	const PafNames nm = { c->mi->names.data(), c->mi->n_seq };
-	RecAux ax;
-	if (aux) { ax.aux = aux; ax.len = aux_len; ax.mod = aux_mod; }
-	if (int rc = mm355_bam_check_aux(H, nm, (mo->flag & MMF_CIGAR) != 0, qnames, seqs, qlens, rep_len, sam_flags, ax)) return rc;
-	c->bgzf_level = level;
-	return rec_format_where(where, H->n_hits, "MM355_BAM_MIN_HITS", MM355_BAM_MIN_HITS_DEFAULT,
-	                        [&] { return level? mm355_rec_format_host<BamDeflateFmt>(H, qnames, seqs, qlens, quals, rep_len, nm, sam_flags, out, ax)
-	                                          : mm355_bam_format_host(H, qnames, seqs, qlens, quals, rep_len, nm, sam_flags, out, ax); },
-	                        [&] { return ax.aux? rec_format_device<BamAuxDevFmt>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out, ax)
-	                                           : rec_format_device<BamDevFmt>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out); }, out);
+	return bam_format(c, mo, H, qnames, seqs, qlens, quals, rep_len, sam_flags, where, bam_plan_blocks(aux, aux_len, aux_mod, level, out));
 }
 
 extern "C" int mm355_bam_format_deflate(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs,
@@ -618,21 +698,11 @@ extern "C" int mm355_bam_format(mm355_ctx_t *c, const mm355_mapopt_t *mo, const 
 	return mm355_bam_format_aux(c, mo, H, qnames, seqs, qlens, quals, rep_len, 0, 0, 0, sam_flags, where, 0, out);
 }
 
-// rec_map_batch with the tags the format call takes besides
 extern "C" int mm355_map_batch_bam_aux(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
                                        const char *const *names, const char *const *quals, const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod,
                                        int flags, int sam_flags, int where, int level, mm355_text_t **out)
 {
-	if (out == 0) return MM355_EINVAL;
-	*out = 0;
-	if (level < 0 || level > 1 || (aux && (aux_len == 0 || aux_mod == 0))) return MM355_EINVAL;   // (before anything is mapped)
-	if (mo && !(mo->flag & MMF_CIGAR)) return MM355_EINVAL;
-	mm355_hits_t *H = 0; const int32_t *rep_len = 0;
-	int rc = mm355_map_batch_rl(c, mo, n_reads, seqs, lens, names, flags | MM355_OUT_TAGS, &H, &rep_len);
-	if (rc) return rc;
-	rc = mm355_bam_format_aux(c, mo, H, names, seqs, lens, quals, rep_len, aux, aux_len, aux_mod, sam_flags, where, level, out);
-	mm355_free_hits(H);
-	return rc;
+	return bam_map_format(c, mo, n_reads, seqs, lens, names, quals, flags, sam_flags, where, bam_plan_blocks(aux, aux_len, aux_mod, level, out));
 }
 
 extern "C" int mm355_map_batch_bam_deflate(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
@@ -648,12 +718,6 @@ extern "C" int mm355_map_batch_bam(mm355_ctx_t *c, const mm355_mapopt_t *mo, int
 }
 
 // ---- sorted calls
-// the host formatter's records as they are: BamFmt without the framing
-struct BamRawFmt : BamFmt {
-	static constexpr bool FRAMED = false;
-	static int64_t out_size(int64_t n) { return n; }
-};
-
 extern "C" void mm355_free_run(mm355_run_t *r) { mm355_free_run_host(r); }
 
 extern "C" int mm355_bam_gather(const void *base, int64_t base_len, const int64_t *src_off, const int64_t *len, int64_t n, void *out, int64_t out_cap)
@@ -705,92 +769,24 @@ extern "C" int mm355_bam_sort_span(mm355_ctx_t *c, const void *rec, int64_t n_by
 	return bam_sort_stage(c, rec, n_bytes, rec_off, n_rec, where, true, out);
 }
 
-// a packed run from the device formatter, with or without spans and copied tags
-template <bool SPAN, bool PACKED> static int bam_run_device(mm355_ctx_t *c, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens,
-                                                            const char *const *quals, const int32_t *rep_len, int sam_flags, mm355_run_t **out, const RecAux &ax)
-{
-	return ax.aux? rec_format_device_to<BamRunFmtOf<BamAuxDevFmt, SPAN, PACKED>, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out, ax)
-	             : rec_format_device_to<BamRunFmtOf<BamDevFmt, SPAN, PACKED>, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out);
-}
-
-// the records of a batch result as a run: mm355_bam_format_aux's check and its choice of formatter, then the sort where the records were formed
-static int bam_run_format(mm355_ctx_t *c, const mm355_mapopt_t *mo, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens,
-                          const char *const *quals, const int32_t *rep_len, const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod, int sam_flags,
-                          int where, bool span, bool packed, mm355_run_t **out)
-{
-	if (c == 0 || mo == 0 || H == 0 || where < MM355_PAF_AUTO || where > MM355_PAF_DEVICE) return MM355_EINVAL;
-	if (c->mi == 0) return MM355_ENOIDX;
-	const PafNames nm = { c->mi->names.data(), c->mi->n_seq };
-	RecAux ax;
-	if (aux) { ax.aux = aux; ax.len = aux_len; ax.mod = aux_mod; }
-	if (int rc = mm355_bam_check_aux(H, nm, (mo->flag & MMF_CIGAR) != 0, qnames, seqs, qlens, rep_len, sam_flags, ax)) return rc;
-	c->bgzf_level = 0;
-	if (rec_where(where, H->n_hits, "MM355_BAM_MIN_HITS", MM355_BAM_MIN_HITS_DEFAULT) == MM355_PAF_DEVICE) {
-		int rc;
-		if (packed) {
-			rc = span? bam_run_device<true, true>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, out, ax) : bam_run_device<false, true>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, out, ax);
-			if (rc == 0 && span && (*out)->span == 0 && ((*out)->span = (int64_t*)malloc(8)) == 0) { mm355_free_run_host(*out); *out = 0; return MM355_ENOMEM; }   // (the empty run)
-		} else if (span) {
-			rc = ax.aux? rec_format_device_to<BamAuxRunSpanDevFmt, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out, ax)
-			           : rec_format_device_to<BamRunSpanDevFmt, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out);
-			if (rc == 0 && (*out)->span == 0 && ((*out)->span = (int64_t*)malloc(8)) == 0) { mm355_free_run_host(*out); *out = 0; return MM355_ENOMEM; }   // (the empty run)
-		} else
-			rc = ax.aux? rec_format_device_to<BamAuxRunDevFmt, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out, ax)
-			           : rec_format_device_to<BamRunDevFmt, mm355_run_t>(c, H, qnames, seqs, qlens, quals, rep_len, sam_flags, true, out);
-		if (rc == 0) (*out)->on_device = 1;
-		if (rc == 0 && packed && !(*out)->packed) {                // (the empty run: no member)
-			if (((*out)->blk_off = (int64_t*)calloc(1, 8)) == 0) { mm355_free_run_host(*out); *out = 0; return MM355_ENOMEM; }
-			(*out)->packed = 1;
-		}
-		return rc;
-	}
-	mm355_text_t *T = 0;
-	if (int rc = mm355_rec_format_host<BamRawFmt>(H, qnames, seqs, qlens, quals, rep_len, nm, sam_flags, &T, ax)) return rc;
-	std::vector<int64_t> off((size_t)T->n_lines + 1);
-	int64_t at = 0;
-	for (int64_t i = 0; i < T->n_lines; ++i) { off[(size_t)i] = at; at += (int64_t)bam_rec_u32((const uint8_t*)T->text + at) + 4; }   // (the writer's own block_size words)
-	off[(size_t)T->n_lines] = at;
-	const double t0 = mm355_now_ms();
-	int rc = at != T->n_text? MM355_EINVAL : span? bam_span_check(T->text, off.data(), T->n_lines) : 0;
-	if (rc == 0) rc = span? bam_sort_run_span_host(T->text, T->n_text, off.data(), T->n_lines, out) : bam_sort_run_host(T->text, T->n_text, off.data(), T->n_lines, out);
-	if (rc == 0) (*out)->ms_sort = mm355_now_ms() - t0;
-	if (rc == 0 && packed && (rc = bam_run_pack_host(*out)) != 0) { mm355_free_run_host(*out); *out = 0; }   // (the serial coder: the device's bytes)
-	mm355_free_text_host(T);
-	return rc;
-}
-
-static int bam_map_batch_run(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
-                             const char *const *names, const char *const *quals, const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod,
-                             int flags, int sam_flags, int where, bool span, mm355_run_t **out, bool packed = false)
-{
-	if (out == 0) return MM355_EINVAL;
-	*out = 0;
-	if (aux && (aux_len == 0 || aux_mod == 0)) return MM355_EINVAL;   // (before anything is mapped)
-	if (mo && !(mo->flag & MMF_CIGAR)) return MM355_EINVAL;
-	mm355_hits_t *H = 0; const int32_t *rep_len = 0;
-	int rc = mm355_map_batch_rl(c, mo, n_reads, seqs, lens, names, flags | MM355_OUT_TAGS, &H, &rep_len);
-	if (rc) return rc;
-	rc = bam_run_format(c, mo, H, names, seqs, lens, quals, rep_len, aux, aux_len, aux_mod, sam_flags, where, span, packed, out);
-	mm355_free_hits(H);
-	return rc;
-}
+// ---- the sorted calls that map: bam_map_format with a run plan
 extern "C" int mm355_map_batch_bam_run(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
                                        const char *const *names, const char *const *quals, const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod,
                                        int flags, int sam_flags, int where, mm355_run_t **out)
 {
-	return bam_map_batch_run(c, mo, n_reads, seqs, lens, names, quals, aux, aux_len, aux_mod, flags, sam_flags, where, false, out);
+	return bam_map_format(c, mo, n_reads, seqs, lens, names, quals, flags, sam_flags, where, bam_plan_run(aux, aux_len, aux_mod, false, false, out));
 }
 extern "C" int mm355_map_batch_bam_run_span(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
                                             const char *const *names, const char *const *quals, const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod,
                                             int flags, int sam_flags, int where, mm355_run_t **out)
 {
-	return bam_map_batch_run(c, mo, n_reads, seqs, lens, names, quals, aux, aux_len, aux_mod, flags, sam_flags, where, true, out);
+	return bam_map_format(c, mo, n_reads, seqs, lens, names, quals, flags, sam_flags, where, bam_plan_run(aux, aux_len, aux_mod, true, false, out));
 }
 extern "C" int mm355_map_batch_bam_run_packed(mm355_ctx_t *c, const mm355_mapopt_t *mo, int64_t n_reads, const char *const *seqs, const int32_t *lens,
                                               const char *const *names, const char *const *quals, const uint8_t *const *aux, const int32_t *aux_len, const int32_t *aux_mod,
                                               int flags, int sam_flags, int where, int want_span, mm355_run_t **out)
 {
-	return bam_map_batch_run(c, mo, n_reads, seqs, lens, names, quals, aux, aux_len, aux_mod, flags, sam_flags, where, want_span != 0, out, true);
+	return bam_map_format(c, mo, n_reads, seqs, lens, names, quals, flags, sam_flags, where, bam_plan_run(aux, aux_len, aux_mod, want_span != 0, true, out));
 }
 
 // ---- the merge step of compressed runs (mm355_bammerge.h: the plan and the host step)

@@ -137,7 +137,7 @@ struct mm355_ctx : mm355_streams {
 	bool logt_ok = false;
 	DBuf rec_in, rec_work, rec_text; HBuf h_rec_in, h_rec_out;   // record writer (mm355_recdev.h; PAF, SAM and BAM, one call at a time): rows + arenas + names + reads up, lengths / offsets / runs / scan space, the unframed text; pinned staging both ways
 	DBuf bam_out;                          // BAM writer (mm355_bam.hip): the BGZF blocks
-	DBuf bam_stage, bam_work; int bgzf_level = 0;   // its deflate stage: the blocks at a fixed stride before they are compacted; sizes, offsets, scan space and the resident workgroups' token scratch; the level of the call in progress (0: stored)
+	DBuf bam_stage, bam_work;              // its deflate stage: the blocks at a fixed stride before they are compacted; sizes, offsets, scan space and the resident workgroups' token scratch
 	DBuf bam_sorted;                       // its sort stage (sorted calls only): the records of rec_text in key order; the merge step: the inflated slices
 	mm355_stats_t stats;
 	mm355_timer_book timers;           // lazy stage timers (EvTimer, mm355_kt)

@@ -336,9 +336,12 @@ static int rec_text_empty(int64_t nr, mm355_text_t **out)
 
 // what a call's format-specific steps are told: the records, the bytes of the unframed text in c->rec_text, the tiles, the host clock at the
 // call's begin and after the packing; times: the format's *_TIMES variable is set
-struct RecCall { int64_t n_reads, n_lines, n_text, n_tiles; double t_begin, t_packed, t_copy; bool times; hipEvent_t bulk_ev[2] = { 0, 0 }; const int64_t *d_off = 0; };   // bulk_ev: a format's own, around its bulk kernel; d_off: the n_lines + 1 record offsets on the device
+// last: what the caller asks of the format's last step (BAM: the deflate level of the blocks; a sorted call: whether the run carries spans, and
+// whether it is packed).  Run-time values: the kernels and the steps before the last one do not depend on them
+struct RecLast { int level = 0; bool span = false, packed = false; };
+struct RecCall { int64_t n_reads, n_lines, n_text, n_tiles; double t_begin, t_packed, t_copy; bool times; hipEvent_t bulk_ev[2] = { 0, 0 }; const int64_t *d_off = 0; RecLast last; };   // bulk_ev: a format's own, around its bulk kernel; d_off: the n_lines + 1 record offsets on the device
 
-// the result of a sorted call that writes nothing (mm355_bam.hip: BamRunDevFmt)
+// the result of a sorted call that writes nothing (mm355_bam.hip: BamRunFmtOf)
 static int rec_text_empty(int64_t, mm355_run_t **out)
 {
 	*out = mm355_run_alloc(0, 0);
@@ -352,12 +355,13 @@ template <typename F> struct rec_kern<F, std::void_t<typename F::Kern>> { typede
 // The driver.  F is the format's device half: its traits struct plus Count and Write (the device sinks), TIMES_ENV (the variable that
 // asks for a line of timings on stderr, or null), bulk() (with tiles: launches the bulk kernel on the run table) and finish() (the last
 // step: the result record from the text in c->rec_text and line_off[] on the device).
-// Out: the result record F::finish makes (mm355_text_t; mm355_run_t for a sorted BAM call)
+// Out: the result record F::finish makes (mm355_text_t; mm355_run_t for a sorted BAM call); last: handed to F::finish in the RecCall
 template <typename F, typename Out> static int rec_format_device_to(mm355_ctx *c, const mm355_hits_t *H, const char *const *qnames, const char *const *seqs, const int32_t *qlens,
-                                                                    const char *const *quals, const int32_t *rep_len, int sam_flags, bool has_cigar, Out **out, const RecAux &ax = RecAux())
+                                                                    const char *const *quals, const int32_t *rep_len, int sam_flags, bool has_cigar, Out **out, const RecAux &ax = RecAux(),
+                                                                    const RecLast &last = RecLast())
 {
 	typedef typename rec_kern<F>::type K;
-	RecCall k; k.n_reads = H->n_reads; k.n_tiles = 0;
+	RecCall k; k.n_reads = H->n_reads; k.n_tiles = 0; k.last = last;
 	const char *te = F::TIMES_ENV? getenv(F::TIMES_ENV) : 0; k.times = te && *te && *te != '0';   // (read per call)
 	k.t_begin = mm355_now_ms();
 	typename F::Dev D;

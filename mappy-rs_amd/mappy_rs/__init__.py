@@ -14,7 +14,6 @@ import collections
 import collections.abc
 import ctypes as C
 import os
-import queue
 import struct
 import tempfile
 import threading
@@ -27,7 +26,7 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, _pipeline
 
 __all__ = ["Aligner", "Mapping", "paf_line", "sam_lines", "shard_by_bases", "order_by_length", "bgzf_unwrap", "bam_aux_split"]
 
@@ -596,6 +595,203 @@ def _cs_flag(cs):
     raise ValueError("`cs` must be False, True, 'short' or 'long'")
 
 
+# one entry point of the C-ABI that maps reads and writes records: the function; whether it takes qualities and sam_flags (SAM, BAM); whether it
+# takes the three aux arguments; what stands between `where` and the result; the result's type (_ffi.Text, or _ffi.Run for a sorted call)
+_Entry = collections.namedtuple("_Entry", "fn sam aux tail out")
+
+
+def _check_reads(seqs, names, quals=None):
+    """the reads of a one-call writer, checked: (seqs as a list, names as a list or None, None or (the qualities as a char* array, what it
+    points into))"""
+    seqs = list(seqs)
+    for s in seqs:
+        if not isinstance(s, str):
+            raise TypeError("argument 'seq': 'bytes' object cannot be converted to 'PyString'" if isinstance(s, bytes)
+                            else "argument 'seq' must be str")
+    if names is not None:
+        names = list(names)
+        if len(names) != len(seqs) or not all(nm is None or isinstance(nm, str) for nm in names):
+            raise ValueError("`names` must hold a string or None for every read")
+    if quals is None:
+        return seqs, names, None
+    quals = list(quals)
+    if len(quals) != len(seqs) or not all(q is None or (isinstance(q, str) and len(q) == len(s) and q.isascii()) for q, s in zip(quals, seqs)):
+        raise ValueError("`quals` must hold None or an ASCII string of the read's length for every read")
+    if not all(q is None or s.isascii() for q, s in zip(quals, seqs)):
+        raise ValueError("a read that has a quality string must be ASCII: its quality is matched to it byte by byte")
+    qkeep = [None if q is None else q.encode() for q in quals]
+    return seqs, names, ((C.c_char_p * len(qkeep))(*qkeep), qkeep)
+
+
+# what map_bam_file adds to a map_file call (map_bam_file's docstring)
+_FileOpts = collections.namedtuple("_FileOpts", "sam_flags compress read_on_gpu keep_aux sort tmp_dir index tmp_compress",
+                                   defaults=(0, False, False, None, False, None, False, False))
+
+# what a worker of _map_file hands on for one sub-batch: the result record (mm355_text_t or mm355_run_t), its reads, bases and bytes of kept tags
+_SubBatch = collections.namedtuple("_SubBatch", "tp n_reads n_bases n_aux")
+
+# the sorted run of one sub-batch as the merge needs it: the records' keys and lengths in key order, where the run's bytes begin in the spool,
+# the records' spans (index=True; else empty), and the offsets of its BGZF members in its bytes (a packed run; else None)
+_Run = collections.namedtuple("_Run", "keys lens place spans blk_off")
+
+
+class _TextSink:
+    """where the results of an unsorted file go: the texts, written in input order"""
+
+    def __init__(self, out):
+        self.out, self.n_lines, self.n_dev, self.ms_format, self.n_out = out, 0, 0, 0.0, 0
+
+    def take(self, k, tp):
+        t = tp.contents
+        self.n_lines += int(t.n_lines); self.n_dev += int(t.on_device); self.ms_format += float(t.ms_format); self.n_out += int(t.n_text)
+        self.out.write(_ffi.text_view(tp))
+
+
+class _RunSpool:
+    """where the results of a sorted file go: every run's bytes (its records; the BGZF members of a packed run) appended to the temporary
+    file as the runs complete, and per run the tables the merge needs (24 bytes per record, 32 with spans)"""
+
+    def __init__(self, tmp, index, packed):
+        self.tmp, self.index, self.packed = tmp, index, packed
+        self.runs, self.n_tmp, self.n_raw = {}, 0, 0      # per sub-batch; the spool's bytes; packed: the bytes of the records its members hold
+        self.n_lines, self.n_dev, self.ms_format = 0, 0, 0.0
+
+    def take(self, k, tp):
+        t = tp.contents
+        n = int(t.n_rec)
+        self.n_lines += n; self.n_dev += int(t.on_device); self.ms_format += float(t.ms_sort)
+        keys = np.ctypeslib.as_array(t.key, shape=(n,)).copy() if n else np.zeros(0, np.uint64)
+        lens = np.diff(np.ctypeslib.as_array(t.rec_off, shape=(n + 1,))) if n else np.zeros(0, np.int64)
+        spans = np.ctypeslib.as_array(t.span, shape=(n,)).copy() if self.index and n else np.zeros(0, np.int64)
+        blk_off = None
+        if self.packed:
+            blk_off = np.ctypeslib.as_array(t.blk_off, shape=(int(t.n_blk) + 1,)).copy()
+            self.n_raw += int(t.rec_off[n])
+        self.runs[k] = _Run(keys, lens, self.n_tmp, spans, blk_off)
+        if t.n_bytes:
+            self.tmp.write(memoryview((C.c_char * int(t.n_bytes)).from_address(C.addressof(t.rec.contents))))
+        self.n_tmp += int(t.n_bytes)
+
+
+class _GatherStep:
+    """a step of the merge of plain runs: the records gathered from the spool (mm355_bam_gather) into a host buffer behind the bytes the
+    last step left over, and the whole payloads framed (level 0, on the host: no context) or deflated (mm355_bgzf_deflate on the device)"""
+
+    def __init__(self, L, level):
+        self.L, self.level, self.where = L, level, _ffi.PAF_DEVICE if level else _ffi.PAF_HOST
+
+    def begin(self, runs, order, spool):
+        self.spool, self.carry = spool, np.zeros(0, np.uint8)
+        self.src = np.ascontiguousarray(np.concatenate([r.place + np.cumsum(r.lens, dtype=np.int64) - r.lens for r in runs])[order])
+
+    def blocks(self, ctx, i, lens, last):
+        L, carry, j, n_new = self.L, self.carry, i + len(lens), int(lens.sum())
+        buf = np.empty(len(carry) + n_new, np.uint8)
+        buf[:len(carry)] = carry
+        _ffi.check(L.mm355_bam_gather(self.spool.ctypes.data, len(self.spool), self.src[i:j].ctypes.data, lens.ctypes.data, j - i, buf.ctypes.data + len(carry), n_new))
+        # whole payloads now; what is left opens the next step's buffer (the last step writes everything)
+        n_now = len(buf) if last else len(buf) // 0xff00 * 0xff00
+        self.carry = buf[n_now:].copy()
+        if not n_now:
+            return None
+        tp = C.POINTER(_ffi.Text)()
+        _ffi.check(L.mm355_bgzf_deflate(ctx, C.cast(buf.ctypes.data, C.c_char_p), n_now, self.where, self.level, C.byref(tp)))
+        return tp
+
+
+class _PackedStep:
+    """a step of the merge of packed runs (map_bam_file(tmp_compress=True)).  A step is a contiguous range of the merged order, so it takes
+    from every run a contiguous range of that run's records: record counts per run (a bincount) and a running count of what earlier
+    steps took give the raw range [lo, hi) each run contributes, the members [lo // 0xff00, ceil(hi / 0xff00)) hold it, and one
+    mm355_bam_merge_step call turns the slices and the records' places into the step's blocks, the leftover bytes staying with the call.
+    The file writers run it on the device whatever the level; the host `where` is the C-ABI's and the tests'."""
+
+    def __init__(self, L, level, where=_ffi.PAF_DEVICE):
+        self.L, self.level, self.where = L, level, where
+
+    def begin(self, runs, order, spool):
+        n_runs = len(runs)
+        counts = np.array([len(r.keys) for r in runs], np.int64)
+        self.spool = spool
+        self.run_of = np.repeat(np.arange(n_runs, dtype=np.int64), counts)[order]
+        self.raw_all = np.concatenate([np.concatenate(([0], np.cumsum(r.lens, dtype=np.int64))) for r in runs])     # per run its n + 1 raw offsets
+        self.raw_first = np.cumsum(counts + 1) - (counts + 1)
+        self.at = np.ascontiguousarray(np.concatenate([np.cumsum(r.lens, dtype=np.int64) - r.lens for r in runs])[order])   # a record's place in its run's unframed stream
+        self.blk_all = np.concatenate([r.blk_off for r in runs]).astype(np.int64, copy=False)                      # per run its n_blk + 1 member offsets
+        blk_n = np.array([len(r.blk_off) for r in runs], np.int64)
+        self.blk_first = np.cumsum(blk_n) - blk_n
+        self.place = np.array([r.place for r in runs], np.int64)
+        self.carry, self.n_carry = np.empty(0xff00, np.uint8), C.c_int64(0)
+        self.taken = np.zeros(n_runs, np.int64)          # the records of every run that earlier steps took
+        self.slice_of_run = np.empty(n_runs, np.int32)
+
+    def blocks(self, ctx, i, lens, last):
+        P, j, carry = 0xff00, i + len(lens), self.carry
+        took = np.bincount(self.run_of[i:j], minlength=len(self.taken))
+        sel = np.flatnonzero(took)
+        first = self.raw_first[sel] + self.taken[sel]
+        lo, hi = self.raw_all[first], self.raw_all[first + took[sel]]
+        m_lo, m_hi = lo // P, (hi + P - 1) // P
+        b_lo, b_hi = self.blk_all[self.blk_first[sel] + m_lo], self.blk_all[self.blk_first[sel] + m_hi]
+        slice_at, slice_bytes, slice_raw_at = np.ascontiguousarray(self.place[sel] + b_lo), np.ascontiguousarray(b_hi - b_lo), np.ascontiguousarray(m_lo * P)
+        self.slice_of_run[sel] = np.arange(len(sel), dtype=np.int32)
+        rec_slice = np.ascontiguousarray(self.slice_of_run[self.run_of[i:j]])
+        self.taken += took
+        tp = C.POINTER(_ffi.Text)()
+        _ffi.check(self.L.mm355_bam_merge_step(ctx, self.spool.ctypes.data, len(self.spool), slice_at.ctypes.data, slice_bytes.ctypes.data, slice_raw_at.ctypes.data, len(sel),
+                                               rec_slice.ctypes.data, self.at[i:j].ctypes.data, lens.ctypes.data, j - i, carry.ctypes.data, self.n_carry.value,
+                                               1 if last else 0, self.where, self.level, C.byref(tp), carry.ctypes.data, C.byref(self.n_carry)))
+        return tp
+
+
+def _merge(L, runs, spool, out, step, bai=None, contexts=None):
+    """the merge phase of map_bam_file(sort=True).  runs: the _Run of every sub-batch, in input order, the records of a run in key order;
+    spool: their bytes, one array (the memory-mapped temporary file).  The stable argsort of the concatenated keys is the k-way merge -- and
+    the stable sort of the unsorted file, because ties inside a run are in input order already.  The merged order is cut into steps of
+    SORT_CHUNK_BYTES; `step` (_GatherStep, _PackedStep) makes the BGZF blocks of each, carrying what does not fill a block into the next, and
+    they are written to `out`.  Array operations and one or two library calls per step: no Python work per record.
+    bai: the .bai builder -- it gets the ordered keys, spans and lengths once, and every step's blocks as they are written.
+    contexts: (acquire, release) of the pool; one is taken for the steps where `step` runs on the device, none otherwise.
+    Returns (the bytes written, the seconds spent in the builder's calls)"""
+    keys = np.concatenate([r.keys for r in runs]) if runs else np.zeros(0, np.uint64)
+    if len(keys) == 0:
+        return 0, 0.0
+    order = np.argsort(keys, kind="stable")
+    lens = np.ascontiguousarray(np.concatenate([r.lens for r in runs]).astype(np.int64, copy=False)[order])
+    n_out, t_index = 0, 0.0
+    if bai is not None:
+        t_ix = time.perf_counter()
+        keys, spans = np.ascontiguousarray(keys[order]), np.ascontiguousarray(np.concatenate([r.spans for r in runs])[order])
+        _ffi.check(L.mm355_bai_records(bai, keys.ctypes.data, spans.ctypes.data, lens.ctypes.data, len(lens)))
+        t_index += time.perf_counter() - t_ix
+    end_at = np.cumsum(lens)                         # the sorted stream's offset behind every record
+    step.begin(runs, order, spool)
+    dev_ctx = contexts[0](0) if step.where == _ffi.PAF_DEVICE else None
+    try:
+        i, n = 0, len(lens)
+        while i < n:
+            base = int(end_at[i - 1]) if i else 0
+            j = max(i + 1, int(np.searchsorted(end_at, base + SORT_CHUNK_BYTES, side="right")))
+            tp = step.blocks(dev_ctx[1] if dev_ctx else None, i, lens[i:j], j == n)
+            i = j
+            if tp is None:
+                continue
+            try:
+                if tp.contents.n_text:
+                    n_out += int(tp.contents.n_text)
+                    out.write(_ffi.text_view(tp))
+                    if bai is not None:
+                        t_ix = time.perf_counter()
+                        _ffi.check(L.mm355_bai_blocks(bai, C.addressof(tp.contents.text.contents), int(tp.contents.n_text)))
+                        t_index += time.perf_counter() - t_ix
+            finally:
+                L.mm355_free_text(tp)
+    finally:
+        if dev_ctx is not None:
+            contexts[1](dev_ctx)
+    return n_out, t_index
+
+
 class Aligner:
     """mappy-compatible aligner (lib.rs:288-671) whose mapping path runs on MI355X GPUs.
 
@@ -989,28 +1185,7 @@ class Aligner:
         where (keyword-only): _ffi.PAF_AUTO (the library picks the formatter by the hit count), PAF_HOST or PAF_DEVICE; which one wrote the
         text of the last call is kept in `paf_on_device`."""
         flags = self._paf_flags(cs, MD)
-        seqs = list(seqs)
-        for s in seqs:
-            if not isinstance(s, str):
-                raise TypeError("argument 'seq': 'bytes' object cannot be converted to 'PyString'" if isinstance(s, bytes)
-                                else "argument 'seq' must be str")
-        if names is not None:
-            names = list(names)
-            if len(names) != len(seqs) or not all(nm is None or isinstance(nm, str) for nm in names):
-                raise ValueError("`names` must hold a string or None for every read")
-        L = self._L
-        packed, narr = _ffi.pack_reads(seqs), _ffi.pack_names(names)
-        tp = C.POINTER(_ffi.Text)()
-        with self._lock:
-            rc = L.mm355_map_batch_paf(self._context(), C.byref(self._mo), len(seqs), packed.arr, packed.lens, narr, flags, int(where),
-                                       C.byref(tp))
-        if rc != 0:
-            raise RuntimeError(L.mm355_strerror(rc).decode())
-        try:
-            self.paf_on_device = bool(tp.contents.on_device)
-            return bytes(_ffi.text_view(tp))
-        finally:
-            L.mm355_free_text(tp)
+        return self._map_records(seqs, names, None, flags, 0, where, _Entry(self._L.mm355_map_batch_paf, False, False, (), _ffi.Text))
 
     paf_on_device = None              # whether the device formatter wrote the text of the last map_paf / map_sam call
 
@@ -1034,63 +1209,57 @@ class Aligner:
         Mapping objects.  The lines of a read are sam_lines() of the records map() would return with tags; a read without hits writes one
         unmapped record unless hit_only (minimap2 --sam-hit-only); an empty sequence writes nothing.  names as in map_paf; quals[i] is None or
         a str as long as the read; softclip: minimap2 -Y.  where and `paf_on_device`: as for map_paf."""
-        return self._map_records(self._L.mm355_map_batch_sam, seqs, names, quals, cs, MD, softclip, hit_only, where)
-
-    def _map_records(self, call, seqs, names, quals, cs, MD, softclip, hit_only, where, run_level=None):
-        """map_sam / map_bam: the arguments checked, one call of mm355_map_batch_sam or mm355_map_batch_bam, the text as bytes.
-        run_level (map_bam(sort=True)): `call` returns a run (mm355_map_batch_bam_run); its records go through mm355_bgzf_deflate at that level"""
-        flags = self._sam_flags(cs, MD)
-        seqs = list(seqs)
-        for s in seqs:
-            if not isinstance(s, str):
-                raise TypeError("argument 'seq': 'bytes' object cannot be converted to 'PyString'" if isinstance(s, bytes)
-                                else "argument 'seq' must be str")
-        if names is not None:
-            names = list(names)
-            if len(names) != len(seqs) or not all(nm is None or isinstance(nm, str) for nm in names):
-                raise ValueError("`names` must hold a string or None for every read")
-        qarr = qkeep = None
-        if quals is not None:
-            quals = list(quals)
-            if len(quals) != len(seqs) or not all(q is None or (isinstance(q, str) and len(q) == len(s) and q.isascii()) for q, s in zip(quals, seqs)):
-                raise ValueError("`quals` must hold None or an ASCII string of the read's length for every read")
-            if not all(q is None or s.isascii() for q, s in zip(quals, seqs)):
-                raise ValueError("a read that has a quality string must be ASCII: its quality is matched to it byte by byte")
-            qkeep = [None if q is None else q.encode() for q in quals]
-            qarr = (C.c_char_p * len(qkeep))(*qkeep)
-        L = self._L
-        packed, narr = _ffi.pack_reads(seqs), _ffi.pack_names(names)
         sam_flags = (_ffi.SAM_SOFTCLIP if softclip else 0) | (_ffi.SAM_HIT_ONLY if hit_only else 0)
-        tp = C.POINTER(_ffi.Text)()
-        if run_level is not None:
-            rp = C.POINTER(_ffi.Run)()
-            with self._lock:
-                rc = call(self._context(), C.byref(self._mo), len(seqs), packed.arr, packed.lens, narr, qarr, flags, sam_flags, int(where), C.byref(rp))
-                if rc != 0:
-                    raise RuntimeError(L.mm355_strerror(rc).decode())
-                try:
-                    r = rp.contents
-                    self.paf_on_device = bool(r.on_device)
-                    # deflated where the records were sorted; stored blocks are the host's (mm355_bgzf_wrap's rule)
-                    rc = L.mm355_bgzf_deflate(self._context(), C.cast(r.rec, C.c_char_p), r.n_bytes, _ffi.PAF_DEVICE if run_level and r.on_device else _ffi.PAF_HOST,
-                                              run_level, C.byref(tp))
-                finally:
-                    L.mm355_free_run(rp)
-            if rc != 0:
-                raise RuntimeError(L.mm355_strerror(rc).decode())
-            try:
-                return bytes(_ffi.text_view(tp))
-            finally:
-                L.mm355_free_text(tp)
-        with self._lock:
-            rc = call(self._context(), C.byref(self._mo), len(seqs), packed.arr, packed.lens, narr, qarr, flags, sam_flags, int(where), C.byref(tp))
+        return self._map_records(seqs, names, quals, self._sam_flags(cs, MD), sam_flags, where, _Entry(self._L.mm355_map_batch_sam, True, False, (), _ffi.Text))
+
+    def _bam_entry(self, level, aux, sort, index=False, packed=False):
+        """the entry point of a BAM call, chosen once from what the call asks for: sorted calls return a run (with spans for the index, packed
+        for a compressed spool) and always take the aux arguments; an unsorted call takes them only where there are tags"""
+        L = self._L
+        if sort and packed:
+            return _Entry(L.mm355_map_batch_bam_run_packed, True, True, (1 if index else 0,), _ffi.Run)
+        if sort:
+            return _Entry(L.mm355_map_batch_bam_run_span if index else L.mm355_map_batch_bam_run, True, True, (), _ffi.Run)
+        if aux:
+            return _Entry(L.mm355_map_batch_bam_aux, True, True, (level,), _ffi.Text)
+        if level:
+            return _Entry(L.mm355_map_batch_bam_deflate, True, False, (1,), _ffi.Text)
+        return _Entry(L.mm355_map_batch_bam, True, False, (), _ffi.Text)
+
+    def _call_entry(self, e, ctx, reads, quals, aux, flags, sam_flags, where):
+        """one call of the entry point `e` on `ctx`: reads = (n, seqs, lens, names) and aux = (blocks, lengths, mod_off) as the C-ABI takes
+        them; returns (rc, the pointer to the result record)"""
+        tp = C.POINTER(e.out)()
+        a = (ctx, C.byref(self._mo)) + tuple(reads) + ((quals,) if e.sam else ()) + (tuple(aux) if e.aux else ()) + (flags,) + ((sam_flags,) if e.sam else ())
+        return e.fn(*a, int(where), *e.tail, C.byref(tp)), tp
+
+    def _take_text(self, rc, tp, note=True):
+        """the end of a one-call writer: rc checked, which formatter wrote the text kept in `paf_on_device` (note), the text as bytes, the record freed"""
         if rc != 0:
-            raise RuntimeError(L.mm355_strerror(rc).decode())
+            raise RuntimeError(self._L.mm355_strerror(rc).decode())
         try:
-            self.paf_on_device = bool(tp.contents.on_device)
+            if note:
+                self.paf_on_device = bool(tp.contents.on_device)
             return bytes(_ffi.text_view(tp))
         finally:
-            L.mm355_free_text(tp)
+            self._L.mm355_free_text(tp)
+
+    def _map_records(self, seqs, names, quals, flags, sam_flags, where, entry, aux=(None, None, None), run_level=0):
+        """map_paf / map_sam / map_bam: the arguments checked, one call of `entry` on the aligner's own context, the text as bytes.
+        An entry that returns a run (map_bam(sort=True)): its records go through mm355_bgzf_deflate at run_level"""
+        seqs, names, qarr = _check_reads(seqs, names, quals)
+        L, note = self._L, entry.out is _ffi.Text
+        packed, narr = _ffi.pack_reads(seqs), _ffi.pack_names(names)
+        with self._lock:
+            rc, tp = self._call_entry(entry, self._context(), (len(seqs), packed.arr, packed.lens, narr), qarr and qarr[0], aux, flags, sam_flags, where)
+            if rc == 0 and not note:        # a run: deflated where the records were sorted; stored blocks are the host's (mm355_bgzf_wrap's rule)
+                rp, tp = tp, C.POINTER(_ffi.Text)()
+                r = rp.contents
+                self.paf_on_device = bool(r.on_device)
+                rc = L.mm355_bgzf_deflate(self._context(), C.cast(r.rec, C.c_char_p), r.n_bytes, _ffi.PAF_DEVICE if run_level and r.on_device else _ffi.PAF_HOST,
+                                          run_level, C.byref(tp))
+                L.mm355_free_run(rp)
+        return self._take_text(rc, tp, note)
 
     # ---- BAM records (mm355_map_batch_bam): the BAM encoding of map_sam's lines in stored BGZF blocks, formed by the library
     def map_bam(self, seqs, names=None, quals=None, cs=False, MD=False, *, softclip=False, hit_only=False, where=_ffi.PAF_AUTO, compress=False, aux=None, sort=False):
@@ -1107,12 +1276,12 @@ class Aligner:
         sort=True: the same records in coordinate order (samtools' key: contig, position, forward before reverse, unmapped last; records of
         equal key in input order) -- one mm355_map_batch_bam_run call, which sorts the records where they were formed, then
         mm355_bgzf_deflate of the sorted stream.  The blocks of THIS call's records: a file of several calls is map_bam_file(sort=True)'s."""
-        ptrs = lens = mods = None
+        aux3 = (None, None, None)
         if aux is not None:
             seqs, aux = list(seqs), list(aux)
             if len(aux) != len(seqs) or not all(a is None or isinstance(a, (bytes, bytearray)) for a in aux):
                 raise ValueError("`aux` must hold bytes or None for every read")
-            L, n = self._L, len(aux)
+            n = len(aux)
             keep, lens, mods = [None] * n, (C.c_int32 * n)(), (C.c_int32 * n)()
             for i, a in enumerate(aux):
                 if a is None:
@@ -1122,18 +1291,10 @@ class Aligner:
                 except ValueError:
                     raise ValueError("`aux[%d]` is no well-formed BAM aux block" % i) from None
                 lens[i] = len(keep[i])
-            ptrs = (C.c_void_p * n)(*[None if k is None else C.cast(C.c_char_p(k), C.c_void_p).value for k in keep])
-        if sort:
-            L = self._L
-            return self._map_records(lambda *a: L.mm355_map_batch_bam_run(*a[:7], ptrs, lens, mods, *a[7:]), seqs, names, quals, cs, MD, softclip, hit_only, where,
-                                     run_level=1 if compress else 0)
-        if aux is not None:
-            return self._map_records(lambda *a: L.mm355_map_batch_bam_aux(*a[:7], ptrs, lens, mods, *a[7:-1], 1 if compress else 0, a[-1]),
-                                     seqs, names, quals, cs, MD, softclip, hit_only, where)
-        if compress:
-            L = self._L
-            return self._map_records(lambda *a: L.mm355_map_batch_bam_deflate(*a[:-1], 1, a[-1]), seqs, names, quals, cs, MD, softclip, hit_only, where)
-        return self._map_records(self._L.mm355_map_batch_bam, seqs, names, quals, cs, MD, softclip, hit_only, where)
+            aux3 = ((C.c_void_p * n)(*[None if k is None else C.cast(C.c_char_p(k), C.c_void_p).value for k in keep]), lens, mods)
+        level = 1 if compress else 0
+        sam_flags = (_ffi.SAM_SOFTCLIP if softclip else 0) | (_ffi.SAM_HIT_ONLY if hit_only else 0)
+        return self._map_records(seqs, names, quals, self._sam_flags(cs, MD), sam_flags, where, self._bam_entry(level, aux is not None, sort), aux3, run_level=level)
 
     def bam_header(self, compress=False, rg=b"", *, sort=False):
         """the BAM header of this index as BGZF blocks (compress=True: deflated): the magic, sam_header(rg) as the text, the contigs with their
@@ -1202,8 +1363,8 @@ class Aligner:
                 if self._L.mm355_index_seq_len(self._idx, i) > BAI_MAX_LEN:
                     raise ValueError("contig %s is longer than 2^29 bases: a .bai index cannot hold it" % nm)
         sam_flags = (_ffi.SAM_SOFTCLIP if softclip else 0) | (_ffi.SAM_HIT_ONLY if hit_only else 0)
-        return self._map_file("bam", reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags, compress=bool(compress),
-                              read_on_gpu=bool(read_on_gpu), keep_aux=_keep_of(copy_tags), sort=bool(sort), tmp_dir=tmp_dir, index=bool(index), tmp_compress=bool(tmp_compress))
+        o = _FileOpts(sam_flags, bool(compress), bool(read_on_gpu), _keep_of(copy_tags), bool(sort), tmp_dir, bool(index), bool(tmp_compress))
+        return self._map_file("bam", reads_path, out_path, self._sam_flags(cs, MD), n_threads, sub_batch_reads, where, o)
 
     def map_file(self, reads_path, out_path, cs=False, MD=False, n_threads=None, sub_batch_reads=SUB_BATCH_READS, *, where=_ffi.PAF_AUTO, format="paf",
                  read_on_gpu=False):
@@ -1227,18 +1388,83 @@ class Aligner:
         text, plain gzip) is opened as without the keyword.  The returned dict then has reader_on_device (bool): which of the two happened."""
         if format not in ("paf", "sam"):
             raise ValueError("`format` must be \"paf\" or \"sam\"")
-        return self._map_file(format, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, 0, read_on_gpu=bool(read_on_gpu))
+        flags = self._sam_flags(cs, MD) if format == "sam" else self._paf_flags(cs, MD)
+        return self._map_file(format, reads_path, out_path, flags, n_threads, sub_batch_reads, where, _FileOpts(read_on_gpu=bool(read_on_gpu)))
 
-    def _map_file(self, kind, reads_path, out_path, cs, MD, n_threads, sub_batch_reads, where, sam_flags, compress=False, read_on_gpu=False, keep_aux=None, sort=False,
-                  tmp_dir=None, index=False, tmp_compress=False):
-        """map_file (kind "paf" / "sam") and map_bam_file ("bam"): reader thread, workers, ordered writer, .part file.  sort (BAM only): the
-        workers make sorted runs, the writer spools them to a temporary file, and a merge phase writes the records (map_bam_file's docstring);
-        index (with sort): the runs carry spans, the merge feeds the .bai builder, and the index is written beside the file;
-        tmp_compress (with sort): the runs are packed (BGZF members), and the merge inflates, gathers and deflates them on the device"""
-        sam = kind != "paf"                               # the reader keeps qualities, the call takes them and sam_flags
-        flags = self._sam_flags(cs, MD) if sam else self._paf_flags(cs, MD)
-        header = self.sam_header() if kind == "sam" else self.bam_header(compress, sort=sort) if kind == "bam" else b""
-        trailer = BAM_EOF if kind == "bam" else b""
+    def _open_reads(self, reads_path, sam, o):
+        """the library's streaming reader on a reads file: (the handle; whether the device inflates the file; the @RG lines of a BAM whose
+        tags are kept, else b"").  sam: the reader keeps qualities"""
+        L = self._L
+        fx = C.c_void_p()
+        rc = _ffi.MM355_EINVAL
+        if o.read_on_gpu:
+            rc = L.mm355_fastx_open_device(os.fsencode(reads_path), 1 if sam else 0, self._devices[0], C.byref(fx))
+        reader_on_device = rc == 0
+        if rc == _ffi.MM355_EINVAL:               # not asked for, or not a BGZF file: the host reader
+            rc = (L.mm355_fastx_open_qual if sam else L.mm355_fastx_open)(os.fsencode(reads_path), C.byref(fx))
+        if rc == 0 and o.keep_aux is not None:    # the tags to keep
+            rc = L.mm355_fastx_keep_aux(fx, o.keep_aux)
+            if rc != 0:
+                L.mm355_fastx_close(fx)
+        if rc != 0:
+            raise RuntimeError("%s: %s" % (reads_path, L.mm355_strerror(rc).decode()))
+        n_rg = C.c_int64()
+        rg = L.mm355_fastx_bam_rg(fx, C.byref(n_rg)) if o.keep_aux is not None else None
+        return fx, reader_on_device, C.string_at(rg, n_rg.value) if rg else b""
+
+    def _file_work(self, kind, flags, where, o):
+        """what a worker of _map_file does with one sub-batch of reads, built once per file: work(ctx, reads) -> _SubBatch.  Inside it the
+        library call is one callable, (ctx, reads) -> (rc, result, bytes of kept tags), on the entry point the file's keywords choose"""
+        L, sam = self._L, kind != "paf"
+        entry = (self._bam_entry(1 if o.compress else 0, o.keep_aux is not None, o.sort, o.index, o.tmp_compress) if kind == "bam" else
+                 _Entry(L.mm355_map_batch_sam, True, False, (), _ffi.Text) if sam else _Entry(L.mm355_map_batch_paf, False, False, (), _ffi.Text))
+
+        def call(ctx, rp):
+            r = rp.contents
+            aux, n_aux = (None, None, None), 0
+            if o.keep_aux is not None:
+                alen, amod = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
+                ap = L.mm355_reads_aux(rp, C.byref(alen), C.byref(amod))
+                if ap:
+                    n_aux = int(np.ctypeslib.as_array(alen, shape=(int(r.n),)).sum(dtype=np.int64))
+                aux = (ap, alen, amod)
+            rc, tp = self._call_entry(entry, ctx, (int(r.n), r.seqs, r.lens, r.names), L.mm355_reads_quals(rp) if sam else None, aux, flags, o.sam_flags, where)
+            return rc, tp, n_aux
+
+        def work(ctx, rp):
+            r = rp.contents
+            n_bases = int(np.ctypeslib.as_array(r.lens, shape=(int(r.n),)).sum(dtype=np.int64))
+            rc, tp, n_aux = call(ctx[1], rp)
+            if rc != 0:
+                raise RuntimeError(L.mm355_strerror(rc).decode())
+            return _SubBatch(tp, int(r.n), n_bases, n_aux)
+        return work, lambda d: (L.mm355_free_run if o.sort else L.mm355_free_text)(d.tp)
+
+    def _merge_spool(self, sink, out, level, bai):
+        """the merge phase on what the run sink holds (the workers' contexts are back in the pool: the merge takes one): (bytes written,
+        seconds in the .bai builder)"""
+        sink.tmp.flush()
+        spool = np.memmap(sink.tmp, dtype=np.uint8, mode="r", shape=(sink.n_tmp,)) if sink.n_tmp else np.zeros(0, np.uint8)
+        step = _PackedStep(self._L, level) if sink.packed else _GatherStep(self._L, level)
+        return _merge(self._L, [sink.runs[k] for k in sorted(sink.runs)], spool, out, step, bai, (self._ctx_acquire, self._ctx_release))
+
+    def _write_bai(self, bai, bai_part):
+        """the finished index to bai_part: (its bytes, the seconds that took)"""
+        t_ix = time.perf_counter()
+        tp = C.POINTER(_ffi.Text)()
+        _ffi.check(self._L.mm355_bai_finish(bai, C.byref(tp)))
+        try:
+            with open(bai_part, "wb") as f:
+                f.write(_ffi.text_view(tp))
+            return int(tp.contents.n_text), time.perf_counter() - t_ix
+        finally:
+            self._L.mm355_free_text(tp)
+
+    def _map_file(self, kind, reads_path, out_path, flags, n_threads, sub_batch_reads, where, o=_FileOpts()):
+        """map_file (kind "paf" / "sam") and map_bam_file ("bam", with its keywords in `o`).  The reader, the workers and the bound on
+        memory are _pipeline.Pipeline's; here: the arguments, the reads file, the sink -- texts written in input order, or (sort) runs
+        spooled to a temporary file as they complete and merged afterwards (_merge; index: it feeds the .bai builder; tmp_compress:
+        packed runs, merged on the device) -- the ".part" files with their rename or removal, and the returned dict"""
         L = self._L
         nt = self._n_threads if n_threads is None else int(n_threads)
         n_workers = max(1, min(nt, 8)) * len(self._devices)
@@ -1246,382 +1472,82 @@ class Aligner:
         if sub_batch_reads < 1:
             raise ValueError("`sub_batch_reads` must be at least 1")
         t0 = time.perf_counter()
-        fx = C.c_void_p()
-        rc = _ffi.MM355_EINVAL
-        if read_on_gpu:
-            rc = L.mm355_fastx_open_device(os.fsencode(reads_path), 1 if sam else 0, self._devices[0], C.byref(fx))
-        reader_on_device = rc == 0
-        if rc == _ffi.MM355_EINVAL:               # not asked for, or not a BGZF file: the host reader
-            rc = (L.mm355_fastx_open_qual if sam else L.mm355_fastx_open)(os.fsencode(reads_path), C.byref(fx))
-        if rc != 0:
-            raise RuntimeError("%s: %s" % (reads_path, L.mm355_strerror(rc).decode()))
-        if keep_aux is not None:                  # the tags to keep, and the header with the input's @RG lines
-            rc = L.mm355_fastx_keep_aux(fx, keep_aux)
-            if rc != 0:
-                L.mm355_fastx_close(fx)
-                raise RuntimeError("%s: %s" % (reads_path, L.mm355_strerror(rc).decode()))
-            n_rg = C.c_int64()
-            rg = L.mm355_fastx_bam_rg(fx, C.byref(n_rg))
-            if rg:
-                header = self.bam_header(compress, C.string_at(rg, n_rg.value), sort=sort)
-        part = os.fspath(out_path) + (b".part" if isinstance(os.fspath(out_path), bytes) else ".part")
-        bai_path = os.fspath(out_path) + (b".bai" if isinstance(os.fspath(out_path), bytes) else ".bai")
-        bai_part = bai_path + (b".part" if isinstance(bai_path, bytes) else ".part")
+        fx, reader_on_device, rg = self._open_reads(reads_path, kind != "paf", o)
+        suffix = (lambda x: x.encode()) if isinstance(os.fspath(out_path), bytes) else (lambda x: x)
+        part, bai_path = os.fspath(out_path) + suffix(".part"), os.fspath(out_path) + suffix(".bai")
+        bai_part = bai_path + suffix(".part")
+        tmp, bai = None, C.c_void_p()
+        n_index, seconds_index, seconds_merge = 0, 0.0, 0.0
         try:
+            header = self.sam_header() if kind == "sam" else self.bam_header(o.compress, rg, sort=o.sort) if kind == "bam" else b""
+            trailer = BAM_EOF if kind == "bam" else b""
+
+            def next_item():
+                rp = C.POINTER(_ffi.Reads)()
+                rc = L.mm355_fastx_next(fx, sub_batch_reads, SUB_BATCH_BASES, C.byref(rp))
+                if rc != 0:
+                    raise RuntimeError("%s: %s" % (reads_path, L.mm355_strerror(rc).decode()))
+                return rp if rp else None
+            work, free_result = self._file_work(kind, flags, int(where), o)
             out = open(part, "wb")          # (an unwritable path raises here: nothing has run, no file is left)
-        except BaseException:
-            L.mm355_fastx_close(fx)
-            raise
-        tokens = threading.Semaphore(2 * n_workers)     # one per sub-batch in existence, from the read to the written text
-        work = queue.Queue()
-        cv = threading.Condition()
-        done, errors, workers = {}, [], []
-        cancel = threading.Event()
-        st = {"n_sub": None, "n_reads": 0, "n_bases": 0, "n_aux": 0}
-        mo, where = self._mo, int(where)
-        acquire, release = self._ctx_acquire, self._ctx_release
-        map_records = L.mm355_map_batch_bam if kind == "bam" else L.mm355_map_batch_sam
-        if compress:
-            def map_records(*a):
-                return L.mm355_map_batch_bam_deflate(*a[:-1], 1, a[-1])
-        level = 1 if compress else 0
-        map_run = L.mm355_map_batch_bam_run_span if index else L.mm355_map_batch_bam_run
-        if tmp_compress:
-            def map_run(*a):
-                return L.mm355_map_batch_bam_run_packed(*a[:-1], 1 if index else 0, a[-1])
-
-        def fail(e):
-            errors.append(e)
-            cancel.set()
-            with cv:
-                cv.notify_all()
-
-        def worker(slot):
-            ctx = None
             try:
-                ctx = acquire(slot)
-                while True:
-                    item = work.get()
-                    if item is None:
-                        return
-                    k, rp = item
+                self._names()
+                if o.index:
+                    _ffi.check(L.mm355_bai_open(len(self._names()), len(header), C.byref(bai)))
+                out.write(header)
+                if o.sort:                  # (unlinked as soon as it is open: no exit path leaves it behind)
+                    tmp = tempfile.TemporaryFile(dir=os.fspath(o.tmp_dir) if o.tmp_dir is not None else os.path.dirname(os.path.abspath(os.fspath(out_path))))
+                sink = _RunSpool(tmp, o.index, o.tmp_compress) if o.sort else _TextSink(out)
+                n_reads = n_bases = n_aux = 0
+                with _pipeline.Pipeline(next_item, work, L.mm355_reads_free, free_result, self._ctx_acquire, self._ctx_release, n_workers, ordered=not o.sort) as pipe:
+                    for k, d in pipe:
+                        sink.take(k, d.tp)
+                        n_reads += d.n_reads; n_bases += d.n_bases; n_aux += d.n_aux
+                n_out = len(header) + len(trailer)
+                if o.sort:
+                    t_merge = time.perf_counter()
+                    n_merged, seconds_index = self._merge_spool(sink, out, 1 if o.compress else 0, bai if o.index else None)
+                    n_out += n_merged
+                    seconds_merge = time.perf_counter() - t_merge
+                else:
+                    n_out += sink.n_out
+                out.write(trailer)
+                out.close()
+                if o.index:                 # the whole index exists as a file before either name changes
+                    n_index, t_ix = self._write_bai(bai, bai_part)
+                    seconds_index += t_ix
+                os.replace(part, out_path)
+                if o.index:
+                    os.replace(bai_part, bai_path)
+            except BaseException:
+                out.close()
+                for p in (part, bai_part) if o.index else (part,):
                     try:
-                        if cancel.is_set():
-                            continue
-                        r = rp.contents
-                        n = int(r.n)
-                        n_bases = int(np.ctypeslib.as_array(r.lens, shape=(n,)).sum(dtype=np.int64))
-                        tp = C.POINTER(_ffi.Run if sort else _ffi.Text)()
-                        n_aux = 0
-                        if sort:
-                            ap = alen = amod = None
-                            if keep_aux is not None:
-                                alen, amod = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
-                                ap = L.mm355_reads_aux(rp, C.byref(alen), C.byref(amod))
-                                if ap:
-                                    n_aux = int(np.ctypeslib.as_array(alen, shape=(n,)).sum(dtype=np.int64))
-                            rc = map_run(ctx[1], C.byref(mo), n, r.seqs, r.lens, r.names, L.mm355_reads_quals(rp), ap, alen, amod, flags,
-                                                           sam_flags, where, C.byref(tp))
-                        elif keep_aux is not None:
-                            alen, amod = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
-                            ap = L.mm355_reads_aux(rp, C.byref(alen), C.byref(amod))
-                            if ap:
-                                n_aux = int(np.ctypeslib.as_array(alen, shape=(n,)).sum(dtype=np.int64))
-                            rc = L.mm355_map_batch_bam_aux(ctx[1], C.byref(mo), n, r.seqs, r.lens, r.names, L.mm355_reads_quals(rp), ap, alen, amod, flags,
-                                                           sam_flags, where, level, C.byref(tp))
-                        elif sam:
-                            rc = map_records(ctx[1], C.byref(mo), n, r.seqs, r.lens, r.names, L.mm355_reads_quals(rp), flags, sam_flags, where, C.byref(tp))
-                        else:
-                            rc = L.mm355_map_batch_paf(ctx[1], C.byref(mo), n, r.seqs, r.lens, r.names, flags, where, C.byref(tp))
-                    finally:
-                        L.mm355_reads_free(rp)
-                    if rc != 0:
-                        raise RuntimeError(L.mm355_strerror(rc).decode())
-                    with cv:
-                        st["n_reads"] += n
-                        st["n_bases"] += n_bases
-                        st["n_aux"] += n_aux
-                        done[k] = tp
-                        cv.notify_all()
-            except Exception as e:
-                fail(e)
-            finally:
-                if ctx is not None:
-                    release(ctx)
-
-        def reader():
-            k = 0
-            try:
-                while not cancel.is_set():
-                    if not tokens.acquire(timeout=0.2):
-                        continue
-                    rp = C.POINTER(_ffi.Reads)()
-                    rc = L.mm355_fastx_next(fx, sub_batch_reads, SUB_BATCH_BASES, C.byref(rp))
-                    if rc != 0:
-                        raise RuntimeError("%s: %s" % (reads_path, L.mm355_strerror(rc).decode()))
-                    if not rp:
-                        break
-                    work.put((k, rp))
-                    k += 1
-                    if len(workers) < min(n_workers, k):
-                        t = threading.Thread(target=worker, args=(len(workers),), daemon=True)
-                        workers.append(t)
-                        t.start()
-            except Exception as e:
-                fail(e)
-            finally:
-                for _ in workers:
-                    work.put(None)
-                with cv:
-                    st["n_sub"] = k
-                    cv.notify_all()
-
-        n_lines = n_dev = nxt = 0
-        n_out = len(header) + len(trailer)
-        ms_format = 0.0
-        rd = None
-        free_result = L.mm355_free_run if sort else L.mm355_free_text
-        tmp, runs, n_tmp, seconds_merge = None, {}, 0, 0.0       # sort: the spool file, per sub-batch (keys, lengths, place in the file), its bytes
-        n_tmp_raw = 0                                            # tmp_compress: the bytes of the records the spool's members hold
-        bai, n_index, seconds_index = C.c_void_p(), 0, 0.0       # index: the builder, the .bai's bytes, the builder's calls and the write
-        try:
-            self._names()
-            if index:
-                _ffi.check(L.mm355_bai_open(len(self._names()), len(header), C.byref(bai)))
-            out.write(header)
-            if sort:                        # (unlinked as soon as it is open: no exit path leaves it behind)
-                tmp = tempfile.TemporaryFile(dir=os.fspath(tmp_dir) if tmp_dir is not None else os.path.dirname(os.path.abspath(os.fspath(out_path))))
-            rd = threading.Thread(target=reader, daemon=True)
-            rd.start()
-            while True:
-                with cv:
-                    # in input order; the runs of a sorted file in completion order (nxt counts them)
-                    while not (done if sort else nxt in done) and not cancel.is_set() and (st["n_sub"] is None or nxt < st["n_sub"]):
-                        cv.wait(0.2)
-                    if cancel.is_set() or not (done if sort else nxt in done):
-                        break
-                    k_run = next(iter(done)) if sort else nxt
-                    tp = done.pop(k_run)
-                try:
-                    t = tp.contents
-                    if sort:
-                        n = int(t.n_rec)
-                        n_lines += n; n_dev += int(t.on_device); ms_format += float(t.ms_sort)
-                        keys = np.ctypeslib.as_array(t.key, shape=(n,)).copy() if n else np.zeros(0, np.uint64)
-                        lens = np.diff(np.ctypeslib.as_array(t.rec_off, shape=(n + 1,))) if n else np.zeros(0, np.int64)
-                        runs[k_run] = (keys, lens, n_tmp, np.ctypeslib.as_array(t.span, shape=(n,)).copy() if index and n else np.zeros(0, np.int64))
-                        if tmp_compress:        # a packed run: rec holds members; where each begins, and the raw bytes they hold
-                            runs[k_run] += (np.ctypeslib.as_array(t.blk_off, shape=(int(t.n_blk) + 1,)).copy(),)
-                            n_tmp_raw += int(t.rec_off[n])
-                        if t.n_bytes:
-                            tmp.write(memoryview((C.c_char * int(t.n_bytes)).from_address(C.addressof(t.rec.contents))))
-                        n_tmp += int(t.n_bytes)
-                    else:
-                        n_lines += int(t.n_lines); n_dev += int(t.on_device); ms_format += float(t.ms_format); n_out += int(t.n_text)
-                        out.write(_ffi.text_view(tp))
-                finally:
-                    free_result(tp)
-                    tokens.release()
-                nxt += 1
-            if errors:
-                raise errors[0]
-            if sort:
-                rd.join()
-                for t in workers:           # (their contexts are back in the pool: the merge takes one)
-                    t.join()
-                t_merge = time.perf_counter()
-                tix = [0.0]
-                merge = self._merge_packed_runs if tmp_compress else self._merge_runs
-                n_out += merge([runs[k] for k in sorted(runs)], tmp, n_tmp, out, level, bai if index else None, tix)
-                seconds_merge = time.perf_counter() - t_merge
-                seconds_index = tix[0]
-            out.write(trailer)
-            out.close()
-            if index:                       # the whole index exists as a file before either name changes
-                t_ix = time.perf_counter()
-                tp = C.POINTER(_ffi.Text)()
-                _ffi.check(L.mm355_bai_finish(bai, C.byref(tp)))
-                try:
-                    n_index = int(tp.contents.n_text)
-                    with open(bai_part, "wb") as f:
-                        f.write(_ffi.text_view(tp))
-                finally:
-                    L.mm355_free_text(tp)
-                seconds_index += time.perf_counter() - t_ix
-            os.replace(part, out_path)
-            if index:
-                os.replace(bai_part, bai_path)
-        except BaseException:
-            cancel.set()
-            out.close()
-            for p in (part, bai_part) if index else (part,):
-                try:
-                    os.remove(p)
-                except OSError:
-                    pass
-            raise
+                        os.remove(p)
+                    except OSError:
+                        pass
+                raise
         finally:
-            if rd is not None:
-                rd.join()
-            for t in workers:
-                t.join()
-            while not work.empty():           # what nobody took: reads of sub-batches after the failure
-                item = work.get()
-                if item is not None:
-                    L.mm355_reads_free(item[1])
-            for tp in done.values():
-                free_result(tp)
             if tmp is not None:
                 tmp.close()
             if bai:
                 L.mm355_bai_close(bai)
             L.mm355_fastx_close(fx)
-        res = {"n_reads": st["n_reads"], "n_bases": st["n_bases"], "n_lines": n_lines, "n_sub_batches": st["n_sub"],
-               "seconds": time.perf_counter() - t0, "ms_format": ms_format, "n_on_device": n_dev}
-        if compress:
+        res = {"n_reads": n_reads, "n_bases": n_bases, "n_lines": sink.n_lines, "n_sub_batches": pipe.n_items,
+               "seconds": time.perf_counter() - t0, "ms_format": sink.ms_format, "n_on_device": sink.n_dev}
+        if o.compress:
             res["n_bytes_out"] = n_out
-        if read_on_gpu:
+        if o.read_on_gpu:
             res["reader_on_device"] = reader_on_device
-        if keep_aux is not None:
-            res["n_aux_bytes"] = st["n_aux"]
-        if sort:
-            res["n_runs"], res["seconds_merge"], res["n_tmp_bytes"] = len(runs), seconds_merge, n_tmp
-        if index:
+        if o.keep_aux is not None:
+            res["n_aux_bytes"] = n_aux
+        if o.sort:
+            res["n_runs"], res["seconds_merge"], res["n_tmp_bytes"] = len(sink.runs), seconds_merge, sink.n_tmp
+        if o.index:
             res["n_index_bytes"], res["seconds_index"] = n_index, seconds_index
-        if tmp_compress:
-            res["n_tmp_raw_bytes"] = n_tmp_raw
+        if o.tmp_compress:
+            res["n_tmp_raw_bytes"] = sink.n_raw
         return res
-
-    def _merge_runs(self, runs, tmp, n_tmp, out, level, bai=None, t_index=None):
-        """the merge phase of map_bam_file(sort=True).  runs: per sub-batch, in input order, (keys, lengths, place of its records in tmp), the
-        records of a run in key order; tmp: the spool file of n_tmp bytes.  The stable argsort of the concatenated keys is the k-way merge
-        -- and the stable sort of the unsorted file, because ties inside a run are in input order already.  Writes the BGZF blocks of the
-        sorted stream to `out` and returns their bytes.  Array operations and one library call per step: no Python work per record.
-        bai: the .bai builder -- it gets the ordered keys, spans (a run's fourth entry) and lengths once, and every step's blocks as they
-        are written; t_index[0] collects the seconds of those calls"""
-        L = self._L
-        keys = np.concatenate([r[0] for r in runs]) if runs else np.zeros(0, np.uint64)
-        lens = np.concatenate([r[1] for r in runs]).astype(np.int64, copy=False) if runs else np.zeros(0, np.int64)
-        if len(keys) == 0:
-            return 0
-        src = np.concatenate([r[2] + np.cumsum(r[1], dtype=np.int64) - r[1] for r in runs])
-        order = np.argsort(keys, kind="stable")
-        lens, src = np.ascontiguousarray(lens[order]), np.ascontiguousarray(src[order])
-        if bai is not None:
-            t_ix = time.perf_counter()
-            keys, spans = np.ascontiguousarray(keys[order]), np.ascontiguousarray(np.concatenate([r[3] for r in runs])[order])
-            _ffi.check(L.mm355_bai_records(bai, keys.ctypes.data, spans.ctypes.data, lens.ctypes.data, len(lens)))
-            t_index[0] += time.perf_counter() - t_ix
-        end_at = np.cumsum(lens)                         # the sorted stream's offset behind every record
-        tmp.flush()
-        spool = np.memmap(tmp, dtype=np.uint8, mode="r", shape=(n_tmp,))
-        dev_ctx = self._ctx_acquire(0) if level else None   # the deflate kernels need a context; stored blocks are framed on the host
-        n_out, carry = 0, np.zeros(0, np.uint8)
-        try:
-            i, n = 0, len(lens)
-            while i < n:
-                base = int(end_at[i - 1]) if i else 0
-                j = max(i + 1, int(np.searchsorted(end_at, base + SORT_CHUNK_BYTES, side="right")))
-                n_new = int(end_at[j - 1]) - base
-                buf = np.empty(len(carry) + n_new, np.uint8)
-                buf[:len(carry)] = carry
-                _ffi.check(L.mm355_bam_gather(spool.ctypes.data, n_tmp, src[i:j].ctypes.data, lens[i:j].ctypes.data, j - i, buf.ctypes.data + len(carry), n_new))
-                # whole payloads now; what is left opens the next step's buffer (the last step writes everything)
-                n_now = len(buf) if j == n else len(buf) // 0xff00 * 0xff00
-                if n_now:
-                    tp = C.POINTER(_ffi.Text)()
-                    _ffi.check(L.mm355_bgzf_deflate(dev_ctx[1] if level else None, C.cast(buf.ctypes.data, C.c_char_p), n_now, _ffi.PAF_DEVICE if level else _ffi.PAF_HOST,
-                                                    level, C.byref(tp)))
-                    try:
-                        n_out += int(tp.contents.n_text)
-                        out.write(_ffi.text_view(tp))
-                        if bai is not None:
-                            t_ix = time.perf_counter()
-                            _ffi.check(L.mm355_bai_blocks(bai, C.addressof(tp.contents.text.contents), int(tp.contents.n_text)))
-                            t_index[0] += time.perf_counter() - t_ix
-                    finally:
-                        L.mm355_free_text(tp)
-                carry = buf[n_now:].copy()
-                i = j
-        finally:
-            del spool
-            if dev_ctx is not None:
-                self._ctx_release(dev_ctx)
-        return n_out
-
-    def _merge_packed_runs(self, runs, tmp, n_tmp, out, level, bai=None, t_index=None):
-        """_merge_runs for packed runs (map_bam_file(tmp_compress=True)).  runs: per sub-batch, in input order, (keys, lengths, place of
-        its MEMBERS in tmp, spans, the members' offsets); tmp: the spool of n_tmp bytes of BGZF members.  The same stable argsort.  A
-        step is a contiguous range of the merged order, so it takes from every run a contiguous range of that run's records: record
-        counts per run (a bincount) and a running count of what earlier steps took give the raw range [lo, hi) each run contributes, the
-        members [lo // 0xff00, ceil(hi / 0xff00)) hold it, and one mm355_bam_merge_step call turns the slices and the records' places
-        into the step's blocks.  Array operations and one library call per step: no Python work per record or per member.
-        `where` is always MM355_PAF_DEVICE, on a context of the aligner's first device (an Aligner always has one): the host `where`
-        of mm355_bam_merge_step is the C-ABI's and the tests', and this route never uses it."""
-        L = self._L
-        keys = np.concatenate([r[0] for r in runs]) if runs else np.zeros(0, np.uint64)
-        lens = np.concatenate([r[1] for r in runs]).astype(np.int64, copy=False) if runs else np.zeros(0, np.int64)
-        if len(keys) == 0:
-            return 0
-        P = 0xff00
-        n_runs = len(runs)
-        counts = np.array([len(r[0]) for r in runs], np.int64)
-        run_of = np.repeat(np.arange(n_runs, dtype=np.int64), counts)
-        raw_all = np.concatenate([np.concatenate(([0], np.cumsum(r[1], dtype=np.int64))) for r in runs])     # per run its n + 1 raw offsets
-        raw_first = np.cumsum(counts + 1) - (counts + 1)
-        at = np.concatenate([np.cumsum(r[1], dtype=np.int64) - r[1] for r in runs])                        # a record's place in its run's unframed stream
-        blk_all = np.concatenate([r[4] for r in runs]).astype(np.int64, copy=False)                        # per run its n_blk + 1 member offsets
-        blk_n = np.array([len(r[4]) for r in runs], np.int64)
-        blk_first = np.cumsum(blk_n) - blk_n
-        place = np.array([r[2] for r in runs], np.int64)
-        order = np.argsort(keys, kind="stable")
-        lens, at, run_of = np.ascontiguousarray(lens[order]), np.ascontiguousarray(at[order]), run_of[order]
-        if bai is not None:
-            t_ix = time.perf_counter()
-            keys, spans = np.ascontiguousarray(keys[order]), np.ascontiguousarray(np.concatenate([r[3] for r in runs])[order])
-            _ffi.check(L.mm355_bai_records(bai, keys.ctypes.data, spans.ctypes.data, lens.ctypes.data, len(lens)))
-            t_index[0] += time.perf_counter() - t_ix
-        end_at = np.cumsum(lens)                         # the sorted stream's offset behind every record
-        tmp.flush()
-        spool = np.memmap(tmp, dtype=np.uint8, mode="r", shape=(n_tmp,))
-        dev_ctx = self._ctx_acquire(0)                   # inflate, gather and the blocks on the device, whatever the level
-        n_out = 0
-        carry, n_carry = np.empty(P, np.uint8), C.c_int64(0)
-        taken = np.zeros(n_runs, np.int64)               # the records of every run that earlier steps took
-        slice_of_run = np.empty(n_runs, np.int32)
-        try:
-            i, n = 0, len(lens)
-            while i < n:
-                base = int(end_at[i - 1]) if i else 0
-                j = max(i + 1, int(np.searchsorted(end_at, base + SORT_CHUNK_BYTES, side="right")))
-                took = np.bincount(run_of[i:j], minlength=n_runs)
-                sel = np.flatnonzero(took)
-                lo, hi = raw_all[raw_first[sel] + taken[sel]], raw_all[raw_first[sel] + taken[sel] + took[sel]]
-                m_lo, m_hi = lo // P, (hi + P - 1) // P
-                b_lo, b_hi = blk_all[blk_first[sel] + m_lo], blk_all[blk_first[sel] + m_hi]
-                slice_at, slice_bytes, slice_raw_at = np.ascontiguousarray(place[sel] + b_lo), np.ascontiguousarray(b_hi - b_lo), np.ascontiguousarray(m_lo * P)
-                slice_of_run[sel] = np.arange(len(sel), dtype=np.int32)
-                rec_slice = np.ascontiguousarray(slice_of_run[run_of[i:j]])
-                taken += took
-                tp = C.POINTER(_ffi.Text)()
-                _ffi.check(L.mm355_bam_merge_step(dev_ctx[1], spool.ctypes.data, n_tmp, slice_at.ctypes.data, slice_bytes.ctypes.data, slice_raw_at.ctypes.data, len(sel),
-                                                  rec_slice.ctypes.data, at[i:j].ctypes.data, lens[i:j].ctypes.data, j - i, carry.ctypes.data, n_carry.value,
-                                                  1 if j == n else 0, _ffi.PAF_DEVICE, level, C.byref(tp), carry.ctypes.data, C.byref(n_carry)))
-                try:
-                    if tp.contents.n_text:
-                        n_out += int(tp.contents.n_text)
-                        out.write(_ffi.text_view(tp))
-                        if bai is not None:
-                            t_ix = time.perf_counter()
-                            _ffi.check(L.mm355_bai_blocks(bai, C.addressof(tp.contents.text.contents), int(tp.contents.n_text)))
-                            t_index[0] += time.perf_counter() - t_ix
-                finally:
-                    L.mm355_free_text(tp)
-                i = j
-        finally:
-            del spool
-            self._ctx_release(dev_ctx)
-        return n_out
 
     def _stage_runner(self):
         """per-stage access to the same kernels (parity tests, kernel bench)"""

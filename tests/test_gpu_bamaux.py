@@ -141,7 +141,7 @@ def test_null_aux_is_the_call_without_it(stage, world):
     for level in (0, 1):
         for where in (_ffi.PAF_HOST, _ffi.PAF_DEVICE):
             old = al.map_bam(reads, names=names, quals=quals, cs=True, where=where, compress=bool(level))
-            new = al._map_records(lambda *a: L.mm355_map_batch_bam_aux(*a[:7], None, None, None, *a[7:-1], level, a[-1]), reads, names, quals, True, False, False, False, where)
+            new = al._map_records(reads, names, quals, al._sam_flags(True, False), 0, where, mappy_rs._Entry(L.mm355_map_batch_bam_aux, True, True, (level,), _ffi.Text))
             assert new == old and len(old) > 1000
             assert al.map_bam(reads, names=names, quals=quals, cs=True, where=where, compress=bool(level), aux=[None] * len(reads)) == old
 
