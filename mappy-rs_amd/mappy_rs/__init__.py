@@ -12,13 +12,14 @@ Aligner that maps reads requires the HIP library and a visible MI355X -- there i
 """
 import collections
 import collections.abc
+import contextlib
 import ctypes as C
+import functools
 import os
 import struct
 import tempfile
 import threading
 import time
-import weakref
 
 # ROCclr multiplexes all HIP streams over GPU_MAX_HW_QUEUES hardware queues (default 4); the pipelined map_batch keeps several contexts in
 # flight and measures best with 8 (bench.py sets the same).  Only effective if the HIP runtime has not been started yet.
@@ -26,7 +27,8 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import numpy as np
 
-from . import _ffi, _pipeline
+from . import _batch, _ffi, _pipeline
+from ._batch import AlignmentBatchResultIter
 
 __all__ = ["Aligner", "Mapping", "paf_line", "sam_lines", "shard_by_bases", "order_by_length", "bgzf_unwrap", "bam_aux_split"]
 
@@ -469,120 +471,6 @@ def order_by_length(lengths):
     return np.argsort(-np.asarray(lengths, dtype=np.int64), kind="stable").tolist()
 
 
-class _Channel:
-    """bounded multi-producer channel (the reference's ArrayQueue(50000) + crossbeam `bounded(20000)`, lib.rs:430, 950): producers block while it is full, the consumer blocks
-    while it is empty; both waits release the GIL."""
-
-    def __init__(self, cap):
-        self.cap = cap
-        self.d = collections.deque()
-        self.cv = threading.Condition()
-
-    def put_many(self, items, cancel):
-        """appends the entries in order, waiting whenever the channel is full; False when `cancel` was set while waiting"""
-        i, n = 0, len(items)
-        with self.cv:
-            while i < n:
-                while len(self.d) >= self.cap:
-                    if cancel.is_set():
-                        return False
-                    self.cv.wait(0.2)
-                room = self.cap - len(self.d)
-                self.d.extend(items[i:i + room])
-                i += room
-                self.cv.notify_all()
-        return True
-
-    def get(self):
-        with self.cv:
-            while not self.d:
-                self.cv.wait()
-            x = self.d.popleft()
-            if len(self.d) == self.cap - 1:
-                self.cv.notify_all()      # a producer may be waiting for room
-            return x
-
-    def get_many(self, limit):
-        """blocks until at least one entry is there, then takes up to `limit` of them under ONE lock acquisition (a lock per result was a
-        microsecond and a half of the consumer's GIL time per read)"""
-        with self.cv:
-            while not self.d:
-                self.cv.wait()
-            was_full = len(self.d) >= self.cap
-            n = min(limit, len(self.d))
-            out = [self.d.popleft() for _ in range(n)]
-            if was_full:
-                self.cv.notify_all()      # producers may be waiting for room
-            return out
-
-    def __len__(self):
-        return len(self.d)
-
-
-class _BatchState:
-    """Everything the worker threads and the collector of one map_batch call share.  The threads hold THIS object, never the iterator
-    the caller gets: when the caller drops the iterator (or calls close()) a weakref finalizer sets `cancel` / `abandoned` here, the
-    workers blocked on the full result channel give up, return their GPU contexts to the Aligner's pool and exit -- the reference's
-    workers stop the same way when their `tx.send` fails because the receiver is gone."""
-
-    def __init__(self):
-        self.ch = _Channel(RESULT_CHANNEL_CAP)
-        self.cancel = threading.Event()      # workers stop taking sub-batches (worker error, validation error, abandoned iterator)
-        self.abandoned = threading.Event()   # nobody will ever read the channel again
-        self.errors = []
-        self.n_sub_batches = 0
-        self.t_sub_done = []      # wall-clock time each sub-batch left the GPU pipeline (tests / latency diagnostics)
-        self.threads = []         # workers + collector (tests: they must all exit once the iterator is gone)
-
-    def close(self):
-        self.cancel.set()
-        self.abandoned.set()
-
-
-class AlignmentBatchResultIter:
-    """Iterator returned by map_batch (lib.rs:923-991): yields (list[Mapping], dict) in COMPLETION order.
-
-    Mirrors the reference's plumbing: workers push results into a bounded channel (RESULT_CHANNEL_CAP entries, lib.rs:430 + 950) and `__next__`
-    blocks on it (`rx.recv()`, lib.rs:973) -- here with the GIL released.  A full channel blocks the workers: a slow consumer holds
-    back the GPU pipeline instead of growing memory (back-pressure).  `Finished` arrives after every worker is done (lib.rs:804-815)."""
-
-    _FINISHED = object()
-
-    def __init__(self, state=None):
-        self._st = state if state is not None else _BatchState()
-        self._done = False
-        self._buf = []            # results taken from the channel in one go, handed out one by one (reversed: pop() from the end)
-        self.t_first_yield = None
-        self._fin = weakref.finalize(self, _BatchState.close, self._st)   # the state, not the iterator, is what the threads keep alive
-
-    n_sub_batches = property(lambda s: s._st.n_sub_batches)
-    t_sub_done = property(lambda s: s._st.t_sub_done)
-
-    def __iter__(self):
-        return self
-
-    def __next__(self):
-        if self._done:
-            raise StopIteration("Finished")
-        if not self._buf:
-            self._buf = self._st.ch.get_many(2048)
-            self._buf.reverse()
-        r = self._buf.pop()
-        if r is AlignmentBatchResultIter._FINISHED:
-            self._done = True
-            if self._st.errors:
-                raise self._st.errors[0]
-            raise StopIteration("Finished")
-        if self.t_first_yield is None:
-            self.t_first_yield = time.perf_counter()
-        return r
-
-    def close(self):
-        """stop mapping what has not been started yet; results already produced are dropped"""
-        self._st.close()
-
-
-
 def _cs_flag(cs):
     """the flag bits of a `cs=` argument: False (no cs), True or "short" (minimap2 --cs, `:123*ag+tt-c`), "long" (--cs=long, `=ACGT*ag+tt-c`:
     the matched bases spelled out, what tools that rebuild both sequences of an alignment need).  Anything else: ValueError."""
@@ -943,13 +831,10 @@ class Aligner:
         names: query names (str or None per read); None or all None = the unnamed call"""
         L = self._L
         packed, narr = _ffi.pack_reads(seqs), _ffi.pack_names(names)
-        if ctx is None:
-            with self._lock:
-                rc, hp = _ffi.call_map(L, self._context(), self._mo, packed, flags, narr)
-        else:
-            rc, hp = _ffi.call_map(L, ctx, self._mo, packed, flags, narr)
-        if rc != 0:
-            raise RuntimeError(L.mm355_strerror(rc).decode())
+        own = ctx is None               # the Aligner's own context is shared: under the lock
+        with self._lock if own else contextlib.nullcontext():
+            rc, hp = _ffi.call_map(L, self._context() if own else ctx, self._mo, packed, flags, narr)
+        _ffi.check(rc)
         return _batch_to_mappings(_ffi.take_hits(L, hp, len(seqs)), len(seqs), self._names(), chain_only=not self._mo.flag & 4)
 
     def _names(self):
@@ -966,9 +851,7 @@ class Aligner:
             if free:
                 return dev, free.pop()
         ctx = C.c_void_p()
-        rc = self._L.mm355_ctx_create(self._idx, dev, C.byref(ctx))
-        if rc != 0:
-            raise RuntimeError(self._L.mm355_strerror(rc).decode())
+        _ffi.check(self._L.mm355_ctx_create(self._idx, dev, C.byref(ctx)))
         return dev, ctx
 
     def _ctx_release(self, dev_ctx):
@@ -1021,7 +904,6 @@ class Aligner:
         if isinstance(seqs, (dict, str, bytes)) or not (isinstance(seqs, (list, tuple, collections.abc.Sequence)) or
                                                         isinstance(seqs, collections.abc.Iterator)):
             raise TypeError("Unsupported batch type, pass a list, iter, generator or tuple")
-        st = _BatchState()
         max_workers = max(1, min(self._n_threads, 8)) * len(self._devices)
         try:
             n_known = len(seqs)
@@ -1029,17 +911,11 @@ class Aligner:
             n_known = None
         # sub-batch size: at most SUB_BATCH_READS; small inputs are cut finer so that every worker gets about two sub-batches (16384 reads:
         # 1024 per sub-batch maps 20 % faster than 4096).  Unknown length (iterators): ramp up, so that the first results leave early.
-        sb_fixed = None if n_known is None else min(SUB_BATCH_READS, max(1024, -(-n_known // (2 * max_workers))))
+        sb_reads = SUB_BATCH_READS
+        sb_fixed = None if n_known is None else min(sb_reads, max(1024, -(-n_known // (2 * max_workers))))
 
-        def sb_size(k):
-            return sb_fixed if sb_fixed is not None else min(SUB_BATCH_READS, 512 << min(4, k // max_workers))
-
-        work = collections.deque()          # sub-batches (reads, items) waiting for a worker
-        cv = threading.Condition()
-        state = {"closed": False, "n_sub": 0, "pending": 0}     # pending: reads in `work`, not yet taken by a worker
-        workers = st.threads
-        self._names()                       # fill the name cache before the workers read it
-        map_many, acquire, release = self._map_many, self._ctx_acquire, self._ctx_release
+        def size_of(k):
+            return sb_fixed if sb_fixed is not None else min(sb_reads, 512 << min(4, k // max_workers))
         name_key = self._name_key
 
         def names_of(items):
@@ -1053,123 +929,21 @@ class Aligner:
                 raise ValueError("`%s` must be a string" % (name_key,))
             return names
         out_flags = (cs_flag if self._mo.flag & 4 else 0) | self._tag_flag        # chain-only: no cs string to produce
-
-        # (the closures below capture `st`, never the iterator handed to the caller)
-        def worker(slot):
-            ctx = None
-            try:
-                ctx = acquire(slot)
-                while True:
-                    with cv:
-                        while not work and not state["closed"] and not st.cancel.is_set():
-                            cv.wait(0.2)
-                        if st.cancel.is_set() or not work:
-                            return
-                        reads, items, names = work.popleft()
-                        state["pending"] -= len(reads)
-                        cv.notify_all()                                   # the producer may be waiting for room (back-off)
-                    # cs=true, MD=false: lib.rs:589-590
-                    maps = map_many(reads, out_flags, ctx[1]) if names is None else map_many(reads, out_flags, ctx[1], names=names)
-                    st.t_sub_done.append(time.perf_counter())
-                    # a worker error on one read => no result for that id (lib.rs:621-623)
-                    out = [(m, it) for m, it in zip(maps, items) if not isinstance(m, Exception)]
-                    if not st.ch.put_many(out, st.cancel):
-                        return
-            except Exception as e:   # surfaced by the iterator when it finishes, like a worker panic in the reference
-                st.errors.append(e)
-                st.cancel.set()
-            finally:
-                if ctx is not None:
-                    release(ctx)
-
-        def dispatch(reads, items):
-            names = names_of(items)           # (raises in the caller's thread, before the sub-batch is queued)
-            with cv:
-                # the reference's work queue holds 50 000 reads (lib.rs:429): with back-off the producer sleeps until the workers have
-                # made room (lib.rs:870-888), so a huge iterable never sits in memory as pending sub-batches
-                # (not while the result channel is full: nobody reads it before map_batch has returned, so the workers cannot make room)
-                while (back_off and state["pending"] > 0 and state["pending"] + len(reads) > WORK_QUEUE_CAP and not st.cancel.is_set()
-                       and len(st.ch) < RESULT_CHANNEL_CAP):
-                    cv.wait(0.05)
-                work.append((reads, items, names))
-                state["pending"] += len(reads)
-                state["n_sub"] += 1
-                cv.notify()
-            if len(workers) < max_workers and len(workers) < state["n_sub"]:
-                t = threading.Thread(target=worker, args=(len(workers),), daemon=True)
-                workers.append(t)
-                t.start()
-
-        def close_and_join():
-            with cv:
-                state["closed"] = True
-                cv.notify_all()
-            for t in list(workers):
-                t.join()
-
-        cur_reads, cur_items, cur_bases = [], [], 0
-        sb_limit = sb_size(0)
-        n_fast = 0
+        self._names()                       # fill the name cache before the workers read it
+        # the caps are module globals read per call (tests and tools set them); the cut and the engine of mappy_rs/_batch.py get them as arguments
+        run = _batch.BatchRun(functools.partial(self._map_sub, out_flags), self._ctx_acquire, self._ctx_release, max_workers,
+                              WORK_QUEUE_CAP, RESULT_CHANNEL_CAP, back_off)
         try:
-            # lists and tuples of plain dicts with str sequences -- what a FASTQ reader hands over -- are cut a sub-batch at a time with
-            # C-level loops (0.4 us per read instead of 2 under the interpreter: the producer shares the GIL with the workers' result
-            # building).  Anything else -- another element type, a missing key, a sub-batch over the base limit, the capacity rule without
-            # back-off -- leaves the remainder to the element-wise loop below, which raises what the reference raises, at the same element.
-            if isinstance(seqs, (list, tuple)) and (back_off or len(seqs) <= WORK_QUEUE_CAP):
-                n_all = len(seqs)
-                while n_fast < n_all:
-                    chunk = seqs[n_fast:n_fast + sb_limit]
-                    if set(map(type, chunk)) != {dict}:
-                        break
-                    try:
-                        reads = [it["seq"] for it in chunk]
-                    except KeyError:
-                        break
-                    if set(map(type, reads)) != {str} or sum(map(len, reads)) > SUB_BATCH_BASES:
-                        break
-                    dispatch(reads, list(map(dict, chunk)))   # the reference hands back its own copy of the dict (lib.rs:849-855, 977-979)
-                    n_fast += len(chunk)
-                    sb_limit = sb_size(state["n_sub"])
-                if n_fast:
-                    seqs = seqs[n_fast:]
-            for n_pending, item in enumerate(seqs, n_fast):
-                if not isinstance(item, dict):
-                    raise TypeError("Element in iterable is not a dictionary")
-                if "seq" not in item:
-                    raise KeyError("AHHH Key \U0001F5DD\uFE0F  not found in iterated dictionary")
-                s = item["seq"]
-                if not isinstance(s, str):
-                    raise ValueError("`seq` must be a string")
-                # capacity rule made deterministic: without back-off more than 50 000 pending items is an error
-                if not back_off and n_pending >= WORK_QUEUE_CAP:
-                    raise RuntimeError("Internal error adding data to work queue, without backoff. "
-                                       "Is your fastq batch larger than 50000? Perhaps try `map_batch` with back_off=True?")
-                if len(cur_reads) >= sb_limit or cur_bases + len(s) > SUB_BATCH_BASES:
-                    if cur_reads:
-                        dispatch(cur_reads, cur_items)
-                        cur_reads, cur_items, cur_bases = [], [], 0
-                        sb_limit = sb_size(state["n_sub"])
-                cur_reads.append(s)
-                cur_items.append(dict(item))      # the reference hands back its own copy of the dict (lib.rs:849-855, 977-979)
-                cur_bases += len(s)
-            if cur_reads:
-                dispatch(cur_reads, cur_items)
+            for reads, items in _batch.sub_batches(seqs, size_of, SUB_BATCH_BASES, WORK_QUEUE_CAP, back_off):
+                run.submit(reads, items, names_of(items))     # (names_of raises in the caller's thread, before the sub-batch is queued)
         except BaseException:
-            st.close()                            # nothing is yielded: the workers stop after their current sub-batch
-            close_and_join()
+            run.abort()                     # nothing is yielded: the workers stop after their current sub-batch
             raise
-        st.n_sub_batches = state["n_sub"]
+        return run.finish()
 
-        def finalize():                           # the reference's collector thread: `Finished` once every worker is done (lib.rs:804-815)
-            close_and_join()
-            while not st.ch.put_many([AlignmentBatchResultIter._FINISHED], st.abandoned):
-                if st.abandoned.is_set():
-                    return
-
-        tf = threading.Thread(target=finalize, daemon=True)
-        tf.start()
-        st.threads = list(workers) + [tf]
-        return AlignmentBatchResultIter(st)
+    def _map_sub(self, flags, dev_ctx, reads, names):
+        """one sub-batch of map_batch on a worker's (device, context); cs=true, MD=false: lib.rs:589-590"""
+        return self._map_many(reads, flags, dev_ctx[1]) if names is None else self._map_many(reads, flags, dev_ctx[1], names=names)
 
     # ---- PAF text (mm355_map_batch_paf): the lines of mappy_rs.paf_line, formatted by the library -- on the device for large batches
     def _paf_flags(self, cs, MD):
